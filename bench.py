@@ -8,8 +8,12 @@ heads), ZINB NLL + gradient, full backward, clipvalue + RMSprop.  Inputs are res
 before the timed region starts.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torchrun)
+  python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, DIR/<name>.npy)
+  python bench.py ... --full                             (+ everything below)
 
-Prints ONE JSON line on rank 0 (contract in the repository task statement), with
+Prints ONE JSON line on rank 0: metric, value (cells/s), unit, higher_is_better, dtype, ms_per_step (one timed step),
+steps, warmup, config, loss_first / loss_last.  A plain run sets up, warms up, times the K steps and stops there; with
+--full the line also holds
   roofline      the dominant kernel: HIP events around each of its launches (on the launch stream).  With the step
                 replayed as a hipGraph the individual launches are invisible, so the events come from eager steps of
                 the same workload run right AFTER the timed region (config.launch says which); the rocprofv3
@@ -85,7 +89,35 @@ def parse():
     ap.add_argument('--graph', type=str, default='auto', choices=['auto', 'on', 'off'])
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure per-kernel timing and roofline, the epoch and batch-32 figures, '
+                         'the CPU baseline (one GPU) and the exposed communication (N GPUs)')
+    ap.add_argument('--dump-outputs', type=str, default='', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy')
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # under 64 MB with room for the .npy headers
+
+
+def dump_outputs(eng, d, seed=0):
+    """What a caller of the timed step holds after its last step: the updated parameters and BN moving statistics
+    (Engine.get_params), that step's gradient (Engine.get_grads, as grad_<name>) and its loss, as d/<name>.npy in float32.
+    Over DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements: a seeded sample of the flattened
+    array, in index order, identical from run to run for the same shapes."""
+    out = dict(eng.get_params())
+    out.update(('grad_' + k, v) for k, v in eng.get_grads().items())
+    out['loss'] = eng.g[eng.lay.P:eng.lay.P + 1].cpu().numpy()
+    total = sum(v.size for v in out.values()) * 4
+    frac = min(1.0, DUMP_LIMIT_BYTES / float(total))
+    rng = np.random.default_rng(seed)
+    os.makedirs(d, exist_ok=True)
+    for k in sorted(out):
+        v = np.ascontiguousarray(out[k], dtype=np.float32)
+        if frac < 1.0:
+            n = max(1, int(v.size * frac))
+            v = v.reshape(-1)[np.sort(rng.choice(v.size, n, replace=False))] if n < v.size else v.reshape(-1)
+        np.save(os.path.join(d, k + '.npy'), v)
 
 
 _SPIN = {}
@@ -529,7 +561,7 @@ def main():
         runner.run(runner.spe - (runner.k % runner.spe))   # untimed: to the end of the epoch, first replay of every graph
         runner.run(runner.spe)                             # untimed: one whole epoch through the graphs
         runner.run(K, capture_only=True)                   # (a K that ends inside an epoch needs a shorter graph)
-        if not use_graph:
+        if not use_graph and args.full:
             prof = EventProfiler(); eng.prof = prof
         barrier()
         t_start = time.perf_counter()
@@ -561,12 +593,13 @@ def main():
         eng.cursor.zero_(); eng.acc.zero_()
         for i in range(args.warmup):
             eng.train_step(B, B * W, counts, B)
-        # exposed communication of the EAGER step: what the compute stream spent inside (or waiting for) each exchange
-        comm.timer = {}
-        for i in range(8):
-            eng.train_step(B, B * W, counts, B)
-        comm_ms = {k: {'calls_per_step': v[0] / 8, 'ms_per_step': v[1] / 8} for k, v in comm.timer_summary().items()}
-        comm.timer = None
+        if args.full:
+            # exposed communication of the EAGER step: what the compute stream spent inside (or waiting for) each exchange
+            comm.timer = {}
+            for i in range(8):
+                eng.train_step(B, B * W, counts, B)
+            comm_ms = {k: {'calls_per_step': v[0] / 8, 'ms_per_step': v[1] / 8} for k, v in comm.timer_summary().items()}
+            comm.timer = None
         use_graph = args.graph != 'off' and eng.cfg.dp_graph and getattr(comm, 'capturable', False)
         graphs = {}
         if use_graph:
@@ -587,7 +620,7 @@ def main():
             torch.cuda.synchronize()
             if not bool(torch.isfinite(eng.g[eng.lay.P]).item()):
                 raise SystemExit('bench: the replayed data-parallel steps left a non-finite loss')
-        else:
+        elif args.full:
             prof = EventProfiler(); eng.prof = prof
         barrier()
         t_start = time.perf_counter()
@@ -613,124 +646,129 @@ def main():
     loss_last = float(eng.g[eng.lay.P].item())
     loss_first = float(eng.hist[0].item())
 
-    # ---- per-kernel timing (HIP events on the launch stream)
-    ksum = prof.summary() if prof is not None else {}
-    if use_graph:
-        # graph replay hides individual launches: time the dominant kernels in isolation (eager full-batch steps)
-        eng.prof = EventProfiler()
-        eng.cursor.zero_()
-        # The events must see a GPU that is never waiting for the host: a Python-level launch costs 10 - 20 us, a scope of three
-        # launches between two event records would otherwise include the host's gaps (measured: K-HEADS' scope 0.79 ms against
-        # 0.705 ms for its three kernels under rocprofv3).  The device is parked on a spin kernel while the host enqueues all the
-        # profiled steps.
-        n_prof = min(steps_timed, 16, n_local // B)
-        _park_device(30.0)
-        for i in range(n_prof):
-            eng.train_step(B, B * W, counts, B)
-        ksum = eng.prof.summary(); eng.prof = None
-    # The dominant operation once more, as the product launches it: ten consecutive launches captured into ONE hipGraph, replayed
-    # between two events.  (Events round every scope of an eager step cost a barrier packet each: the scope of K-HEADS' three
-    # launches reads 0.76 - 0.79 ms that way against 0.70 ms for the same three kernels under rocprofv3.)
-    graph_ms = {}
-    last = getattr(eng, '_last_heads_args', None)
-    if last is not None and last[0] == B and not multi:       # (one process only: nothing new is captured beside live communicators)
-        try:
-            if eng.ws_heads is not None:
-                graph_ms['heads_fused'] = _graph_timed(lambda: eng.heads_fused_launch(*last))
-            else:
-                graph_ms['gemm_heads_fwd'] = _graph_timed(lambda: eng._heads_forward(last[0], last[1]))
-        except Exception as exc:                           # (never fatal for the bench line: the event figure stays)
-            sys.stderr.write('[bench] graph timing of the dominant operation failed: %r\n' % (exc,))
-    kernels = []
-    # 16-bit matrix products spent per fp32 product: K-HEADS and the wide networks' plane GEMMs run on two fp16 pieces and three
-    # products (round 6); the first layer from the byte store (and the three-piece planes) on three bf16 pieces and six
-    wide_h2 = bool(getattr(eng, '_h2', None) and eng.pl is not None and eng._h2(B))
-    ppp = {'heads_fused': 3}
-    for nm in ('gemm_heads_fwd', 'gemm_heads_dW', 'gemm_heads_dH', 'gemm_enc0_fwd', 'gemm_enc0_dW'):
-        ppp[nm] = 3 if wide_h2 else 6
-    for name, st in ksum.items():
-        bound, work = kernel_model(name, B, G, hidden, nheads={'zinb-conddisp': 3, 'zinb': 2, 'nb-conddisp': 2, 'nb': 1}.get(ae_type, 3))
-        if name in graph_ms:                               # the event figure stays beside it
-            st = dict(st, eager_event_mean_ms=st['mean_ms'], mean_ms=graph_ms[name])
-        ent = {'kernel': name, 'mean_ms': st['mean_ms'], 'median_ms': st.get('median_ms'), 'share_of_step': st['mean_ms'] / (1e3 * el / steps_timed)}
-        if 'eager_event_mean_ms' in st:
-            ent['eager_event_mean_ms'] = st['eager_event_mean_ms']
-            ent['timing'] = 'ten consecutive launches of the operation in one hipGraph, replayed between two events (median of 5 replays)'
-        if work:
-            if bound == 'hbm':
-                ent.update(bound='hbm', achieved=work / (st['mean_ms'] * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit='GB/s')
-            else:
-                # The products are computed as `n` 16-bit MFMAs per fp32 product (3: two fp16 pieces; 6: three bf16 pieces): the
-                # bound of the matrix pipe for THIS result is the dense 16-bit peak / n -- `peak`.  (The fp32-MFMA peak,
-                # 157.3 TF/s, prices the same algorithmic flops on an instruction these kernels do not use and can exceed:
-                # a secondary field; so is the fraction of peak / 6, the denominator of rounds 2 - 5.)
-                n16 = ppp.get(name, 6)
-                ent.update(bound='mfma', achieved=work / (st['mean_ms'] * 1e-3) / 1e12, peak=MFMA_BF16_PEAK_TFLOPS / n16,
-                           unit='TFLOP/s')
-                ent['products_per_fp32_product'] = n16
-                ent['frac_of_bf16x6_peak'] = ent['achieved'] / (MFMA_BF16_PEAK_TFLOPS / 6.0)
-                ent['peak_fp32_mfma'] = MFMA_F32_PEAK_TFLOPS
-                ent['frac_of_fp32_mfma_peak'] = ent['achieved'] / MFMA_F32_PEAK_TFLOPS
-            ent['frac'] = ent['achieved'] / ent['peak']
-        kernels.append(ent)
-    kernels.sort(key=lambda e: -e['mean_ms'])
-    pmc = {}
-    try:
-        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-            pmc = json.load(f)
-    except (OSError, ValueError):
-        pass
-    roof = None
-    for e in kernels:
-        if 'frac' in e:
-            roof = {'kernel': e['kernel'], 'bound': e['bound'], 'achieved': e['achieved'], 'peak': e['peak'],
-                    'unit': e['unit'], 'frac': e['frac'], 'traffic': None,
-                    'traffic_source': None,
-                    'timing': 'HIP events on the launch stream around the scope of the launches that make up the operation ('
-                              + ('eager steps after the graph-replayed timed region, enqueued while the device is parked on a spin '
-                                 'kernel so that no host gap falls between two events' if use_graph else 'inside the timed region')
-                              + '); heads_fused = heads_split_h + heads_fused_h2 + heads_reduce_both (three launches: their '
-                                'rocprofv3 averages add up to this figure), gemm_enc0_* = operand split + product + reduce / finish'}
-            if e.get('timing'):
-                roof['timing'] = e['timing'] + ('; the operation = heads_split_h + heads_fused_h2 + heads_reduce_both (their rocprofv3 '
-                                                'averages add up to this figure)' if e['kernel'] == 'heads_fused' else
-                                                '; the operation = operand maxima + plane splits + gemm_h2w (+ tail sum)') + \
-                                 '; eager_event_mean_ms = the same launches between two events of an eager step (each event costs a barrier)'
-                roof['eager_event_mean_ms'] = e.get('eager_event_mean_ms')
-            if e['bound'] == 'mfma':
-                roof['peak_note'] = ('dense 16-bit MFMA peak (2 500 TF/s) / %d: the matrix-pipe bound of an fp32-accurate product '
-                                     'computed as %d 16-bit products (%s); frac_of_bf16x6_peak = the same launch against peak / 6, '
-                                     'the denominator of rounds 2 - 5; the fp32-MFMA peak is a secondary field'
-                                     % (e['products_per_fp32_product'], e['products_per_fp32_product'],
-                                        'two fp16 pieces per operand' if e['products_per_fp32_product'] == 3 else 'three bf16 pieces per operand'))
-                roof['products_per_fp32_product'] = e['products_per_fp32_product']
-                roof['frac_of_bf16x6_peak'] = e['frac_of_bf16x6_peak']
-                roof['peak_fp32_mfma'] = e['peak_fp32_mfma']
-                roof['frac_of_fp32_mfma_peak'] = e['frac_of_fp32_mfma_peak']
-            m = pmc.get(e['kernel'])
-            if m and m['shape']['B'] == B and m['shape']['G'] == G and m['shape']['hL'] == hidden[-1] and \
-                    m['shape'].get('ae_type', 'zinb-conddisp') == ae_type:
-                if m.get('source_sha') == source_sha():
-                    roof['traffic'] = m['traffic_bytes']
-                    roof['traffic_source'] = ('rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same kernel and shape on THIS '
-                                              'source tree (profiles/pmc_traffic.json, %s; sources %s): bytes per launch; algorithmic '
-                                              'HBM bytes %.0f' % (m.get('raw', 'raw files not recorded'), m['source_sha'],
-                                                                  m['algorithmic_hbm_bytes']))
-                else:
-                    roof['traffic_source'] = ('not attached: profiles/pmc_traffic.json was measured on kernel sources %s, this tree is '
-                                              '%s (tools/gpu_pmc_traffic.sh re-measures)' % (m.get('source_sha'), source_sha()))
-            break
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
-    if roof is not None:
-        nheads = {'zinb-conddisp': 3, 'zinb': 2, 'nb-conddisp': 2, 'nb': 1}.get(ae_type, 3)
-        hm = [e['mean_ms'] for e in kernels if e['kernel'] == 'heads_fused']
-        roof['step'] = step_roofline(cells_timed / el / W, B, G, hidden, nheads, int(eng.lay.P), ae_type, hm[0] if hm else None,
-                                     ppp_heads=3 if (hm or wide_h2) else 6, ppp_enc0=3 if wide_h2 else 6)
+    roof = kernels = None
+    if args.full:
+        # ---- per-kernel timing (HIP events on the launch stream)
+        ksum = prof.summary() if prof is not None else {}
+        if use_graph:
+            # graph replay hides individual launches: time the dominant kernels in isolation (eager full-batch steps)
+            eng.prof = EventProfiler()
+            eng.cursor.zero_()
+            # The events must see a GPU that is never waiting for the host: a Python-level launch costs 10 - 20 us, a scope of three
+            # launches between two event records would otherwise include the host's gaps (measured: K-HEADS' scope 0.79 ms against
+            # 0.705 ms for its three kernels under rocprofv3).  The device is parked on a spin kernel while the host enqueues all the
+            # profiled steps.
+            n_prof = min(steps_timed, 16, n_local // B)
+            _park_device(30.0)
+            for i in range(n_prof):
+                eng.train_step(B, B * W, counts, B)
+            ksum = eng.prof.summary(); eng.prof = None
+        # The dominant operation once more, as the product launches it: ten consecutive launches captured into ONE hipGraph, replayed
+        # between two events.  (Events round every scope of an eager step cost a barrier packet each: the scope of K-HEADS' three
+        # launches reads 0.76 - 0.79 ms that way against 0.70 ms for the same three kernels under rocprofv3.)
+        graph_ms = {}
+        last = getattr(eng, '_last_heads_args', None)
+        if last is not None and last[0] == B and not multi:       # (one process only: nothing new is captured beside live communicators)
+            try:
+                if eng.ws_heads is not None:
+                    graph_ms['heads_fused'] = _graph_timed(lambda: eng.heads_fused_launch(*last))
+                else:
+                    graph_ms['gemm_heads_fwd'] = _graph_timed(lambda: eng._heads_forward(last[0], last[1]))
+            except Exception as exc:                           # (never fatal for the bench line: the event figure stays)
+                sys.stderr.write('[bench] graph timing of the dominant operation failed: %r\n' % (exc,))
+        kernels = []
+        # 16-bit matrix products spent per fp32 product: K-HEADS and the wide networks' plane GEMMs run on two fp16 pieces and three
+        # products (round 6); the first layer from the byte store (and the three-piece planes) on three bf16 pieces and six
+        wide_h2 = bool(getattr(eng, '_h2', None) and eng.pl is not None and eng._h2(B))
+        ppp = {'heads_fused': 3}
+        for nm in ('gemm_heads_fwd', 'gemm_heads_dW', 'gemm_heads_dH', 'gemm_enc0_fwd', 'gemm_enc0_dW'):
+            ppp[nm] = 3 if wide_h2 else 6
+        for name, st in ksum.items():
+            bound, work = kernel_model(name, B, G, hidden, nheads={'zinb-conddisp': 3, 'zinb': 2, 'nb-conddisp': 2, 'nb': 1}.get(ae_type, 3))
+            if name in graph_ms:                               # the event figure stays beside it
+                st = dict(st, eager_event_mean_ms=st['mean_ms'], mean_ms=graph_ms[name])
+            ent = {'kernel': name, 'mean_ms': st['mean_ms'], 'median_ms': st.get('median_ms'), 'share_of_step': st['mean_ms'] / (1e3 * el / steps_timed)}
+            if 'eager_event_mean_ms' in st:
+                ent['eager_event_mean_ms'] = st['eager_event_mean_ms']
+                ent['timing'] = 'ten consecutive launches of the operation in one hipGraph, replayed between two events (median of 5 replays)'
+            if work:
+                if bound == 'hbm':
+                    ent.update(bound='hbm', achieved=work / (st['mean_ms'] * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit='GB/s')
+                else:
+                    # The products are computed as `n` 16-bit MFMAs per fp32 product (3: two fp16 pieces; 6: three bf16 pieces): the
+                    # bound of the matrix pipe for THIS result is the dense 16-bit peak / n -- `peak`.  (The fp32-MFMA peak,
+                    # 157.3 TF/s, prices the same algorithmic flops on an instruction these kernels do not use and can exceed:
+                    # a secondary field; so is the fraction of peak / 6, the denominator of rounds 2 - 5.)
+                    n16 = ppp.get(name, 6)
+                    ent.update(bound='mfma', achieved=work / (st['mean_ms'] * 1e-3) / 1e12, peak=MFMA_BF16_PEAK_TFLOPS / n16,
+                               unit='TFLOP/s')
+                    ent['products_per_fp32_product'] = n16
+                    ent['frac_of_bf16x6_peak'] = ent['achieved'] / (MFMA_BF16_PEAK_TFLOPS / 6.0)
+                    ent['peak_fp32_mfma'] = MFMA_F32_PEAK_TFLOPS
+                    ent['frac_of_fp32_mfma_peak'] = ent['achieved'] / MFMA_F32_PEAK_TFLOPS
+                ent['frac'] = ent['achieved'] / ent['peak']
+            kernels.append(ent)
+        kernels.sort(key=lambda e: -e['mean_ms'])
+        pmc = {}
+        try:
+            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+                pmc = json.load(f)
+        except (OSError, ValueError):
+            pass
+        roof = None
+        for e in kernels:
+            if 'frac' in e:
+                roof = {'kernel': e['kernel'], 'bound': e['bound'], 'achieved': e['achieved'], 'peak': e['peak'],
+                        'unit': e['unit'], 'frac': e['frac'], 'traffic': None,
+                        'traffic_source': None,
+                        'timing': 'HIP events on the launch stream around the scope of the launches that make up the operation ('
+                                  + ('eager steps after the graph-replayed timed region, enqueued while the device is parked on a spin '
+                                     'kernel so that no host gap falls between two events' if use_graph else 'inside the timed region')
+                                  + '); heads_fused = heads_split_h + heads_fused_h2 + heads_reduce_both (three launches: their '
+                                    'rocprofv3 averages add up to this figure), gemm_enc0_* = operand split + product + reduce / finish'}
+                if e.get('timing'):
+                    roof['timing'] = e['timing'] + ('; the operation = heads_split_h + heads_fused_h2 + heads_reduce_both (their rocprofv3 '
+                                                    'averages add up to this figure)' if e['kernel'] == 'heads_fused' else
+                                                    '; the operation = operand maxima + plane splits + gemm_h2w (+ tail sum)') + \
+                                     '; eager_event_mean_ms = the same launches between two events of an eager step (each event costs a barrier)'
+                    roof['eager_event_mean_ms'] = e.get('eager_event_mean_ms')
+                if e['bound'] == 'mfma':
+                    roof['peak_note'] = ('dense 16-bit MFMA peak (2 500 TF/s) / %d: the matrix-pipe bound of an fp32-accurate product '
+                                         'computed as %d 16-bit products (%s); frac_of_bf16x6_peak = the same launch against peak / 6, '
+                                         'the denominator of rounds 2 - 5; the fp32-MFMA peak is a secondary field'
+                                         % (e['products_per_fp32_product'], e['products_per_fp32_product'],
+                                            'two fp16 pieces per operand' if e['products_per_fp32_product'] == 3 else 'three bf16 pieces per operand'))
+                    roof['products_per_fp32_product'] = e['products_per_fp32_product']
+                    roof['frac_of_bf16x6_peak'] = e['frac_of_bf16x6_peak']
+                    roof['peak_fp32_mfma'] = e['peak_fp32_mfma']
+                    roof['frac_of_fp32_mfma_peak'] = e['frac_of_fp32_mfma_peak']
+                m = pmc.get(e['kernel'])
+                if m and m['shape']['B'] == B and m['shape']['G'] == G and m['shape']['hL'] == hidden[-1] and \
+                        m['shape'].get('ae_type', 'zinb-conddisp') == ae_type:
+                    if m.get('source_sha') == source_sha():
+                        roof['traffic'] = m['traffic_bytes']
+                        roof['traffic_source'] = ('rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same kernel and shape on THIS '
+                                                  'source tree (profiles/pmc_traffic.json, %s; sources %s): bytes per launch; algorithmic '
+                                                  'HBM bytes %.0f' % (m.get('raw', 'raw files not recorded'), m['source_sha'],
+                                                                      m['algorithmic_hbm_bytes']))
+                    else:
+                        roof['traffic_source'] = ('not attached: profiles/pmc_traffic.json was measured on kernel sources %s, this tree is '
+                                                  '%s (tools/gpu_pmc_traffic.sh re-measures)' % (m.get('source_sha'), source_sha()))
+                break
+
+        if roof is not None:
+            nheads = {'zinb-conddisp': 3, 'zinb': 2, 'nb-conddisp': 2, 'nb': 1}.get(ae_type, 3)
+            hm = [e['mean_ms'] for e in kernels if e['kernel'] == 'heads_fused']
+            roof['step'] = step_roofline(cells_timed / el / W, B, G, hidden, nheads, int(eng.lay.P), ae_type, hm[0] if hm else None,
+                                         ppp_heads=3 if (hm or wide_h2) else 6, ppp_enc0=3 if wide_h2 else 6)
     if getattr(comm, 'peer', None) is not None:
         comm.peer.check()                                  # K-PEER: an exchange a rank never joined fails the run here
     extra = {}
     _mark('timed region and kernel timing done')
-    if not multi:
+    if not multi and args.full:
         extra = after_measurements(eng, args, B, n_local, n_val, G, dev, runner)
     _mark('after-measurements done')
 
@@ -756,7 +794,7 @@ def main():
                                        ('%d steps of %d cells per GPU' % (steps_timed, B)),
                        'exposed_comm_ms_per_step': comm_ms,
                        'exposed_comm_source': ('8 eager steps before the timed region: events round each exchange (and each wait for '
-                                               'the asynchronous bucket) on the compute stream') if multi else None,
+                                               'the asynchronous bucket) on the compute stream') if comm_ms is not None else None,
                        'optimizer': 'RMSprop+clipvalue', 'params': int(eng.lay.P),
                        'heads_d_exp': int(getattr(eng, 'heads_d_exp', 0)),
                        'arithmetic': 'fp32 results.  Heads (K-HEADS; the wide networks\' plane products): operands block-scaled by a '
@@ -771,7 +809,7 @@ def main():
             # prune `config` keep them)
             'batch32': extra.get('batch32'), 'epoch': extra.get('epoch'),
         }
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             nb = min(n_local, max(B, 4 * B))
             p = eng.get_params()
             # host copy of a bounded sample of the same matrix; weights = current device weights

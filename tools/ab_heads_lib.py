@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = ("import sys, runpy; sys.path.insert(0, %r)\n"
         "lib = %%r\n"
         "if lib:\n    from dca_amd import build as b; b.LIB = lib; b.needs_build = lambda: False\n"
-        "import os\nsys.argv = ['bench.py', '--no-cpu-baseline'] + (os.environ['BENCH_ARGS'].split() if os.environ.get('BENCH_ARGS') else ['--steps', '96', '--warmup', '16'])\n"
+        "import os\nsys.argv = ['bench.py', '--full', '--no-cpu-baseline'] + (os.environ['BENCH_ARGS'].split() if os.environ.get('BENCH_ARGS') else ['--steps', '96', '--warmup', '16'])\n"
         "runpy.run_path(%r, run_name='__main__')\n" % (ROOT, os.path.join(ROOT, 'bench.py')))
 libs = [''] + [os.path.abspath(a) for a in sys.argv[1:]]
 for r in range(2):

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = ("import sys, runpy; sys.path.insert(0, %r); import dca_amd.config as c; o = c.EngineConfig.from_env.__func__\n"
         "def f(cls):\n    x = o(cls); x.lut_fwd_min = %%d; return x\n"
         "c.EngineConfig.from_env = classmethod(f)\n"
-        "sys.argv = ['bench.py', '--steps', '96', '--warmup', '16', '--no-cpu-baseline']\n"
+        "sys.argv = ['bench.py', '--full', '--steps', '96', '--warmup', '16', '--no-cpu-baseline']\n"
         "runpy.run_path(%r, run_name='__main__')\n" % (ROOT, os.path.join(ROOT, 'bench.py')))
 for r in range(int(sys.argv[1]) if len(sys.argv) > 1 else 3):
     for name, v in (('lut', 1024), ('dense', 1 << 30)):

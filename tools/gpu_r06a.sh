@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log; tail -5 $OUT/pytest_gpu.log | cut -c1-300
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
 COMPACT=1 ONLY_FUSED=1 timeout 300 python tools/timing_heads.py 4096 20000 64 1 > $OUT/heads_timing.txt 2>&1; echo "timing rc=$?"; tail -16 $OUT/heads_timing.txt
 python - "$OUT" <<'PY'
 import json,sys

@@ -6,8 +6,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gemm_h2_gpu.py tests/test_heads_fused_gpu.py -q -x 2>&1 | tail -12
 timeout 900 python -m pytest tests/test_engine_gpu.py -q -x -k "wide_network" 2>&1 | tail -12
-timeout 600 python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
-timeout 900 python bench.py --workload c5 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
+timeout 900 python bench.py --full --workload c5 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"
 python - "$OUT" <<'PY'
 import json,sys
 o=sys.argv[1]

@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gemm_h2_gpu.py -q 2>&1 | tail -8
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_c5 -o c5 --output-format csv -- python bench.py --workload c5 --steps 72 --warmup 3 --no-cpu-baseline --graph off > $OUT/bench_c5_prof.json 2> $OUT/bench_c5_prof.err; echo "prof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_c5 -o c5 --output-format csv -- python bench.py --full --workload c5 --steps 72 --warmup 3 --no-cpu-baseline --graph off > $OUT/bench_c5_prof.json 2> $OUT/bench_c5_prof.err; echo "prof rc=$?"
 f=$(find $OUT/prof_c5 -name '*kernel_stats.csv' | head -1)
 python - "$f" <<'PY'
 import csv,sys

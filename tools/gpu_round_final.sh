@@ -6,10 +6,10 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log; tail -3 $OUT/pytest_gpu.log | cut -c1-200
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
-timeout 900 python bench.py --workload c4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "bench c4 rc=$?"
-timeout 900 python bench.py --workload c5 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- python bench.py --steps 48 --warmup 5 --no-cpu-baseline --graph off > $OUT/bench_prof.json 2> $OUT/prof.err; echo "prof rc=$?"
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench c3 rc=$?"
+timeout 900 python bench.py --full --workload c4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "bench c4 rc=$?"
+timeout 900 python bench.py --full --workload c5 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench c5 rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- python bench.py --full --steps 48 --warmup 5 --no-cpu-baseline --graph off > $OUT/bench_prof.json 2> $OUT/prof.err; echo "prof rc=$?"
 find $OUT/prof -name '*kernel_trace*' -delete; find $OUT/prof -name '*domain_stats*' -delete
 bash tools/gpu_pmc_bench.sh $TAG/sq > $OUT/sq.log 2>&1; tail -12 $OUT/sq.log | cut -c1-220
 bash tools/gpu_pmc_traffic.sh $TAG/traffic > $OUT/traffic.log 2>&1; tail -3 $OUT/traffic.log | cut -c1-400
