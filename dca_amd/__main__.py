@@ -58,7 +58,7 @@ _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactor
 
 def build_parser():
     parser = argparse.ArgumentParser(prog='dca', description='Autoencoder')
-    parser.add_argument('input', type=str, help='raw counts: TSV/CSV (gene x cell unless -t) or H5AD')
+    parser.add_argument('input', type=str, help='raw counts: TSV/CSV (gene x cell unless -t), Matrix Market (.mtx, .mtx.gz) or H5AD')
     parser.add_argument('outputdir', type=str, help='output directory')
     for flags, kw in _OPTIONS:
         parser.add_argument(*flags, **kw)

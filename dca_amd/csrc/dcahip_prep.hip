@@ -11,6 +11,9 @@
 //                     filter_genes
 //   column stats      mean, std (ddof = 1, zero std -> 1) exactly as scanpy's scale
 //   scale             x = (x - mean) / std in place
+//   CSR expand        rows of a CSR chunk -> dense fp32 rows of the resident count matrix (the
+//                     upload of a sparse host matrix: index + value bytes cross PCIe, the zeros
+//                     are written here)
 // Arithmetic follows the host restatement operation by operation (fp32 division, fp32 log1p,
 // fp32 square accumulated in fp64) so that host and device inputs agree to the last ulp of
 // log1p.
@@ -155,7 +158,83 @@ __global__ __launch_bounds__(256) void scale_kernel(float* X, long ldx, int n, i
     }
 }
 
+// CSR expand: one workgroup per row (grid-stride).  The row is built in LDS column segments of
+// kCsrSeg floats: zero the segment, scatter the row's entries that fall into it, write it out with
+// V-float stores.  Columns are sorted (canonical rows), so the entries of a segment are the
+// contiguous run [p, q) that starts where the previous segment's run ended; q - p is the number of
+// entries the threads found below the segment's end (each thread walks its strided share and stops
+// at the first column beyond it).  Every LDS and global write is bounds-checked against the segment
+// and the row, so unsorted or malformed input can give wrong values but never touches memory outside
+// Y; entries with a column outside [0, G) and rows whose indptr leaves [0, nnz] or decreases are
+// counted into *status.  Each element is written by exactly one plain store: no atomics on Y.
+constexpr int kCsrSeg = 8064;                 // floats per LDS segment (31.5 KiB + the counter: 5 workgroups per CU)
+
+template <int V>
+__global__ __launch_bounds__(256) void csr_expand_kernel(const int* __restrict__ indptr, const int* __restrict__ indices,
+                                                         const float* __restrict__ values, long nnz, int rows, int G,
+                                                         float* __restrict__ Y, long ldy, int* status) {
+    __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
+    __shared__ int found;
+    const int tid = threadIdx.x;
+    int bad = 0;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+        long s = indptr[r], e = indptr[r + 1];
+        const long s0 = s < 0 ? 0 : (s > nnz ? nnz : s);
+        const long e0 = e < s0 ? s0 : (e > nnz ? nnz : e);
+        if (tid == 0 && (s0 != s || e0 != e)) ++bad;
+        long p = s0;
+        float* yrow = Y + (long)r * ldy;
+        for (long c0 = 0; c0 < ldy; c0 += kCsrSeg) {
+            const int len = (int)(ldy - c0 < kCsrSeg ? ldy - c0 : kCsrSeg);
+            // the last segment takes every remaining entry (columns >= ldy are counted, not written)
+            const long c1 = c0 + kCsrSeg < ldy ? c0 + kCsrSeg : (1L << 40);
+            if (V == 4) {
+                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
+            }
+            if (tid == 0) found = 0;
+            __syncthreads();
+            int mine = 0;
+            for (long j = p + tid; j < e0; j += 256) {
+                const long c = indices[j];
+                if (c >= c1) break;
+                ++mine;
+                if (c < 0 || c >= G) { ++bad; continue; }
+                const long k = c - c0;
+                if (k >= 0 && k < len) seg[k] = values[j];
+            }
+            if (mine) atomicAdd(&found, mine);
+            __syncthreads();
+            p += found;
+            if (p > e0) p = e0;
+            if (V == 4) {
+                for (int i = tid; i < (len >> 2); i += 256)
+                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
+            } else {
+                for (int i = tid; i < len; i += 256) yrow[c0 + i] = seg[i];
+            }
+            __syncthreads();
+        }
+    }
+    if (bad) atomicAdd(status, bad);
+}
+
 }  // namespace
+
+extern "C" int dcahip_csr_expand(const int* indptr, const int* indices, const float* values, long nnz, int rows, int G,
+                                 float* Y, long ldy, int* status, void* stream) {
+    if (rows < 0 || G <= 0 || ldy < G || nnz < 0 || nnz > 0x7fffffffL || !status) return DCAHIP_EINVAL;
+    if (rows == 0) return 0;
+    if (!indptr || !Y || (nnz > 0 && (!indices || !values))) return DCAHIP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = rows < 16384 ? rows : 16384;
+    if (al16(Y) && (ldy & 3) == 0)
+        hipLaunchKernelGGL(csr_expand_kernel<4>, dim3(grid), dim3(256), 0, s, indptr, indices, values, nnz, rows, G, Y, ldy, status);
+    else
+        hipLaunchKernelGGL(csr_expand_kernel<1>, dim3(grid), dim3(256), 0, s, indptr, indices, values, nnz, rows, G, Y, ldy, status);
+    return (int)hipGetLastError();
+}
 
 extern "C" int dcahip_prep_chunks(int n) { return prep_chunks(n); }
 

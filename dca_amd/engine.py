@@ -549,23 +549,34 @@ class Engine:
 
     # ------------------------------------------------------------------ data
     def load_data(self, X, Y=None, sf=None, chunk_rows=8192):
-        """Uploads host matrices once into padded device buffers ([n, ld], ld % 4 == 0)."""
+        """Uploads host matrices once into padded device buffers ([n, ld], ld % 4 == 0).  scipy.sparse matrices go to a
+        GPU as CSR (prep.upload_sparse: no dense copy on the host)."""
         lay = self.lay
         n = X.shape[0]
         assert X.shape[1] == lay.G_in
         self.n = n
         self.ldx = _r4(lay.G_in)
-        self.X = torch.zeros(n, self.ldx, dtype=torch.float32, device=self.dev)
+        csr_x = _prep.csr_capable(X, self.dev, self.ops)
+        csr_y = Y is not None and _prep.csr_capable(Y, self.dev, self.ops)
+        if csr_x:
+            self.X = _prep.upload_sparse(X, self.dev, self.ops, self.ldx)
+        else:
+            self.X = torch.zeros(n, self.ldx, dtype=torch.float32, device=self.dev)
         if Y is not None:
             assert Y.shape == (n, lay.G_out)
             self.ldy = lay.Gp
-            self.Y = torch.zeros(n, self.ldy, dtype=torch.float32, device=self.dev)
-        for s in range(0, n, chunk_rows):
+            if csr_y:
+                self.Y = _prep.upload_sparse(Y, self.dev, self.ops, self.ldy)
+            else:
+                self.Y = torch.zeros(n, self.ldy, dtype=torch.float32, device=self.dev)
+        dense_rows = not csr_x or (Y is not None and not csr_y)
+        for s in range(0, n if dense_rows else 0, chunk_rows):
             e = min(n, s + chunk_rows)
-            xs = X[s:e]
-            xs = xs.toarray() if hasattr(xs, 'toarray') else np.asarray(xs)
-            self.X[s:e, :lay.G_in] = _prep.host_chunk_tensor(xs).to(self.dev)
-            if Y is not None:
+            if not csr_x:
+                xs = X[s:e]
+                xs = xs.toarray() if hasattr(xs, 'toarray') else np.asarray(xs)
+                self.X[s:e, :lay.G_in] = _prep.host_chunk_tensor(xs).to(self.dev)
+            if Y is not None and not csr_y:
                 ys = Y[s:e]
                 ys = ys.toarray() if hasattr(ys, 'toarray') else np.asarray(ys)
                 self.Y[s:e, :lay.G_out] = _prep.host_chunk_tensor(ys).to(self.dev)

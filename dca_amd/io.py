@@ -151,8 +151,19 @@ def _read_text_native(filename, sep):
     return AnnData(X, obs=pd.DataFrame(index=pd.Index(idx.values).astype(str)), var=pd.DataFrame(index=pd.Index(cols).astype(str)))
 
 
+def read_mtx(filename):
+    """Stand-in for sc.read_mtx, which sc.read(path, first_column_names=True) (io.py:58-59) takes for a Matrix Market file
+    ('.mtx' or '.mtx.gz'): the matrix in float32 CSR, obs / var names '0' .. 'n-1' (the file carries none)."""
+    from scipy.io import mmread
+    X = sp_sparse.csr_matrix(mmread(filename).astype('float32'))
+    n, g = X.shape
+    return AnnData(X, obs=pd.DataFrame(index=pd.RangeIndex(n).astype(str)),
+                   var=pd.DataFrame(index=pd.RangeIndex(g).astype(str)))
+
+
 def read_dataset(adata, transpose=False, test_split=False, copy=False, check_counts=True):
-    """dca/io.py:53-85."""
+    """dca/io.py:53-85.  A path is read as sc.read does it: '.h5ad' through anndata, '.mtx' / '.mtx.gz' (Matrix Market)
+    into a sparse float32 CSR matrix (read_mtx), anything else as a TSV / CSV table with the names in its first column."""
     if is_anndata(adata):
         if copy:
             adata = adata.copy()
@@ -160,6 +171,8 @@ def read_dataset(adata, transpose=False, test_split=False, copy=False, check_cou
         if adata.endswith('.h5ad'):
             import anndata as _ad          # ImportError if unavailable, like the reference
             adata = _ad.read_h5ad(adata)
+        elif adata.endswith('.mtx') or adata.endswith('.mtx.gz'):
+            adata = read_mtx(adata)
         else:
             adata = read_text(adata, first_column_names=True)
     else:

@@ -485,6 +485,13 @@ class HipOps:
         p = hip.ptr
         hip.check(self.L.dcahip_prep_scale(p(X), ldx, n, G, p(mean), p(stdv), hip.stream()), 'prep_scale')
 
+    def csr_expand(self, indptr, indices, values, nnz, rows, G, Y, ldy, status):
+        """Rows of a CSR chunk (int32 indptr / indices, fp32 values, device tensors) -> every element of Y[:rows, :ldy];
+        status (int32 device word) += what had to be ignored (include/dcahip.h)."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_csr_expand(p(indptr), p(indices), p(values), nnz, rows, G, p(Y), ldy, p(status),
+                                           hip.stream()), 'csr_expand')
+
     # ------------------------------------------------------------------ optimizer
     def rmsprop_clip_end(self, w, g, ms, n, lr, rho, eps, clip, loss, weight, hist, rows_per_slot, acc, cursor, advance):
         p = hip.ptr

@@ -14,6 +14,7 @@ sums are exact integer arithmetic.  The median of the library sizes is taken on 
 (``np.median`` over n values), exactly as the reference does.
 """
 import numpy as np
+import scipy.sparse as sp_sparse
 import torch
 
 
@@ -92,11 +93,132 @@ def _stage_buffers(rows, cols):
     return _STAGE[key]
 
 
-def _upload(X, dev, chunk_rows=2048):
+def csr_capable(X, dev, ops):
+    """Whether the host matrix X goes to `dev` as CSR (upload_sparse): a scipy.sparse matrix, a GPU, ops with the kernel."""
+    return sp_sparse.issparse(X) and dev.type == 'cuda' and ops is not None and hasattr(ops, 'csr_expand')
+
+
+def plan_csr_chunks(indptr, nnz_cap, row_cap):
+    """Row chunks [(r0, r1), ...] of a CSR matrix with row pointer `indptr` (n + 1 entries, int32 or int64): consecutive,
+    every row in exactly one, each of at most row_cap rows and at most nnz_cap entries -- except a chunk of ONE row, which
+    holds its row whatever the row's length.  (Any indptr gives a plan; a malformed one is caught by the kernel.)"""
+    indptr = np.asarray(indptr)
+    n = len(indptr) - 1
+    nnz_cap, row_cap = int(nnz_cap), int(row_cap)
+    assert nnz_cap >= 1 and row_cap >= 1
+    chunks = []
+    r0 = 0
+    while r0 < n:
+        # the last row r1 with indptr[r1] - indptr[r0] <= nnz_cap (indptr ascending)
+        r1 = int(np.searchsorted(indptr, int(indptr[r0]) + nnz_cap, side='right')) - 1
+        r1 = max(r0 + 1, min(r1, r0 + row_cap, n))
+        chunks.append((r0, r1))
+        r0 = r1
+    return chunks
+
+
+_CSR_STAGE = {}
+
+
+def _csr_stage(rows, nnz):
+    """Two page-locked slots (indptr int32 [rows + 1], indices int32 [nnz], values fp32 [nnz]) for upload_sparse, kept
+    for the life of the process apart from _stage_buffers' (which keeps one shape only); grown when a matrix needs more."""
+    have = _CSR_STAGE.get('slots')
+    if have is None or have[0][0].numel() < rows + 1 or have[0][1].numel() < nnz:
+        rows = max(rows, have[0][0].numel() - 1 if have else 0)
+        nnz = max(nnz, have[0][1].numel() if have else 0)
+        _CSR_STAGE['slots'] = None
+        _CSR_STAGE['slots'] = [(torch.empty(rows + 1, dtype=torch.int32).pin_memory(),
+                                torch.empty(max(nnz, 1), dtype=torch.int32).pin_memory(),
+                                torch.empty(max(nnz, 1), dtype=torch.float32).pin_memory()) for _ in range(2)]
+    return _CSR_STAGE['slots']
+
+
+def _pack(dst, src):
+    """dst[:] = src converted to dst's dtype (round to nearest for floats, as np.asarray(src, float32) does); host threads
+    for large same-dtype runs."""
+    if src.dtype == dst.dtype and src.nbytes >= (1 << 20):
+        from . import hostlib
+        hostlib.parallel_copy(dst, np.ascontiguousarray(src))
+    else:
+        np.copyto(dst, src, casting='unsafe')
+
+
+def pack_csr_chunk(X, r0, r1, indptr_out, indices_out, values_out):
+    """Rows r0 .. r1 of the CSR matrix X into the given int32 / int32 / fp32 arrays (at least r1 - r0 + 1 and the chunk's
+    entries long): chunk-relative indptr, column indices, values in fp32.  A matrix without canonical format is made
+    canonical on a COPY of the chunk (sum_duplicates: duplicates add in the source dtype, as toarray() does); X is never
+    modified.  Column indices that do not fit int32 are clamped to -1 (the kernel counts them).  Returns the chunk's nnz."""
+    ip = X.indptr
+    a, b = int(ip[r0]), int(ip[r1])
+    rel = ip[r0:r1 + 1].astype(np.int64) - a
+    idx, val = X.indices[max(a, 0):max(b, a, 0)], X.data[max(a, 0):max(b, a, 0)]
+    if not X.has_canonical_format:
+        sub = sp_sparse.csr_matrix((val.copy(), idx.copy(), rel.copy()), shape=(r1 - r0, X.shape[1]))
+        sub.sum_duplicates()
+        rel, idx, val = sub.indptr, sub.indices, sub.data
+    m = len(idx)
+    np.copyto(indptr_out[:r1 - r0 + 1], np.clip(rel, -1, 2 ** 31 - 1), casting='unsafe')
+    if idx.dtype.itemsize > 4:
+        idx = np.where((idx >= 0) & (idx < 2 ** 31), idx, -1)
+    _pack(indices_out[:m], idx)
+    _pack(values_out[:m], val)
+    return m
+
+
+def upload_sparse(X, dev, ops, ld, nnz_cap=1 << 22, row_cap=1 << 14):
+    """scipy.sparse host matrix [n, G] -> new [n, ld] fp32 device tensor (ld >= G; pad columns zero), without a dense copy
+    on the host: row chunks of the CSR arrays travel through two page-locked slots (chunk i + 1 is packed while chunk i
+    crosses PCIe and dcahip_csr_expand writes its dense rows).  Bit for bit what the dense upload of X.toarray() gives.
+    Other sparse formats are converted to CSR once.  A malformed matrix (a column outside [0, G), a bad indptr) raises
+    ValueError."""
+    n, G = X.shape
+    if X.format != 'csr':
+        X = X.tocsr()
+    out = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    ip = X.indptr.astype(np.int64, copy=False)
+    if len(ip) != n + 1 or ip[0] != 0 or ip[-1] > len(X.indices) or len(X.data) != len(X.indices) or (np.diff(ip) < 0).any():
+        # (checked here, O(n): scipy's own canonical-format test and the chunk slices trust indptr)
+        raise ValueError('dca_amd: malformed sparse matrix: indptr is not a non-decreasing row pointer into its %d entries'
+                         % len(X.indices))
+    chunks = plan_csr_chunks(ip, max(int(nnz_cap), G), row_cap)
+    cap = max(int(ip[r1] - ip[r0]) for r0, r1 in chunks)
+    stage = _csr_stage(max(r1 - r0 for r0, r1 in chunks), cap)
+    cap = stage[0][1].numel()
+    dbuf = [(torch.empty(s[0].numel(), dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+             torch.empty(cap, dtype=torch.float32, device=dev)) for s in stage]
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    events = [torch.cuda.Event() for _ in range(2)]
+    for ci, (r0, r1) in enumerate(chunks):
+        slot = ci % 2
+        if ci >= 2:
+            events[slot].synchronize()                 # the copies that last read this slot are done
+        hp, hi, hv = stage[slot]
+        m = pack_csr_chunk(X, r0, r1, hp.numpy(), hi.numpy(), hv.numpy())
+        dp, di, dv = dbuf[slot]
+        dp[:r1 - r0 + 1].copy_(hp[:r1 - r0 + 1], non_blocking=True)
+        di[:m].copy_(hi[:m], non_blocking=True)
+        dv[:m].copy_(hv[:m], non_blocking=True)
+        events[slot].record()
+        ops.csr_expand(dp, di, dv, m, r1 - r0, G, out[r0:r1], ld, status)
+    torch.cuda.current_stream().synchronize()
+    bad = int(status.item())
+    if bad:
+        raise ValueError('dca_amd: malformed sparse matrix: %d entries / rows outside the matrix (a column outside '
+                         '[0, %d) or an indptr out of order)' % (bad, G))
+    return out
+
+
+def _upload(X, dev, chunk_rows=2048, ops=None):
     """Host matrix -> [n, r4(G)] device tensor.  On a GPU the rows travel through two page-locked staging buffers:
     host threads fill buffer i + 1 (dcahost_parallel_copy) while buffer i crosses PCIe -- a pageable .to(device)
-    of the 5.5 GB benchmark matrix moves ~13 GB/s, this ~45."""
+    of the 5.5 GB benchmark matrix moves ~13 GB/s, this ~45.  A scipy.sparse matrix goes as CSR (upload_sparse) when
+    `ops` has the kernel."""
     n, G = X.shape
+    if csr_capable(X, dev, ops):
+        return upload_sparse(X, dev, ops, _r4(G))
     out = torch.zeros(n, _r4(G), dtype=torch.float32, device=dev)
     dense = not hasattr(X, 'toarray')
     staged = dev.type == 'cuda' and dense and X.dtype == np.float32 and X.flags['C_CONTIGUOUS'] and n * G >= (1 << 22)
@@ -204,7 +326,7 @@ def resident_counts(X, ops=None, device=None):
     dev = torch.device(device) if device is not None else (
         torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
     n, G = X.shape
-    Y = _upload(X, dev)
+    Y = _upload(X, dev, ops=ops)
     return Y, gene_counts(ops, Y, n, G).cpu().numpy()
 
 
@@ -219,7 +341,7 @@ def normalize_device(adata, filter_min_counts=True, size_factors=True, normalize
         torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
     n, G = adata.X.shape
     if Y is None or tuple(Y.shape) != (n, _r4(G)):
-        Y = _upload(adata.X, dev)       # (else: resident_counts() uploaded these counts already)
+        Y = _upload(adata.X, dev, ops=ops)       # (else: resident_counts() uploaded these counts already)
 
     if filter_min_counts:                                         # io.py:90-92
         gc = gene_counts(ops, Y, n, G).cpu().numpy()

@@ -487,6 +487,21 @@ int dcahip_prep_col_finish(const double* col_part, int R, int G, double n_total,
                            float* sums, float* mean, float* stdv, void* stream);
 int dcahip_prep_scale(float* X, long ldx, int n, int G, const float* mean, const float* stdv,
                       void* stream);
+/*
+ * CSR expand: the upload of a sparse host count matrix (scipy.sparse .X of an AnnData, a Matrix Market file), read by
+ * the reference through sc.read (dca/io.py:58-59) and densified by Keras' batch feed (dca/train.py:82-88).  Only the
+ * CSR arrays of a row chunk cross PCIe; this writes the dense fp32 rows of the resident count matrix.
+ *   indptr [rows + 1] int32, chunk-relative (indptr[0] = 0, indptr[rows] = nnz); indices [nnz] int32, values [nnz]
+ *   fp32 (may be NULL when nnz = 0).  Rows must be canonical: sorted columns, no duplicates (the host sums
+ *   duplicates first).  Writes EVERY element Y[r, 0 .. ldy) for r < rows -- the entry's value or 0, pad columns
+ *   G .. ldy included -- so Y may be allocated uninitialised.  Never reads or writes outside its buffers, whatever the
+ *   chunk holds: *status += a positive count of what it had to ignore (entries with a column outside [0, G), rows
+ *   whose indptr entries leave [0, nnz] or decrease); status (one int32, device memory) is zeroed by the caller.
+ *   Deterministic: each element is written by one plain store.  rows = 0 launches nothing; ldy < G, G <= 0 or
+ *   nnz > INT32_MAX: DCAHIP_EINVAL.
+ */
+int dcahip_csr_expand(const int* indptr, const int* indices, const float* values, long nnz, int rows, int G,
+                      float* Y, long ldy, int* status, void* stream);
 
 /*
  * Keras clipvalue + Keras RMSprop (momentum 0) on one flat parameter buffer:
