@@ -1475,11 +1475,7 @@ Plan make_plan(int M, int N, int K, int split_k) {
     // at most 64 tiles of 128 x 128 -- a quarter of the chip -- which only a deep split-K (+ its reduce launch) could spread;
     // 64 x 64 tiles fill it with little or no split (tools/bench_hidden_gemm.py: the twelve products of configs[4]'s stack
     // 283 -> 160 us; profiles/r03_hidden_gemm_notes.txt)
-#ifndef DCA_GEMM_NO_MID64
     const bool mid = p.cfg == 2 && (long)M * N <= 2048L * 512;
-#else
-    const bool mid = false;
-#endif
     if (mid) { p.cfg = 3; p.BM = 64; p.BN = 64; }
     p.mtiles = (M + p.BM - 1) / p.BM;
     p.ntiles = (N + p.BN - 1) / p.BN;
@@ -1512,19 +1508,6 @@ Plan make_plan(int M, int N, int K, int split_k) {
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// A/B builds only (hipcc -DDCA_GEMM_F32MFMA / -DDCA_GEMM_X3): the exact-fp32 MFMA kernel / the split-bf16 kernel for every
-// layout.  The shipped library has no run-time switches: the choice is a pure function of layout and shape.
-#ifdef DCA_GEMM_F32MFMA
-constexpr bool use_f32_mfma() { return true; }
-#else
-constexpr bool use_f32_mfma() { return false; }
-#endif
-#ifdef DCA_GEMM_X3
-constexpr bool force_x3() { return true; }
-#else
-constexpr bool force_x3() { return false; }
-#endif
 
 template <int BM, int BN, int WGM, int WGN>
 int launch_cfg(const GemmArgs& a, int ta, int tb, bool vec, int grid, hipStream_t s, bool exact) {
@@ -1572,7 +1555,7 @@ extern "C" int dcahip_sgemm(int ta, int tb, int M, int N, int K, const float* A,
     //   NN with fewer columns, TN                                               exact fp32 MFMA (the split kernel's larger LDS
     //       images cost more occupancy than the shorter matrix phase returns on these latency-bound shapes: 0.158 vs 0.157 ms
     //       and 0.195 vs 0.150 ms on the first layer at B = 4096; profiles/r02e_gemm_ab.txt)
-    const bool exact = use_f32_mfma() || split_k < 0 || (ta && !force_x3()) || (!ta && !tb && N < 128 && !force_x3());
+    const bool exact = split_k < 0 || ta || (!tb && N < 128);
     if (p.cfg == 0) rc = launch_cfg<128, 64, 4, 1>(a, ta, tb, vec, grid, s, exact);
     else if (p.cfg == 1) rc = launch_cfg<64, 128, 1, 4>(a, ta, tb, vec, grid, s, exact);
     else if (p.cfg == 3) rc = launch_cfg<64, 64, 2, 2>(a, ta, tb, vec, grid, s, exact);
@@ -1790,7 +1773,6 @@ extern "C" int dcahip_gemm_h2(int ta, int tb, int M, int N, int K, const void* A
                  C, bias, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
                  p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace), exp_a, exp_b, exp_a_add, exp_b_add, alpha};
     hipStream_t s = static_cast<hipStream_t>(stream);
-#ifndef DCA_EXP_H2_NOHALFM
     if (!ta && !tb && !colsum_row) {
         // forward products (A k-contiguous, B n-contiguous): 128 x 256 tiles by four waves, two workgroups per CU
         // (gemm_h2m_kernel).  Measured at configs[4] (tools/ab_heads_lib.py, one box): heads forward 0.87 - 0.90 -> 0.73 - 0.74 ms,
@@ -1819,7 +1801,6 @@ extern "C" int dcahip_gemm_h2(int ta, int tb, int M, int N, int K, const void* A
         }
         return rcm;
     }
-#endif
     int grid = p.mtiles * p.ntiles * p.split;
     if (tp.split > 1) grid = tp.first + (p.mtiles * p.ntiles - tp.first) * tp.split;
 #define DCA_W(AKC, BKC, CSV) do { \

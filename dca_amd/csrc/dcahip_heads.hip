@@ -66,12 +66,6 @@ constexpr int kCUs = 256;
 constexpr int kZU = 4;        // staged rows per Z group (two groups per loop iteration)
 constexpr int kQCap = 320;     // non-zero queue entries per wave (< 64 left over + 4 x 64 pushed)
 
-#ifdef DCA_HEADS_TIMING
-#define TSTAMP(i) { const long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define TSTAMP(i)
-#endif
-
 __device__ __forceinline__ int rowmap(int e, int hi) { return (e & 3) + 8 * (e >> 2) + 4 * hi; }
 
 __device__ __forceinline__ void wave_sync() {
@@ -148,7 +142,6 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 struct HeadsArgs2 {
-    long long* timing;
     const unsigned short* HA;         // [NT][2][32 rows][64 k] fp16 pieces of the scaled decoder output (forward A operand)
     const unsigned short* HT;         // [NT][2][64 k][32 rows, order of the MFMA row map] (dW A operand)
     const int* eH;                    // [NT] exponent of each row tile's scale
@@ -257,10 +250,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef DCA_HEADS_TIMING
-    const long long t_entry = __builtin_readcyclecounter();
-    long long t_loop0 = t_entry, t_loop1 = t_entry;
-#endif
     const int l31 = lane & 31, hi = lane >> 5;
     const int r = wave;
     const long long cur = p.cursor ? *p.cursor : 0;
@@ -387,9 +376,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         const unsigned char* const ycolc = p.yc + gene_c;
         const unsigned ldy_u = YC ? (unsigned)p.ldc : (unsigned)p.ldy;
         auto count_at = [&](int sr) -> YV {
-#ifdef DCA_EXP_YCACHED       // experiment (wrong results): every count from the same 8 storage rows -- always cache hits: prices the count loads' latency
-            sr &= 7;
-#endif
             if constexpr (YC) return (unsigned)ycolc[(unsigned long long)(unsigned)sr * ldy_u];
             else return ycol[(unsigned long long)(unsigned)sr * ldy_u];
         };
@@ -478,19 +464,9 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             }
         }
         int rb = 0;                                  // which half of Rt holds the current tile's rows
-#ifdef DCA_HEADS_TIMING
-        long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        long long tlast = __builtin_readcyclecounter();
-        t_loop0 = tlast;
-#endif
         int tile_no = wave >> 2;
         for (; t < p.NT; t += tstep) {
-#if defined(DCA_EXP_PHASEPRIO)
-            __builtin_amdgcn_s_setprio(2);           // experiment: the matrix phases above the element-wise pass
-#elif !defined(DCA_EXP_NOPRIO)
             if ((tile_no++) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
-            TSTAMP(0)
             const int row0 = t * kTR;
             const int tn = t + tstep < p.NT ? t + tstep : t;
             // the tile's scales (wave-uniform): forward products carry 2^(eH[t] + eW), the gradient D = g 2^kDt
@@ -508,9 +484,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             float scs = 0.f;                          // 2^kDe
             int qn = 0;                               // queue fill
             float dmax = 0.f;                         // the lane's largest |D| of this tile (matrix-product planes only)
-#ifdef DCA_HEADS_TIMING
-            long long tsparse = 0;
-#endif
             auto z_sparse = [&](int q0, int cnt) {
                 const bool act = lane < cnt;
                 const u32x4 ent = Qe[q0 + (act ? lane : 0)];
@@ -560,13 +533,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                 while (qn >= 64 || (last && qn > 0)) {
                     const int c = qn < 64 ? qn : 64;
                     wave_sync();
-#ifdef DCA_HEADS_TIMING
-                    const long long f0 = __builtin_readcyclecounter();
-#endif
                     z_sparse(qn - c, c);
-#ifdef DCA_HEADS_TIMING
-                    tsparse += __builtin_readcyclecounter() - f0;        // (reported in slot 2; still part of slot 4's total)
-#endif
                     qn -= c;
                 }
             };
@@ -699,8 +666,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                     }
                 }
             }
-            TSTAMP(1)
-            TSTAMP(2)
             // ---- stage the unscaled pre-activations: one 16-byte cell per head and group of four rows
 #pragma unroll
             for (int h = 0; h < NH; ++h)
@@ -709,7 +674,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                     *reinterpret_cast<float4*>(Pimg + h * HEAD_B + cell_lane + ((g & 1) + 4 * (g >> 1)) * 16) =
                         make_float4(acc[h][4 * g] * funscale, acc[h][4 * g + 1] * funscale, acc[h][4 * g + 2] * funscale, acc[h][4 * g + 3] * funscale);
             wave_sync();
-            TSTAMP(3)
 
             // ---- Z: element-wise likelihood and gradient (dense y = 0 pass over the staged cells; the non-zero elements compacted
             // into 64-lane batches through a queue that carries their three pre-activations).  The gradients D = g 2^kDe are
@@ -721,18 +685,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             lacc = 0.f;
             qn = 0;
             dmax = 0.f;
-#if defined(DCA_EXP_PHASEPRIO)
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef DCA_HEADS_TIMING
-            tsparse = 0;
-#endif
-#ifndef DCA_EXP_X3NOZ
             if (row0 + kTR <= p.B && g0 + kTG <= p.G) z_loop(std::true_type{}); else z_loop(std::false_type{});
-#endif
-#ifdef DCA_HEADS_TIMING
-            tacc[2] += tsparse;
-#endif
             if (!__ballot(!(dmax <= kDLim))) break;   // (a NaN / inf gradient takes the slow branch once and stays what it is)
             const float mx = wave_max(dmax);
             const int need = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_frexp_expf(mx) - 1 - kTop);    // mx 2^-need < 2^(kTop + 1)
@@ -744,11 +697,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             }   // F + Z (until the scale fits)
             dacc += (double)lacc;
             const float sf_n = p.sf[srow_n];
-#if defined(DCA_EXP_PHASEPRIO)
-            __builtin_amdgcn_s_setprio(2);
-#endif
             wave_sync();
-            TSTAMP(4)
             const int shift = kDt - kDe;
             if (shift) {                             // the wave's accumulators to the scale of this tile's D
                 const float down = pow2i(-shift);
@@ -775,11 +724,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                 // offset, immediates -- 32 separate 64-bit addresses would not fit the register file
                 const __amdgpu_buffer_rsrc_t dh_rs = __builtin_amdgcn_make_buffer_rsrc(
                     dh_part + (long)t * dh_tstride, 0, kTR * KT * 4, 0x00020000);
-#ifdef DCA_EXP_NODHLOAD      // experiment (wrong results): every item starts its dH partial from zero -- prices the load's exposed latency
-                if (true) {
-#else
                 if (first_item) {
-#endif
 #pragma unroll
                     for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
@@ -815,7 +760,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                             MFMA_H3(bf, af, dHa[jb])
                         }
                     }
-                TSTAMP(7)
 #pragma unroll
                 for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
@@ -829,7 +773,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             load_ht(t, 1, htb[1]);
             load_ha(tn, 0, ha0);                     // next tile's first forward step: in flight during the dW products
             __builtin_amdgcn_sched_barrier(0);
-            TSTAMP(5)
             // ---- dW[i, gene] += sum_rows H[row, i] D[row, gene]: B = the lane's own D column as stored (row positions in
             // the order of the MFMA row map = the order of the transposed H image), A = H^T pieces.  The accumulators carry
             // 2^(eHmin + kD0) = 2^(eH[t] + kDt) in every tile.  The column sums (bias gradients) from the pieces: v_dot2_f32_f16.
@@ -884,13 +827,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             if (lane < 32) Sft[l31] = sf_n;          // (the pass over this tile is over: its size factors are no longer read)
             rb ^= 1;
             wave_sync();
-            TSTAMP(6)
         }
-#ifdef DCA_HEADS_TIMING
-        t_loop1 = __builtin_readcyclecounter();
-        if (p.timing && lane == 0)
-            for (int i = 0; i < 8; ++i) p.timing[((long)blockIdx.x * WR + wave) * 10 + i] += tacc[i];
-#endif
         // the wave's weight gradient back to g units x H (exact: a power of two) before the waves are summed
         {
             const float wun = pow2i(-(eHmin + kD0));
@@ -984,13 +921,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         for (int w = 0; w < WR; ++w) v += lred[w];
         p.partials[blockIdx.x] = v;
     }
-#ifdef DCA_HEADS_TIMING
-    if (p.timing && lane == 0) {
-        long long* tp = p.timing + ((long)blockIdx.x * WR + wave) * 10;
-        tp[8] = t_loop0 - t_entry;
-        tp[9] = (long long)__builtin_readcyclecounter() - t_loop1;
-    }
-#endif
 }
 
 
@@ -1214,7 +1144,6 @@ bool make_heads_plan(int B, int hL, int G, long plane, int flags, HeadsPlan* out
         p.npart = p.grid / p.S;
     }
     p.nmain = p.ngb; p.ntail = 0; p.S2 = 0; p.grid2 = 0; p.npart2 = 0; p.nitems2 = 0;
-#ifndef DCA_EXP_NO_TAIL_LAUNCH
     if (!p.small && p.S >= 2) {
         const int full = p.ngb / p.npart, rem = p.ngb - full * p.npart;
         const int tiles = (p.NT + p.S * p.WR - 1) / (p.S * p.WR);
@@ -1239,7 +1168,6 @@ bool make_heads_plan(int B, int hL, int G, long plane, int flags, HeadsPlan* out
             }
         }
     }
-#endif
     p.ldws = (long)NH * plane;
     p.dw_stride = (long)(hL + 2) * p.ldws;
     p.dw_bytes = (long)p.S * p.dw_stride * (long)sizeof(float);
@@ -1250,8 +1178,6 @@ bool make_heads_plan(int B, int hL, int G, long plane, int flags, HeadsPlan* out
     *out = p;
     return true;
 }
-
-long long* g_timing = nullptr;           // (DCA_HEADS_TIMING builds only: per-phase cycle counters)
 
 // =====================================================================================================
 // K-HEADS for batches below 160 rows (B <= 32, ONE row tile, is the reference's default batch size, dca/api.py:33):
@@ -1746,10 +1672,6 @@ extern "C" int dcahip_x3_product_32x32(const float* A, const float* B, float* C,
     return (int)hipGetLastError();
 }
 
-#ifdef DCA_HEADS_TIMING
-extern "C" void dcahip_heads_set_timing(long long* buf) { g_timing = buf; }
-#endif
-
 // (rounded up to pairs, the unit in which the engine sorts tiles by cost; the kernels read the first ceil(G / 32))
 extern "C" int dcahip_heads_tile_order_len(int G) { return G > 0 ? (((G + kTG - 1) / kTG + kWG - 1) / kWG) * kWG : 0; }
 
@@ -1832,7 +1754,7 @@ extern "C" int dcahip_heads_fused_compact(const float* H, long ldh, const float*
             if (rc0 != 0) return rc0;
         }
         direct_dw = pl.S == 1;
-        HeadsArgs2 a{g_timing, HA, HT, eH, H, ldh, gW, ldg, g_theta, Wh, ldw, bh, theta_w, y, ldy, yc, ldc, ovf_ptr, ovf_col, ovf_val,
+        HeadsArgs2 a{HA, HT, eH, H, ldh, gW, ldg, g_theta, Wh, ldw, bh, theta_w, y, ldy, yc, ldc, ovf_ptr, ovf_col, ovf_val,
                      sf, perm, cursor, ws_dw, pl.dw_stride, ws_dh,
                      pl.npart, pl.nitems, tile_order, loss_partials, plane, pl.ldws, B, hL, G, pl.S, pl.NT, ridge, inv_n, d_exp, 0};
         auto launch = [&](const HeadsPlan& q, const HeadsArgs2& b) {

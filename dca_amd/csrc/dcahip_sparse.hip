@@ -236,14 +236,10 @@ constexpr int kDwLut = 64;          // table entries per cell held in LDS (with 
 // kernels want the workgroups of ONE row split (same table rows, same dZ pieces, all gene groups) behind the same L2: this
 // gives workgroup L the (group, split) cell that keeps each XCD on a contiguous range of the split-major order.
 __device__ __forceinline__ void xcd_cell(int& bx, int& by) {
-#ifdef DCA_EXP_NO_XCD_MAP
-    bx = blockIdx.x; by = blockIdx.y;
-#else
     const int total = gridDim.x * gridDim.y, L = blockIdx.x + blockIdx.y * gridDim.x;
     const int q = total >> 3, r = total & 7, x = L & 7;
     const int cell = x * q + (x < r ? x : r) + (L >> 3);
     bx = cell % (int)gridDim.x; by = cell / (int)gridDim.x;
-#endif
 }
 
 // Column sums of one row split's dZ = sum of its K steps' sums, IN ORDER (the bias gradient's summation order), by the H1
@@ -491,12 +487,6 @@ constexpr int kD2CodeChunk = 1024 + 32;                    // two count rows of 
 constexpr int kD2CodeB = 8 * kD2CodeChunk;                 // 8448
 constexpr int kD2StageB = kD2LutB + kD2DzB + kD2CodeB;     // 30976
 
-#ifdef DCA_DW_TIMING
-__device__ long long* g_dw_timing = nullptr;         // [workgroup][8]: clock at kernel entry, after the prologue, after the loop, at the end (wave 0) + realtime at entry / end
-#define DWSTAMP(i) if (g_dw_timing && tid == 0) g_dw_timing[(blockIdx.x + blockIdx.y * gridDim.x) * 8 + (i)] = (i) >= 4 ? (long long)__builtin_amdgcn_s_memrealtime() : (long long)__builtin_readcyclecounter();
-#else
-#define DWSTAMP(i)
-#endif
 __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2, 2))) void enc0_dw2_kernel(DwArgs a) {
     constexpr int H1 = 64, NTL = 2;
     constexpr int KSE = dz_step_elems(H1);
@@ -507,7 +497,6 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
     __shared__ float fac_all[kD2MaxRS];                    // size factors of the split's rows (the formula path)
 
     const int tid = threadIdx.x, lane = tid & 63;
-    DWSTAMP(0) DWSTAMP(4)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
     int bx, by;
@@ -615,28 +604,12 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
     // most steps, and all its waves wait at the barrier meanwhile: each visit cost ~3300 cycles with select chains over the
     // register arrays and global loads -- those workgroups ran 25 % longer than the others, profiles/r05n_*)
     const unsigned fac_base = (unsigned)(size_t)(__attribute__((address_space(3))) float*)fac_all;
-#ifdef DCA_DW_TIMING
-    int n_visits = 0, n_places = 0;
-#endif
-    auto beyond_table = [&](int k, int stage, const unsigned (&code)[kD2MT][8], u32x2 (&ent)[kD2MT][8], unsigned any_dbg) __attribute__((always_inline)) {
+    auto beyond_table = [&](int k, int stage, const unsigned (&code)[kD2MT][8], u32x2 (&ent)[kD2MT][8]) __attribute__((always_inline)) {
         unsigned places = 0u;
         static_for<kD2MT * 8>([&](auto ic) __attribute__((always_inline)) {
             constexpr int q = decltype(ic)::value;
             if (__ballot(code[q >> 3][q & 7] >= (unsigned)kLut)) places |= 1u << q;
         });
-#ifdef DCA_DW_TIMING
-        n_visits += 1; n_places += __builtin_popcount(places);
-        if (places == 0u && g_dw_timing) {                 // (must not happen) leave the evidence: step, lane's sixteen counts packed
-            unsigned long long pk0 = 0ull, pk1 = 0ull;
-            for (int q = 0; q < 8; ++q) { pk0 |= (unsigned long long)(code[0][q] & 0xffu) << (8 * q); pk1 |= (unsigned long long)(code[1][q] & 0xffu) << (8 * q); }
-            unsigned mx = 0u;
-            for (int q = 0; q < 16; ++q) mx |= code[q >> 3][q & 7];
-            if (any_dbg >= (unsigned)kLut) {
-                long long* d = g_dw_timing + 4096 * 8;
-                d[0] = k; d[1] = (long long)pk0; d[2] = (long long)pk1; d[3] = lane + 1000 * wave; d[4] = mx; d[5] = any_dbg;
-            }
-        }
-#endif
 #pragma unroll 1
         while (places) {
             const int q = __builtin_ctz(places);
@@ -664,7 +637,6 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
         }
     };
 #define DCA_TIE8(x, m) "+v"(x[m][0]), "+v"(x[m][1]), "+v"(x[m][2]), "+v"(x[m][3]), "+v"(x[m][4]), "+v"(x[m][5]), "+v"(x[m][6]), "+v"(x[m][7])
-#define DCA_TIE_ACC "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1])
 
     if (nsteps > 0) {
         u32x4 A0[kD2MT][3], A1[kD2MT][3], B0[NTL][3], B1[NTL][3];
@@ -692,16 +664,11 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
         asm volatile("" ::: "memory");
         issue_counts(0, c0);
         int sk = 0;                                       // stage of step k
-        DWSTAMP(1)
         // One matrix instruction of the six-product scheme: product PR (0..5, small terms first) of gene tile M with dZ tile T.
         // The accumulator is tied to an (empty) instruction statement behind it: the compiler keeps the matrix instruction
         // between the LDS / vector work written before and after it.
-#ifdef DCA_EXP_DW2_NOMFMA
-#define DCA_MF(Ap, Bp, M, T, PR) { acc[M][T][PR] += __uint_as_float(Ap[M][PR % 3][0] ^ Bp[T][PR % 3][1]); asm volatile("" : "+v"(acc[M][T])); }
-#else
 #define DCA_MF(Ap, Bp, M, T, PR) { constexpr int PA_[6] = {2, 1, 0, 1, 0, 0}, PB_[6] = {0, 1, 2, 0, 1, 0}; \
             acc[M][T] = MFMA16(Ap[M][PA_[PR]], Bp[T][PB_[PR]], acc[M][T]); asm volatile("" : "+v"(acc[M][T])); }
-#endif
         // step k: cK = its counts (requested in the step before), Ap / Bp = table entries / dZ fragments of step k - 1; leaves
         // the counts of step k + 1 in cN, the operands of step k in An / Bk.  A wave's vector and LDS instructions ride behind
         // its OWN matrix instructions (about five per matrix instruction are free, tools/microbench/mfma_valu_interleave.hip);
@@ -740,7 +707,7 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
             // the sixteen entries are in registers (LDS reads return in order: the six dZ fragments and the storage row
             // behind them may still be in flight -- they are waited for at the top of the next step)
             asm volatile("s_waitcnt lgkmcnt(7)" : DCA_TIE8(ent, 0), DCA_TIE8(ent, 1));
-            if (__ballot(any >= (unsigned)kLut)) beyond_table(k, sk, cK, ent, any);
+            if (__ballot(any >= (unsigned)kLut)) beyond_table(k, sk, cK, ent);
             // ---- gene tile 1 of step k - 1, behind it: the operands of step k from its entries, the counts of step k + 1
             const unsigned cad = code_off + (unsigned)sn * kD2StageB;
             static_for<12>([&](auto ic) __attribute__((always_inline)) {
@@ -762,12 +729,14 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
                 }
             });
             retire(min(k + kD2Lead, nsteps - 1) - (k + 2));   // step k + 2 has landed (mine)
-            // the LDS reads of stage sk (six dZ fragments, the storage row) are in registers BEFORE another wave may refill that
-            // stage behind the barrier: LDS reads return in order, the sixteen count reads of stage sn issued last may stay in flight
-            asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-#ifndef DCA_EXP_DW2_NOBARRIER
+            // Behind the barrier another wave may refill stage sk, so its six dZ fragment reads must have returned by then (the
+            // entries were waited for above).  No wait here ensures it: those reads are issued before the storage-row read and the
+            // sixteen count reads of stage sn, LDS reads return in order, and the 4-bit LGKM counter holds at most 15 reads in
+            // flight -- issuing the 23 leaves the earliest 8 returned, the first count read among them.  This rests on that issue
+            // order in the generated ISA, which the compiler does not promise.  The empty statement keeps the compiler from
+            // moving memory operations across the barrier (__builtin_amdgcn_s_barrier alone does not).
+            asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
-#endif
             asm volatile("" ::: "memory");
             sk = sn;
         };
@@ -794,16 +763,8 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
                 for (int t = 0; t < NTL; ++t) { MFMA_X3(A0[m], B0[t], acc[m][t]) }
         }
 #undef DCA_MF
-        DWSTAMP(2)
-#ifdef DCA_DW_TIMING
-        if (g_dw_timing && lane == 0 && n_visits) {
-            atomicAdd((unsigned long long*)&g_dw_timing[(blockIdx.x + blockIdx.y * gridDim.x) * 8 + 6], (unsigned long long)n_visits);
-            atomicAdd((unsigned long long*)&g_dw_timing[(blockIdx.x + blockIdx.y * gridDim.x) * 8 + 7], (unsigned long long)n_places);
-        }
-#endif
     }
 #undef DCA_TIE8
-#undef DCA_TIE_ACC
     if (bx == 0 && tid < H1) split_column_sums<H1>(a.Spp, a.Sp, split, rb / kKS, (re + kKS - 1) / kKS, tid);
 #pragma unroll
     for (int m = 0; m < kD2MT; ++m)
@@ -812,7 +773,6 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
             for (int e = 0; e < 16; ++e)
                 a.P[((long)split * a.Gs + g0 + 32 * m + rowmap(e, hi)) * H1 + 32 * t + l31] = acc[m][t][e];
-    DWSTAMP(3) DWSTAMP(5)
 }
 
 // splits of the batch for the second form: one workgroup per CU (256 slots), at least one 32-row block each, at most
@@ -872,175 +832,6 @@ __global__ __launch_bounds__(256) void enc0_dw_finish_kernel(DwFinishArgs a) {
         dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
     }
 }
-
-// (The round-2 forward over the NON-ZERO counts only -- gathers of W0 rows on the vector pipe -- lost to the dense product at
-// every batch size and is an experiment build: -DDCA_EXP_ENC0_SPARSE_FWD, tools/bench_enc0.py.)
-#ifdef DCA_EXP_ENC0_SPARSE_FWD
-// ------------------------------------------------------------------------------------------------- forward
-constexpr int kC0Blocks = 128;
-
-struct C0Args {
-    const float* W; long ldw; const float* bias; const float* mean; const float* stdv;
-    int G, H1;
-    double* part;                   // [kC0Blocks][H1]
-    unsigned* ticket;
-    float* beff;                    // [H1]
-};
-
-// b_eff[j] = bias[j] - sum_g (mean[g] / std[g]) W[g, j]; the last-arriving workgroup adds the partials in order
-__global__ __launch_bounds__(256) void enc0_c0_kernel(C0Args a) {
-    __shared__ double red[256];
-    __shared__ int is_last;
-    const int tid = threadIdx.x;
-    const int col = tid % a.H1, ph = tid / a.H1, nph = 256 / a.H1;
-    const int per = (a.G + kC0Blocks - 1) / kC0Blocks;
-    const int gb0 = blockIdx.x * per, gb1 = min(a.G, gb0 + per);
-    double s = 0.0;
-    for (int g = gb0 + ph; g < gb1; g += nph) {
-        const float t = a.stdv ? __fdiv_rn(a.mean[g], a.stdv[g]) : a.mean[g];
-        s += (double)t * (double)a.W[(long)g * a.ldw + col];
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (tid < a.H1) {
-        double v = 0.0;
-        for (int k = 0; k < nph; ++k) v += red[k * a.H1 + tid];
-        a.part[(long)blockIdx.x * a.H1 + tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = t == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    {                                                    // the partials in a fixed order: phases of blocks, then the phases
-        double v = 0.0;
-        for (unsigned k = ph; k < gridDim.x; k += nph)
-            v += __hip_atomic_load(a.part + (long)k * a.H1 + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        red[tid] = v;
-    }
-    __syncthreads();
-    if (tid < a.H1) {
-        double v = 0.0;
-        for (int k = 0; k < nph; ++k) v += red[k * a.H1 + tid];
-        a.beff[tid] = (a.bias ? a.bias[tid] : 0.f) - (float)v;
-    }
-    if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct FwArgs {
-    Compact c;
-    const float* fac; int do_log;
-    const float* stdv;
-    const int* perm; const long long* cursor; long row_base;
-    int B, G;
-    const float* W; long ldw;
-    const float* beff;
-    float* Z; long ldz;
-};
-
-constexpr int kFwCap = 320;
-
-template <int H1>
-__global__ __launch_bounds__(256) void enc0_fwd_kernel(FwArgs a) {
-    constexpr int LPE = H1 / 4, EPI = 64 / LPE;
-    __shared__ unsigned q[4][kFwCap];
-    __shared__ uint2 qe[4][64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = blockIdx.x * 4 + wave;
-    if (c >= a.B) return;
-    const long long cur = (a.cursor ? *a.cursor : 0) + a.row_base;
-    const long sr = a.perm ? (long)a.perm[cur + c] : cur + c;
-    const float facr = a.fac ? a.fac[sr] : 1.f;
-    unsigned* const Q = q[wave];
-    uint2* const QE = qe[wave];
-    const int grp = lane / LPE, lidx = lane - grp * LPE;
-    const char* const wb = reinterpret_cast<const char*>(a.W) + lidx * 16;
-    const unsigned ldwb = (unsigned)(a.ldw * 4);
-    const unsigned char* const yrow = a.c.yc + sr * a.c.ldc;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    int qn = 0;
-
-    auto flush = [&](bool all) {
-        wave_sync();
-        while (qn >= 64 || (all && qn > 0)) {
-            const int n = min(64, qn);
-            const unsigned e = lane < n ? Q[qn - n + lane] : 0u;
-            const unsigned code = e & 255u;
-            const int gene = (int)(e >> 8);
-            float val = (float)code;
-            if (code == 255u) val = escaped_count(a.c, sr, gene);
-            float x = a.fac ? __fdiv_rn(val, facr) : val;
-            if (a.do_log) x = log1pf(x);
-            if (a.stdv) x = __fdiv_rn(x, a.stdv[gene]);
-            QE[lane] = make_uint2(__float_as_uint(x), (unsigned)gene * ldwb);
-            wave_sync();
-            // every row of W the batch needs is requested before the first product (lanes beyond n hold x = 0, row 0):
-            // the gathers come from L2 and their latency, not their number, is what a wave waits for
-            constexpr int NIT = 64 / EPI, HALF = NIT > 8 ? 8 : NIT;
-            const int nit = (n + EPI - 1) / EPI;
-#pragma unroll 1
-            for (int h0 = 0; h0 < nit; h0 += HALF) {
-                uint2 en[HALF];
-                float4 w[HALF];
-#pragma unroll
-                for (int it = 0; it < HALF; ++it) en[it] = QE[(h0 + it) * EPI + grp];
-#pragma unroll
-                for (int it = 0; it < HALF; ++it) w[it] = *reinterpret_cast<const float4*>(wb + en[it].y);
-#pragma unroll
-                for (int it = 0; it < HALF; ++it) {
-                    const float xv = __uint_as_float(en[it].x);
-                    acc.x = fmaf(xv, w[it].x, acc.x); acc.y = fmaf(xv, w[it].y, acc.y);
-                    acc.z = fmaf(xv, w[it].z, acc.z); acc.w = fmaf(xv, w[it].w, acc.w);
-                }
-            }
-            qn -= n;
-            wave_sync();
-        }
-    };
-
-    const int nch = (int)((a.c.ldc + 1023) >> 10);
-    uint4 nxt = make_uint4(0u, 0u, 0u, 0u);
-    if (lane * 16 < a.c.ldc) nxt = *reinterpret_cast<const uint4*>(yrow + lane * 16);
-#pragma unroll 1
-    for (int ch = 0; ch < nch; ++ch) {
-        const uint4 codes = nxt;
-        const int gbase = ch * 1024 + lane * 16;
-        nxt = make_uint4(0u, 0u, 0u, 0u);
-        if (ch + 1 < nch && gbase + 1024 < a.c.ldc) nxt = *reinterpret_cast<const uint4*>(yrow + gbase + 1024);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const unsigned dw = d == 0 ? codes.x : d == 1 ? codes.y : d == 2 ? codes.z : codes.w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned code = (dw >> (8 * k)) & 255u;
-                const bool nz = code != 0u;
-                const unsigned long long m = __ballot(nz);
-                if (nz) Q[qn + mbcnt64(m)] = code | ((unsigned)(gbase + 4 * d + k) << 8);
-                qn += __popcll(m);
-            }
-            if (qn > kFwCap - 256) flush(false);
-        }
-    }
-    flush(true);
-#pragma unroll
-    for (int off = LPE; off < 64; off <<= 1) {
-        acc.x += __shfl_xor(acc.x, off, 64); acc.y += __shfl_xor(acc.y, off, 64);
-        acc.z += __shfl_xor(acc.z, off, 64); acc.w += __shfl_xor(acc.w, off, 64);
-    }
-    if (lane < LPE) {
-        const float4 b = a.beff ? *reinterpret_cast<const float4*>(a.beff + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float* dst = a.Z + (long)c * a.ldz + 4 * lane;
-        *reinterpret_cast<float4*>(dst) = make_float4(acc.x + b.x, acc.y + b.y, acc.z + b.z, acc.w + b.w);
-    }
-}
-
-#endif  // DCA_EXP_ENC0_SPARSE_FWD
 
 // ------------------------------------------------------------------------------------------------- forward on the matrix pipe
 // Z0 = L (W0 / std) + b_eff as a dense product whose A operand is LOOKED UP from the byte store (the mirror image of
@@ -1117,11 +908,10 @@ struct FlArgs {
     int n_ms, ms_per;               // macro steps in all / per gene chunk
 };
 
-// RT = 32-row tiles per wave: 1 -> eight waves of 32 rows (two per SIMD), 2 -> four waves of 64 rows (one per SIMD, the W
-// fragments of a K step read from LDS once for both tiles).
-template <int H1, int RT>
-__global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(FlArgs a) {
-    constexpr int NT = kFlRows / (32 * RT) * 64;
+// Eight waves of 32 batch rows each, two per SIMD.
+template <int H1>
+__global__ __launch_bounds__(kFlRows / 32 * 64) void enc0_fwd_lut_kernel(FlArgs a) {
+    constexpr int NT = kFlRows / 32 * 64;
     constexpr int NTL = H1 / 32, MSE = fl_ms_elems(H1), UNITS = MSE / 8, UPT = (UNITS + NT - 1) / NT;
     __shared__ __attribute__((aligned(16))) uint2 lutl[kFlRows * kFlLutLd];
     __shared__ __attribute__((aligned(16))) unsigned short wl[2][MSE];
@@ -1160,23 +950,17 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
         const int u = tid + NT * k;
         lv[k] = *reinterpret_cast<const u32x4*>(a.lutp + (long)srows[u / (kFlLut / 2)] * kLut + (u % (kFlLut / 2)) * 2);
     }
-    long sr[RT]; float facr[RT]; const unsigned char* yrow[RT]; unsigned lp_ad[RT];
+    const int myrow = wave * 32 + l31;
+    const long sr = srows[myrow];
+    const float facr = a.fac ? a.fac[sr] : 1.f;
+    const unsigned char* const yrow = a.c.yc + sr * a.c.ldc + 64 * hi;
+    const unsigned lp_ad = (unsigned)(size_t)(__attribute__((address_space(3))) uint2*)lutl + (unsigned)myrow * (kFlLutLd * 8);
+    f32x16 acc[NTL];
 #pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        const int myrow = wave * (32 * RT) + 32 * r + l31;
-        sr[r] = srows[myrow];
-        facr[r] = a.fac ? a.fac[sr[r]] : 1.f;
-        yrow[r] = a.c.yc + sr[r] * a.c.ldc + 64 * hi;
-        lp_ad[r] = (unsigned)(size_t)(__attribute__((address_space(3))) uint2*)lutl + (unsigned)myrow * (kFlLutLd * 8);
-    }
-    f32x16 acc[RT][NTL];
+    for (int t = 0; t < NTL; ++t)
 #pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int t = 0; t < NTL; ++t)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r][t][e] = 0.f;
-    u32x4 cq[RT][4], cn[RT][4], wr[UPT];
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+    u32x4 cq[4], cn[4], wr[UPT];
     // every load of the loop is unconditional (addresses clamped, results selected): the loads of a step then form one
     // straight queue -- tile first, counts after -- and the wait before the tile's LDS store leaves the counts in flight
     const int ss_last = a.n_ms / 2 - 1;
@@ -1185,19 +969,15 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
     };
     auto load_codes = [&](int ss) __attribute__((always_inline)) {        // raw: take_codes masks them
 #pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                cn[r][i] = *reinterpret_cast<const u32x4*>(yrow[r] + (codes_ok(ss, i) ? (long)min(ss, ss_last) * (2 * kFlMS) + 16 * i : -64L * hi));
+        for (int i = 0; i < 4; ++i)
+            cn[i] = *reinterpret_cast<const u32x4*>(yrow + (codes_ok(ss, i) ? (long)min(ss, ss_last) * (2 * kFlMS) + 16 * i : -64L * hi));
     };
     auto take_codes = [&](int ss) __attribute__((always_inline)) {        // the first use of the loaded bytes
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool ok = codes_ok(ss, i);
 #pragma unroll
-            for (int r = 0; r < RT; ++r)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) cq[r][i][k] = ok ? cn[r][i][k] : 0u;
+            for (int k = 0; k < 4; ++k) cq[i][k] = ok ? cn[i][k] : 0u;
         }
     };
     auto load_w = [&](int ms) __attribute__((always_inline)) {
@@ -1222,18 +1002,17 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
         lutl[row * kFlLutLd + seg * 2 + 1] = make_uint2(lv[k][2], lv[k][3]);
     }
     if (ms0 < ms1) { store_w(0); take_codes(ms0 >> 1); }
-    // ---- software pipeline over the K steps (16 genes; four per macro step): while the 6 NTL RT matrix instructions of K step
-    // k run, the wave looks up the 8 RT values of K step k + 1, reads its W fragments and repacks the entries -- its OWN LDS /
+    // ---- software pipeline over the K steps (16 genes; four per macro step): while the 6 NTL matrix instructions of K step
+    // k run, the wave looks up the 8 values of K step k + 1, reads its W fragments and repacks the entries -- its OWN LDS /
     // vector instructions between its own matrix instructions (the other wave of the SIMD does not hide them: round 5, DESIGN
     // 4.3).  The LDS reads are instruction statements in the order written; each matrix instruction's accumulator is tied to
     // an empty statement so that the compiler keeps it between them.  One barrier per macro step, between its K steps 2 and
     // 3: K step 3 already prepares K step 0 of the next macro step from the other W tile.
     const unsigned wl_ad = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned short*)wl[0] + (unsigned)(hi * 32 + l31) * 16u;
-    u32x4 A0[RT][3], A1[RT][3], Bf0[NTL][3], Bf1[NTL][3];
-    u32x2 ent[RT][8];
-    // the formula for the values of one K step of row tile r beyond the table (rare; `gene0` = gene of the step's first value)
-    auto beyond_table = [&](auto rc, unsigned d0, unsigned d1, int gene0) __attribute__((always_inline)) {
-        constexpr int r = decltype(rc)::value;
+    u32x4 A0[3], A1[3], Bf0[NTL][3], Bf1[NTL][3];
+    u32x2 ent[8];
+    // the formula for the values of one K step beyond the table (rare; `gene0` = gene of the step's first value)
+    auto beyond_table = [&](unsigned d0, unsigned d1, int gene0) __attribute__((always_inline)) {
         unsigned bad = 0u;
 #pragma unroll
         for (int j = 0; j < 8; ++j) bad |= ((((j >> 2) ? d1 : d0) >> (8 * (j & 3) + 5)) & 7u) != 0u ? 1u << j : 0u;
@@ -1246,87 +1025,68 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
             const unsigned code = (dw >> (8 * (j & 3))) & 255u;
             float val = (float)code;
             if (__ballot(on && code == 255u)) {     // an escape: the count itself from the row's overflow list
-                if (on && code == 255u) val = escaped_count(a.c, sr[r], gene0 + j);
+                if (on && code == 255u) val = escaped_count(a.c, sr, gene0 + j);
             }
-            float x = a.fac ? __fdiv_rn(val, facr[r]) : val;
+            float x = a.fac ? __fdiv_rn(val, facr) : val;
             if (a.do_log) x = log1p_beyond_table(x);
             const uint2 e = split_entry(x);
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                if (on && j == k) { ent[r][k][0] = e.x; ent[r][k][1] = e.y; }
+                if (on && j == k) { ent[k][0] = e.x; ent[k][1] = e.y; }
         }
     };
-    // the work for K step `kn` (of the macro step whose counts are d[][], W tile `bn`), cut into twelve pieces that ride behind
+    // the work for K step `kn` (of the macro step whose counts are d[], W tile `bn`), cut into twelve pieces that ride behind
     // the matrix instructions of the K step before it: piece v of prepare<KN>(...)
-    auto prepare = [&](auto kn_c, auto v_c, const unsigned (&d)[RT][8], int bn, int gene0, u32x4 (&An)[RT][3], u32x4 (&Bn)[NTL][3]) __attribute__((always_inline)) {
+    auto prepare = [&](auto kn_c, auto v_c, const unsigned (&d)[8], int bn, int gene0, u32x4 (&An)[3], u32x4 (&Bn)[NTL][3]) __attribute__((always_inline)) {
         constexpr int KN = decltype(kn_c)::value, V = decltype(v_c)::value;
         const unsigned wad = wl_ad + (unsigned)bn * (MSE * 2);
-        if constexpr (V < 4) {                       // lookups 2 V, 2 V + 1 of every row tile
+        if constexpr (V < 4) {                       // lookups 2 V, 2 V + 1
 #pragma unroll
-            for (int r = 0; r < RT; ++r)
-#pragma unroll
-                for (int j = 2 * V; j < 2 * V + 2; ++j) {
-                    const unsigned idx = (d[r][2 * KN + (j >> 2)] >> (8 * (j & 3))) & (unsigned)(kFlLut - 1);
-                    lds_read_b64<0>(ent[r][j], lp_ad[r] + idx * 8u);
-                }
+            for (int j = 2 * V; j < 2 * V + 2; ++j) {
+                const unsigned idx = (d[2 * KN + (j >> 2)] >> (8 * (j & 3))) & (unsigned)(kFlLut - 1);
+                lds_read_b64<0>(ent[j], lp_ad + idx * 8u);
+            }
         } else if constexpr (V < 7) {                // W fragments 2 (V - 4), 2 (V - 4) + 1 of 3 NTL
             constexpr int f0 = 2 * (V - 4), f1 = f0 + 1;
             if constexpr (f0 < 3 * NTL) lds_read_b128<(((f0 % 3) * NTL + f0 / 3) * 4 + KN) * 1024>(Bn[f0 / 3][f0 % 3], wad);
             if constexpr (f1 < 3 * NTL) lds_read_b128<(((f1 % 3) * NTL + f1 / 3) * 4 + KN) * 1024>(Bn[f1 / 3][f1 % 3], wad);
         } else if constexpr (V == 7) {               // the entries are in registers (the W fragments behind them may be in flight)
-#define DCA_ENT8(r) "+v"(ent[r][0]), "+v"(ent[r][1]), "+v"(ent[r][2]), "+v"(ent[r][3]), "+v"(ent[r][4]), "+v"(ent[r][5]), "+v"(ent[r][6]), "+v"(ent[r][7])
-            if constexpr (NTL == 2) asm volatile("s_waitcnt lgkmcnt(6)" : DCA_ENT8(0));
-            else asm volatile("s_waitcnt lgkmcnt(3)" : DCA_ENT8(0));
-            if constexpr (RT == 2) asm volatile("" : DCA_ENT8(RT - 1));
+#define DCA_ENT8 "+v"(ent[0]), "+v"(ent[1]), "+v"(ent[2]), "+v"(ent[3]), "+v"(ent[4]), "+v"(ent[5]), "+v"(ent[6]), "+v"(ent[7])
+            if constexpr (NTL == 2) asm volatile("s_waitcnt lgkmcnt(6)" : DCA_ENT8);
+            else asm volatile("s_waitcnt lgkmcnt(3)" : DCA_ENT8);
 #undef DCA_ENT8
-#ifndef DCA_EXP_FWD_NOFORMULA
-            static_for<RT>([&](auto rc) __attribute__((always_inline)) {
-                constexpr int r = decltype(rc)::value;
-                if (__ballot(((d[r][2 * KN] | d[r][2 * KN + 1]) & 0xe0e0e0e0u) != 0u)) beyond_table(rc, d[r][2 * KN], d[r][2 * KN + 1], gene0 + 8 * KN);
-            });
-#endif
-        } else {                                     // V = 8 .. 11: three of the twelve operand registers of every row tile
+            if (__ballot(((d[2 * KN] | d[2 * KN + 1]) & 0xe0e0e0e0u) != 0u)) beyond_table(d[2 * KN], d[2 * KN + 1], gene0 + 8 * KN);
+        } else {                                     // V = 8 .. 11: three of the twelve operand registers
 #pragma unroll
-            for (int r = 0; r < RT; ++r) {
-#pragma unroll
-                for (int x = 3 * (V - 8); x < 3 * (V - 8) + 3; ++x) {
-                    const int q = x >> 2, jj = x & 3;
-                    An[r][q][jj] = __builtin_amdgcn_perm(ent[r][2 * jj + 1][q == 2 ? 1 : 0], ent[r][2 * jj][q == 2 ? 1 : 0], q == 1 ? 0x07060302u : 0x05040100u);
-                }
-                if constexpr (V == 9) asm volatile("" : "+v"(An[r][0]));
-                if constexpr (V == 10) asm volatile("" : "+v"(An[r][1]));
-                if constexpr (V == 11) asm volatile("" : "+v"(An[r][2]));
+            for (int x = 3 * (V - 8); x < 3 * (V - 8) + 3; ++x) {
+                const int q = x >> 2, jj = x & 3;
+                An[q][jj] = __builtin_amdgcn_perm(ent[2 * jj + 1][q == 2 ? 1 : 0], ent[2 * jj][q == 2 ? 1 : 0], q == 1 ? 0x07060302u : 0x05040100u);
             }
+            if constexpr (V == 9) asm volatile("" : "+v"(An[0]));
+            if constexpr (V == 10) asm volatile("" : "+v"(An[1]));
+            if constexpr (V == 11) asm volatile("" : "+v"(An[2]));
         }
     };
-    // K step K of the current macro step: its 6 NTL RT matrix instructions (operands Ac, Bc), the next K step's preparation between
-    auto kstep = [&](auto kn_c, const unsigned (&dn)[RT][8], int bn, int gene0n, u32x4 (&Ac)[RT][3], u32x4 (&Bc)[NTL][3], u32x4 (&An)[RT][3], u32x4 (&Bn)[NTL][3]) __attribute__((always_inline)) {
+    // K step K of the current macro step: its 6 NTL matrix instructions (operands Ac, Bc), the next K step's preparation between
+    auto kstep = [&](auto kn_c, const unsigned (&dn)[8], int bn, int gene0n, u32x4 (&Ac)[3], u32x4 (&Bc)[NTL][3], u32x4 (&An)[3], u32x4 (&Bn)[NTL][3]) __attribute__((always_inline)) {
         // (the W fragments of this K step: the only LDS reads still in flight)
         if constexpr (NTL == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Bc[0][0]), "+v"(Bc[0][1]), "+v"(Bc[0][2]), "+v"(Bc[1][0]), "+v"(Bc[1][1]), "+v"(Bc[1][2]));
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Bc[0][0]), "+v"(Bc[0][1]), "+v"(Bc[0][2]));
-        constexpr int NS = 6 * NTL * RT;
+        constexpr int NS = 6 * NTL;
         static_for<NS>([&](auto ic) __attribute__((always_inline)) {
-            constexpr int i = decltype(ic)::value, T = i % NTL, R = (i / NTL) % RT, PR = i / (NTL * RT);
+            constexpr int i = decltype(ic)::value, T = i % NTL, PR = i / NTL;
             constexpr int PA_[6] = {2, 1, 0, 1, 0, 0}, PB_[6] = {0, 1, 2, 0, 1, 0};
-#ifdef DCA_EXP_FWD_NOMFMA
-            acc[R][T][PR] += __uint_as_float(Ac[R][PA_[PR]][0] ^ Bc[T][PB_[PR]][1]);
-#else
-            acc[R][T] = MFMA16(Ac[R][PA_[PR]], Bc[T][PB_[PR]], acc[R][T]);
-#endif
-            // (one wave per SIMD: the accumulators live in the AGPR half of its 512 registers -- a "+v" tie would copy them
-            // to vector registers and back around every matrix instruction)
-            if constexpr (RT == 2) asm volatile("" : "+a"(acc[R][T])); else asm volatile("" : "+v"(acc[R][T]));
+            acc[T] = MFMA16(Ac[PA_[PR]], Bc[T][PB_[PR]], acc[T]);
+            asm volatile("" : "+v"(acc[T]));
             constexpr int v0 = i * 12 / NS, v1 = (i + 1) * 12 / NS;          // pieces [v0, v1) behind this matrix instruction
             static_for<v1 - v0>([&](auto jc) __attribute__((always_inline)) {
                 prepare(kn_c, std::integral_constant<int, v0 + decltype(jc)::value>{}, dn, bn, gene0n, An, Bn);
             });
         });
     };
-    auto codes_of = [&](int h, unsigned (&d)[RT][8]) __attribute__((always_inline)) {
+    auto codes_of = [&](int h, unsigned (&d)[8]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { d[r][k] = cq[r][2 * h][k]; d[r][4 + k] = cq[r][2 * h + 1][k]; }
+        for (int k = 0; k < 4; ++k) { d[k] = cq[2 * h][k]; d[4 + k] = cq[2 * h + 1][k]; }
     };
     using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>;
     using K2 = std::integral_constant<int, 2>; using K3 = std::integral_constant<int, 3>;
@@ -1336,7 +1096,7 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
         constexpr int h = decltype(half)::value, b = h;
         load_w(ms + 1);                     // (past the chunk's end: a tile nobody reads)
         if (h == 0) load_codes((ms >> 1) + 1);
-        unsigned d[RT][8], dn[RT][8];
+        unsigned d[8], dn[8];
         codes_of(h, d);
         const int gene0 = (ms >> 1) * (2 * kFlMS) + 64 * hi + 32 * h;
         kstep(K1{}, d, b, gene0, A0, Bf0, A1, Bf1);
@@ -1345,14 +1105,12 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
         store_w(b ^ 1);
         if (h == 1) take_codes((ms >> 1) + 1);              // the next super step's counts (requested a super step ago)
         codes_of(h ^ 1, dn);
-#ifndef DCA_EXP_FWD_NOBARRIER
         __syncthreads();                    // tile b ^ 1 is in LDS; everyone's reads of tile b are in registers
-#endif
         kstep(K0{}, dn, b ^ 1, (((ms + 1) >> 1) * (2 * kFlMS)) + 64 * hi + 32 * (h ^ 1), A1, Bf1, A0, Bf0);
     };
     if (ms0 < ms1) {                        // the operands of the first K step (no matrix instructions to put them behind)
         __syncthreads();                    // tile 0 and the tables are in LDS
-        unsigned d[RT][8];
+        unsigned d[8];
         codes_of(0, d);
         const int gene0 = (ms0 >> 1) * (2 * kFlMS) + 64 * hi;
         static_for<12>([&](auto vc) __attribute__((always_inline)) { prepare(K0{}, vc, d, 0, gene0, A0, Bf0); });
@@ -1367,15 +1125,12 @@ __global__ __launch_bounds__(kFlRows / (32 * RT) * 64) void enc0_fwd_lut_kernel(
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Bf0[0][0]), "+v"(Bf0[0][1]), "+v"(Bf0[0][2]));
     }
     if (ms0 >= ms1) __syncthreads();        // (an empty chunk never passed a barrier after csum was written)
+    float* const dst = a.P + ((long)blockIdx.y * a.Bp + rg0 + wave * 32) * H1;
 #pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        float* const dst = a.P + ((long)blockIdx.y * a.Bp + rg0 + wave * (32 * RT) + 32 * r) * H1;
+    for (int t = 0; t < NTL; ++t) {
+        const float c0 = csum[32 * t + l31];
 #pragma unroll
-        for (int t = 0; t < NTL; ++t) {
-            const float c0 = csum[32 * t + l31];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dst[(long)rowmap(e, hi) * H1 + 32 * t + l31] = acc[r][t][e] + c0;
-        }
+        for (int e = 0; e < 16; ++e) dst[(long)rowmap(e, hi) * H1 + 32 * t + l31] = acc[t][e] + c0;
     }
 }
 
@@ -1410,8 +1165,6 @@ inline int fl_ms_per(int B, int G) {
     return 2 * ((n_ss + nsk - 1) / nsk);
 }
 
-inline bool width_ok(int H1) { return H1 == 16 || H1 == 32 || H1 == 64 || H1 == 128 || H1 == 256; }
-
 inline bool dw_width_ok(int H1) { return H1 == 32 || H1 == 64 || H1 == 128; }
 
 // row splits: as many workgroups as are resident at once (or just below): one round
@@ -1439,103 +1192,6 @@ inline int dw_rows_per_split(int B, int ns, int H1, int form) {
 }
 inline long r16(long x) { return (x + 15) / 16 * 16; }
 
-
-// (The byte-store weight gradient for batches of at most 64 rows measured 11.2 us against the GEMM's 7.4 us at batch 32
-// (profiles/r05g_*): an experiment build, -DDCA_EXP_DW_SMALL.)
-#ifdef DCA_EXP_DW_SMALL
-// ------------------------------------------------------------------------------------------------- small batches
-// The first layer's weight gradient at the reference's default batch (32 rows, dca/train.py:37; up to 64 here) straight
-// from the byte store: dW0[g, :] = (sum over the batch rows with a NON-ZERO count of f(y / fac) dZ[r, :] - mean[g] colsum(dZ)) / std[g]
-// -- about two terms per gene at 93 % zeros -- instead of a rank-32 update through the GEMM (14 us + a split-K reduce at
-// G = 20 000).  A group of 16 lanes owns one gene (lane t: hidden units 4 t .. 4 t + 3: one 16-byte store), a workgroup
-// kGenesSmall genes; dZ, its column sums, the storage rows and the per-cell divisors sit in LDS.  fp32 FMAs in row order:
-// deterministic.  Row G of gW = colsum(dZ) (the bias gradient, as dcahip_sgemm's colsum_row).  The kernel is bound by
-// memory round trips and instruction fetch, not by work: the workgroup requests its 16 x B count bytes in one round trip into
-// LDS and walks them in ONE compact loop body (measured at G = 20 000, batch 32: four genes per group with eight requests in
-// flight 44 us; all 32 requests at once but unrolled bodies with libm's log1pf 35 us, with the fast logarithm 22 us; the GEMM
-// + split-K reduce it replaces 19 us).
-constexpr int kSmallRows = 64;
-constexpr int kGenesSmall = 16;          // per workgroup: one gene per group of 16 lanes
-
-struct DwSmallArgs {
-    Compact c;
-    const float* fac; int do_log;
-    const float* mean; const float* stdv;
-    const int* perm; const long long* cursor; long row_base;
-    int B, G, H1;
-    const float* dZ; long ldz;
-    float* gW; long ldg;
-};
-
-__global__ __launch_bounds__(256) void enc0_dw_small_kernel(DwSmallArgs a) {
-    __shared__ __attribute__((aligned(16))) float dz[kSmallRows * 64];
-    __shared__ float cs[64];
-    __shared__ int srow[kSmallRows];
-    __shared__ float rfac[kSmallRows];
-    __shared__ unsigned char codes[kSmallRows][kGenesSmall];
-    const int tid = threadIdx.x;
-    const long cur = a.cursor ? (long)*a.cursor : 0;
-    const int H4 = a.H1 >> 2;
-    const int g0 = blockIdx.x * kGenesSmall;
-    // every request of the workgroup in ONE memory round trip behind the row indices: thread (row, gene) takes the count
-    // byte of its pair straight away (its row index from memory, not from LDS), rows 0 .. 15, then 16 .. 31, ...
-    {
-        const int gl = tid & 15;
-        const int gene = g0 + gl < a.G ? g0 + gl : a.G - 1;
-        for (int r = tid >> 4; r < a.B; r += 16) {
-            const long rr = cur + a.row_base + r;
-            const int sr = a.perm ? a.perm[rr] : (int)rr;
-            codes[r][gl] = a.c.yc[(unsigned long long)(unsigned)sr * (unsigned long long)a.c.ldc + gene];
-            if (gl == 0) { srow[r] = sr; rfac[r] = a.fac ? 1.f / a.fac[sr] : 1.f; }
-        }
-    }
-    for (int i = tid; i < a.B * 16; i += 256) {
-        const int r = i >> 4, q = i & 15;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < H4) v = *reinterpret_cast<const float4*>(a.dZ + (long)r * a.ldz + 4 * q);
-        *reinterpret_cast<float4*>(dz + r * 64 + 4 * q) = v;
-    }
-    __syncthreads();
-    if (tid < 64) {
-        float v = 0.f;
-        for (int r = 0; r < a.B; ++r) v += dz[r * 64 + tid];
-        cs[tid] = v;
-    }
-    __syncthreads();
-    const int t = tid & 15, grp = tid >> 4;
-    if (blockIdx.x == 0 && tid < H4)           // the bias gradient
-        *reinterpret_cast<float4*>(a.gW + (long)a.G * a.ldg + 4 * tid) = *reinterpret_cast<const float4*>(cs + 4 * tid);
-    const int gene = g0 + grp;
-    if (t >= H4 || gene >= a.G) return;
-    const float4 c4 = *reinterpret_cast<const float4*>(cs + 4 * t);
-    const float m = a.mean ? a.mean[gene] : 0.f;
-    const float sd = a.stdv ? a.stdv[gene] : 1.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-    for (int r = 0; r < a.B; ++r) {             // (one compact body: the unrolled form spent its time fetching instructions)
-        const unsigned code = codes[r][grp];
-        if (code == 0u) continue;
-        float val = (float)code;
-        if (code == 255u) val = escaped_count(a.c, srow[r], gene);
-        float L = val * rfac[r];
-        if (a.do_log) {
-            // log1p on the transcendental unit (v_log_f32, 1 ulp) with Kahan's exact-ratio correction of the rounded 1 + L:
-            // ~2e-7 relative for the arguments counts produce (L >= 1 / fac)
-            const float u = 1.f + L, d1 = u - 1.f;
-            const float lg = __builtin_amdgcn_logf(u) * 0.69314718055994531f;
-            L = d1 == 0.f ? L : lg * (L * __builtin_amdgcn_rcpf(d1));
-        }
-        const float4 d = *reinterpret_cast<const float4*>(dz + r * 64 + 4 * t);
-        acc.x = fmaf(L, d.x, acc.x); acc.y = fmaf(L, d.y, acc.y); acc.z = fmaf(L, d.z, acc.z); acc.w = fmaf(L, d.w, acc.w);
-    }
-    const float is = 1.f / sd;
-    float4 o;
-    o.x = (acc.x - m * c4.x) * is; o.y = (acc.y - m * c4.y) * is; o.z = (acc.z - m * c4.z) * is; o.w = (acc.w - m * c4.w) * is;
-    *reinterpret_cast<float4*>(a.gW + (long)gene * a.ldg + 4 * t) = o;
-}
-
-#endif  // DCA_EXP_DW_SMALL
-
 }  // namespace
 
 extern "C" long dcahip_counts_compact_ld(int G) { return ((long)G + 15) / 16 * 16; }
@@ -1549,24 +1205,6 @@ extern "C" int dcahip_counts_compact(const float* Y, long ldy, int n, int G, uns
                        Y, ldy, n, G, Yc, ldc, status);
     return (int)hipGetLastError();
 }
-
-#ifdef DCA_EXP_DW_SMALL
-extern "C" int dcahip_enc0_dw_small_max_rows(void) { return kSmallRows; }
-
-extern "C" int dcahip_enc0_dw_small(const unsigned char* Yc, long ldc, const int* ovf_ptr, const int* ovf_col,
-                                    const float* ovf_val, const float* fac, int do_log, const float* mean, const float* stdv,
-                                    const int* perm, const long long* cursor, long row_base, int B, int G, int H1,
-                                    const float* dZ, long ldz, float* gW, long ldg, void* stream) {
-    if (!Yc || !dZ || !gW || B <= 0 || B > kSmallRows || G <= 0 || H1 <= 0 || H1 > 64 || (H1 & 3) || ldc < G || ldz < H1 || ldg < H1 ||
-        (ldz & 3) || (ldg & 3) || ((reinterpret_cast<uintptr_t>(dZ) | reinterpret_cast<uintptr_t>(gW)) & 15))
-        return DCAHIP_EINVAL;
-    DwSmallArgs a{Compact{Yc, ldc, ovf_ptr, ovf_col, ovf_val}, fac, do_log, mean, stdv, perm, cursor, row_base, B, G, H1, dZ, ldz, gW, ldg};
-    hipLaunchKernelGGL(enc0_dw_small_kernel, dim3((unsigned)((G + kGenesSmall - 1) / kGenesSmall)), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-#endif  // DCA_EXP_DW_SMALL
 
 extern "C" int dcahip_enc0_sparse_supported(int H1) { return dw_width_ok(H1) ? 1 : 0; }
 
@@ -1589,9 +1227,6 @@ extern "C" long dcahip_enc0_dw_sparse_workspace_bytes(int B, int G, int H1) {
 }
 
 
-#ifdef DCA_DW_TIMING
-extern "C" void dcahip_enc0_dw_set_timing(long long* buf) { hipMemcpyToSymbol(HIP_SYMBOL(g_dw_timing), &buf, sizeof(buf)); }
-#endif
 extern "C" int dcahip_enc0_lut_entries(void) { return kLut; }
 
 extern "C" int dcahip_enc0_dw_sparse(const unsigned char* Yc, long ldc, const int* ovf_ptr, const int* ovf_col,
@@ -1644,57 +1279,6 @@ extern "C" int dcahip_enc0_dw_sparse(const unsigned char* Yc, long ldc, const in
     return (int)hipGetLastError();
 }
 
-#ifdef DCA_EXP_ENC0_SPARSE_FWD
-extern "C" long dcahip_enc0_fwd_sparse_workspace_bytes(int H1) {
-    return width_ok(H1) ? (long)kC0Blocks * H1 * 8 + 256 + (long)H1 * 4 : 0;
-}
-
-extern "C" int dcahip_enc0_fwd_sparse(const unsigned char* Yc, long ldc, const int* ovf_ptr, const int* ovf_col,
-                                      const float* ovf_val, const float* fac, int do_log, const float* mean,
-                                      const float* stdv, const int* perm, const long long* cursor, long row_base,
-                                      int B, int G, int H1, const float* W, long ldw, const float* bias,
-                                      float* Z, long ldz, void* workspace, long workspace_bytes, void* stream) {
-    if (!width_ok(H1) || B <= 0 || G <= 0 || !Yc || (ldc & 15) || ldc < G || !W || (ldw & 3) || ldw < H1 || !Z ||
-        (ldz & 3) || ldz < H1 || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(Z) & 15) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 15) || !workspace)
-        return DCAHIP_EINVAL;
-    if (workspace_bytes < dcahip_enc0_fwd_sparse_workspace_bytes(H1)) return DCAHIP_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    // workspace: [kC0Blocks][H1] doubles | ticket (zero before the first call, left at zero by every call) | b_eff [H1]
-    double* part = static_cast<double*>(workspace);
-    unsigned* ticket = reinterpret_cast<unsigned*>(part + (long)kC0Blocks * H1);
-    float* beff = reinterpret_cast<float*>(reinterpret_cast<char*>(ticket) + 256);
-    C0Args c{W, ldw, bias, mean, stdv, G, H1, part, ticket, beff};
-    if (mean) {
-        hipLaunchKernelGGL(enc0_c0_kernel, dim3(kC0Blocks), dim3(256), 0, s, c);
-        int rc = (int)hipGetLastError();
-        if (rc) return rc;
-    }
-    FwArgs f;
-    f.c = Compact{Yc, ldc, ovf_ptr, ovf_col, ovf_val};
-    f.fac = fac; f.do_log = do_log; f.stdv = stdv; f.perm = perm; f.cursor = cursor; f.row_base = row_base;
-    f.B = B; f.G = G; f.W = W; f.ldw = ldw; f.beff = mean ? beff : bias; f.Z = Z; f.ldz = ldz;
-    const dim3 grid((unsigned)((B + 3) / 4));
-    switch (H1) {
-        case 16: hipLaunchKernelGGL(enc0_fwd_kernel<16>, grid, dim3(256), 0, s, f); break;
-        case 32: hipLaunchKernelGGL(enc0_fwd_kernel<32>, grid, dim3(256), 0, s, f); break;
-        case 64: hipLaunchKernelGGL(enc0_fwd_kernel<64>, grid, dim3(256), 0, s, f); break;
-        case 128: hipLaunchKernelGGL(enc0_fwd_kernel<128>, grid, dim3(256), 0, s, f); break;
-        default: hipLaunchKernelGGL(enc0_fwd_kernel<256>, grid, dim3(256), 0, s, f); break;
-    }
-    return (int)hipGetLastError();
-}
-
-#endif  // DCA_EXP_ENC0_SPARSE_FWD
-
-// 32-row tiles per wave of the matrix-pipe forward: 1 = eight waves (the product).  2 = four waves of 64 rows: built,
-// bit-identical, measured SLOWER (0.080 vs 0.067 ms) -- an experiment build (-DDCA_EXP_FWD_FORM2), not a switch.
-#ifdef DCA_EXP_FWD_FORM2
-constexpr int kFlRT = 2;
-#else
-constexpr int kFlRT = 1;
-#endif
-
 // workspace: WP | C0P | P
 extern "C" long dcahip_enc0_fwd_lut_workspace_bytes(int B, int G, int H1) {
     if (!fl_width_ok(H1) || B <= 0 || G <= 0) return 0;
@@ -1728,10 +1312,10 @@ extern "C" int dcahip_enc0_fwd_lut(const unsigned char* Yc, long ldc, const int*
     const dim3 grid((unsigned)fl_row_groups(B), (unsigned)nsk);
     if (H1 == 32) {
         hipLaunchKernelGGL(enc0_wsplit_kernel<32>, dim3((unsigned)n_ms, 1), dim3(256), 0, s, W, ldw, mean, stdv, G, WP, C0P);
-        hipLaunchKernelGGL((enc0_fwd_lut_kernel<32, kFlRT>), grid, dim3(512 / kFlRT), 0, s, f);
+        hipLaunchKernelGGL(enc0_fwd_lut_kernel<32>, grid, dim3(512), 0, s, f);
     } else {
         hipLaunchKernelGGL(enc0_wsplit_kernel<64>, dim3((unsigned)n_ms, 2), dim3(256), 0, s, W, ldw, mean, stdv, G, WP, C0P);
-        hipLaunchKernelGGL((enc0_fwd_lut_kernel<64, kFlRT>), grid, dim3(512 / kFlRT), 0, s, f);
+        hipLaunchKernelGGL(enc0_fwd_lut_kernel<64>, grid, dim3(512), 0, s, f);
     }
     int rc = (int)hipGetLastError();
     if (rc) return rc;

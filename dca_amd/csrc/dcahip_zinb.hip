@@ -68,11 +68,6 @@ __device__ __forceinline__ void store_planes4_h2(unsigned short* base, long pstr
     *reinterpret_cast<u32x2*>(base) = u32x2{a0, b0};
     *reinterpret_cast<u32x2*>(base + pstride) = u32x2{a1, b1};
 }
-__device__ __forceinline__ void store_planes1(unsigned short* base, long pstride, float v) {
-    unsigned a0, a1, a2;
-    split_pair(v, 0.f, a0, a1, a2);
-    base[0] = (unsigned short)a0; base[pstride] = (unsigned short)a1; base[2 * pstride] = (unsigned short)a2;
-}
 
 __device__ __forceinline__ double block_reduce_sum(double v) {
     __shared__ double red[4];
@@ -171,10 +166,9 @@ __global__ __launch_bounds__(256) void zinb_nll_kernel(NllArgs a) {
 //     16-byte stores of the same wave: `s_waitcnt vmcnt(0)` in between orders them).
 // Before: both branches for every wave-row (~370 VALU per element) at 3.0-3.2 TB/s = 0.38-0.40 of the HBM peak.
 constexpr int kNzCap = 64 + 256;      // entries per wave: < 64 left over + up to 4 x 64 pushed per row
-struct NzEntry { float am, ad, ap, y, sf; unsigned dof, dof2; };     // dof2: the fp32 dispersion plane beside bf16 planes
+struct NzEntry { float am, ad, ap, y, sf; unsigned dof, pad; };      // pad (a copy of dof): 32-byte entries
 
-// PL: the gradient planes leave as pre-split bf16 pieces (a.pl; the per-gene dispersion plane of CONST_DISP stays fp32)
-template <bool HAS_PI, bool CONST_DISP, bool GRAD, bool PL = false>
+template <bool HAS_PI, bool CONST_DISP, bool GRAD>
 __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {     // 4 waves per SIMD: 128 registers
     constexpr int V = 4;
     __shared__ NzEntry queue[4][kNzCap];
@@ -203,15 +197,9 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
             lsp += act ? nll : 0.f;
             if (GRAD && act) {
                 __builtin_amdgcn_s_waitcnt(0x0f70);                       // vmcnt(0): the dense stores of these addresses are done
-                if (PL) {
-                    store_planes1(a.pl[0] + e.dof, a.pstride, o1 * a.inv_n);
-                    if (CONST_DISP) a.d_disp[e.dof2] = o2 * a.inv_n; else store_planes1(a.pl[1] + e.dof, a.pstride, o2 * a.inv_n);
-                    if (HAS_PI) store_planes1(a.pl[2] + e.dof, a.pstride, o3 * a.inv_n);
-                } else {
-                    a.d_mean[e.dof] = o1 * a.inv_n;
-                    a.d_disp[e.dof] = o2 * a.inv_n;
-                    if (HAS_PI) a.d_pi[e.dof] = o3 * a.inv_n;
-                }
+                a.d_mean[e.dof] = o1 * a.inv_n;
+                a.d_disp[e.dof] = o2 * a.inv_n;
+                if (HAS_PI) a.d_pi[e.dof] = o3 * a.inv_n;
             }
             qn -= c;
         }
@@ -231,8 +219,7 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
             srow_n = a.perm ? (long)a.perm[cur + rown] : (long)(cur + rown);
             const float sf = a.sf[srow];
             const long ao = (long)row * a.lda + g;
-            const long dof2 = (long)row * a.ldd + g;
-            const long dof = PL ? (long)row * a.ldp + g : dof2;
+            const long dof = (long)row * a.ldd + g;
             float vm[V] = {0.f, 0.f, 0.f, 0.f}, vp[V] = {0.f, 0.f, 0.f, 0.f}, vy[V] = {0.f, 0.f, 0.f, 0.f};
             if (qv) {
                 ldv<V>(a.a_mean + ao, vm);
@@ -255,22 +242,16 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
                 om[j] = gmv * sc; od[j] = gdv * sc; op[j] = gpv * sc;
             }
             if (GRAD && qv) {
-                if (PL) {
-                    store_planes4(a.pl[0] + dof, a.pstride, om);
-                    if (CONST_DISP) stv<V>(a.d_disp + dof2, od); else store_planes4(a.pl[1] + dof, a.pstride, od);
-                    if (HAS_PI) store_planes4(a.pl[2] + dof, a.pstride, op);
-                } else {
-                    stv<V>(a.d_mean + dof, om);
-                    stv<V>(a.d_disp + dof, od);
-                    if (HAS_PI) stv<V>(a.d_pi + dof, op);
-                }
+                stv<V>(a.d_mean + dof, om);
+                stv<V>(a.d_disp + dof, od);
+                if (HAS_PI) stv<V>(a.d_pi + dof, op);
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const unsigned long long m = __ballot(nz[j]);
                 if (m) {
                     const int slot = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (nz[j]) Q[slot] = NzEntry{vm[j], vd[j], vp[j], vy[j], sf, (unsigned)(dof + j), (unsigned)(dof2 + j)};
+                    if (nz[j]) Q[slot] = NzEntry{vm[j], vd[j], vp[j], vy[j], sf, (unsigned)(dof + j), (unsigned)(dof + j)};
                     qn += __popcll(m);
                 }
             }
@@ -291,13 +272,9 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
 // wave-uniform ballot masks) before the one dense store of the two rows.  Against the patching form: no 2- / 4-byte
 // scattered stores behind the dense ones (measured at configs[4]'s decoder, 2048 x 25 000, bf16 pieces out: 0.445 ms, of
 // which 0.145 ms were the patches -- partial-line writes -- profiles/r03_zinb_rows_notes.txt).
-#ifdef DCA_ZINB_ROWS
-constexpr int kRowsPerIter = DCA_ZINB_ROWS;
-#else
 constexpr int kRowsPerIter = 2;
-#endif
 template <bool HAS_PI, bool CONST_DISP, int PL>          // PL: 0 fp32 gradient planes, 1 three bf16 pieces, 2 two fp16 pieces of g 2^kD
-__global__ __launch_bounds__(256, kRowsPerIter <= 2 ? 4 : 3) void zinb_nll_rows_kernel(NllArgs a) {
+__global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
     const float psc = PL == 2 ? a.pscale : a.inv_n;        // scale of the head planes; a per-gene dispersion's plane: inv_n
     constexpr int V = 4, R = kRowsPerIter;
     __shared__ float4 queue[4][R * 256];                   // 8 KB per wave: every element of both rows may be non-zero
@@ -524,19 +501,9 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 template <bool HAS_PI, bool CONST_DISP, bool GRAD>
 int launch_nll(const NllArgs& a, bool vec, dim3 grid, hipStream_t s) {
     // the compacted kernel addresses gradient elements with 32 bits
-#ifdef DCA_ZINB_PLAIN          // A/B builds only: K-ZINB without the non-zero compaction
-    constexpr bool plain = true;
-#else
-    constexpr bool plain = false;
-#endif
-#ifdef DCA_ZINB_PATCH          // A/B builds only: the non-zero elements patched behind the dense stores (round-2 form)
-    constexpr bool patching = true;
-#else
-    constexpr bool patching = false;
-#endif
     const bool fits = !GRAD || (long)a.B * a.ldd < (1L << 32);
-    if (vec && fits && !plain && GRAD && !patching) hipLaunchKernelGGL((zinb_nll_rows_kernel<HAS_PI, CONST_DISP, 0>), grid, dim3(256), 0, s, a);
-    else if (vec && fits && !plain) hipLaunchKernelGGL((zinb_nll_compact_kernel<HAS_PI, CONST_DISP, GRAD>), grid, dim3(256), 0, s, a);
+    if (vec && fits && GRAD) hipLaunchKernelGGL((zinb_nll_rows_kernel<HAS_PI, CONST_DISP, 0>), grid, dim3(256), 0, s, a);
+    else if (vec && fits) hipLaunchKernelGGL((zinb_nll_compact_kernel<HAS_PI, CONST_DISP, GRAD>), grid, dim3(256), 0, s, a);
     else if (vec) hipLaunchKernelGGL((zinb_nll_kernel<HAS_PI, CONST_DISP, GRAD, 4>), grid, dim3(256), 0, s, a);
     else     hipLaunchKernelGGL((zinb_nll_kernel<HAS_PI, CONST_DISP, GRAD, 1>), grid, dim3(256), 0, s, a);
     return (int)hipGetLastError();
@@ -636,16 +603,10 @@ static int zinb_nll_planes_impl(int h2, float pscale, const float* a_mean, const
         else hipLaunchKernelGGL((zinb_nll_rows_kernel<false, false, 2>), grid, dim3(256), 0, s, a);
         return (int)hipGetLastError();
     }
-#ifdef DCA_ZINB_PATCH
-#define DCA_ZK(P, C) zinb_nll_compact_kernel<P, C, true, true>
-#else
-#define DCA_ZK(P, C) zinb_nll_rows_kernel<P, C, 1>
-#endif
-    if (has_pi && cdisp) hipLaunchKernelGGL((DCA_ZK(true, true)), grid, dim3(256), 0, s, a);
-    else if (has_pi) hipLaunchKernelGGL((DCA_ZK(true, false)), grid, dim3(256), 0, s, a);
-    else if (cdisp) hipLaunchKernelGGL((DCA_ZK(false, true)), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((DCA_ZK(false, false)), grid, dim3(256), 0, s, a);
-#undef DCA_ZK
+    if (has_pi && cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, true, 1>), grid, dim3(256), 0, s, a);
+    else if (has_pi) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, false, 1>), grid, dim3(256), 0, s, a);
+    else if (cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<false, true, 1>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((zinb_nll_rows_kernel<false, false, 1>), grid, dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -197,19 +197,6 @@ _SIGNATURES = {
                                               _c.c_long, _i32p, _f32p, _c.c_int, _vp]),
 }
 
-# Entry points that exist only in EXPERIMENT builds of the sources (-DDCA_EXP_DW_SMALL, -DDCA_EXP_ENC0_SPARSE_FWD: kernels
-# that were measured and lost, include/dcahip.h conventions): bound when the loaded library has them (tools/ point build.LIB
-# at such a build), absent from the product library (tests/test_cabi.py).
-_EXPERIMENT_SIGNATURES = {
-    'dcahip_enc0_dw_small_max_rows': (_c.c_int, []),
-    'dcahip_enc0_dw_small': (_c.c_int, [_vp, _c.c_long, _i32p, _i32p, _f32p, _f32p, _c.c_int, _f32p, _f32p, _i32p, _i64p,
-                                        _c.c_long, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_long, _vp]),
-    'dcahip_enc0_fwd_sparse_workspace_bytes': (_c.c_long, [_c.c_int]),
-    'dcahip_enc0_fwd_sparse': (_c.c_int, [_vp, _c.c_long, _i32p, _i32p, _f32p, _f32p, _c.c_int, _f32p, _f32p, _i32p, _i64p,
-                                          _c.c_long, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _c.c_long,
-                                          _vp, _c.c_long, _vp]),
-}
-
 _lib = None
 
 
@@ -238,10 +225,6 @@ def lib():
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(L, name)          # AttributeError => header / library mismatch: loud
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in _EXPERIMENT_SIGNATURES.items():
-        if hasattr(L, name):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
     assert L.dcahip_version() == 1
     _lib = L
     return L
@@ -249,11 +232,6 @@ def lib():
 
 def exported_symbols():
     return sorted(_SIGNATURES)
-
-
-def has(name):
-    """Whether the loaded library exports `name` (experiment entry points: only in -D builds)."""
-    return hasattr(lib(), name)
 
 
 def require_gpu():

@@ -14,7 +14,7 @@
  *     and keeps no global state (no environment variables, no setters: every choice of kernel is a pure function of the
  *     arguments of the call; kernels that were measured and lost -- the pipelined one-wave-per-SIMD K-HEADS, the
  *     non-zero-only first-layer forward, the small-batch byte-store weight gradient, the four-wave matrix-pipe forward --
- *     exist only as -D builds of the sources (DCA_EXP_*), never in the product library);
+ *     were removed from the sources; the version control history keeps them);
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*), re-entrant
  *     across streams and capturable into a hipGraph (no host synchronisation inside);
  *   - return value: 0 on success, otherwise the hipError_t of the failed launch or

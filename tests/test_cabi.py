@@ -30,11 +30,11 @@ def test_library_exports_every_declared_symbol():
     assert L.dcahip_version() == 1
 
 
-def test_product_library_has_no_setters_and_no_experiment_kernels():
+def test_product_library_has_no_setters_and_no_removed_kernels():
     """include/dcahip.h: "keeps no global state ... every choice of kernel is a pure function of the arguments".  The product
     library exports no `*_set_*` switch, and the kernels that were measured and lost (pipelined one-wave-per-SIMD K-HEADS, the
-    non-zero-only first-layer forward, the small-batch byte-store weight gradient, the four-wave matrix-pipe forward) are in
-    experiment builds (-DDCA_EXP_*) only: neither their entry points nor their device code is in libdcahip.so."""
+    non-zero-only first-layer forward, the small-batch byte-store weight gradient, the four-wave matrix-pipe forward) were
+    removed from the sources: neither their entry points nor their device code is in libdcahip.so."""
     import shutil
     import subprocess
     from dca_amd import build
@@ -48,9 +48,28 @@ def test_product_library_has_no_setters_and_no_experiment_kernels():
         assert gone not in exported
     assert set(exported) == set(_declared()), set(exported) ^ set(_declared())
     blob = open(lib_path, 'rb').read()
-    for kernel in (b'heads_fused_p4_kernel', b'heads_fused_x3_kernel', b'enc0_dw_small_kernel', b'enc0_fwd_kernel'):
+    for kernel in (b'heads_fused_p4_kernel', b'heads_fused_x3_kernel', b'enc0_dw_small_kernel', b'enc0_fwd_kernel',
+                   b'enc0_c0_kernel'):
         assert kernel not in blob, kernel
-    assert b'enc0_fwd_lut_kernelILi64ELi2E' not in blob and b'enc0_fwd_lut_kernelILi64ELi1E' in blob
+    # exactly one 64-unit matrix-pipe forward (no second shape of it)
+    fwd64 = set(re.findall(rb'enc0_fwd_lut_kernelILi64E\w*', blob))
+    assert fwd64 == {b'enc0_fwd_lut_kernelILi64EEEvNS_6FlArgsE'}, fwd64
+
+
+def test_kernel_sources_have_no_build_switches():
+    """A kernel that lost its measurement is deleted, not kept behind a -D switch: the only preprocessor conditional on a
+    project macro in the kernel sources is DCA_EXP_H2_TWO, the negative control of the K-HEADS parity tests."""
+    csrc = os.path.join(ROOT, 'dca_amd', 'csrc')
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith(('.hip', '.hpp', '.cpp', '.h')):
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, name)), 1):
+            m = re.match(r'\s*#\s*(?:el)?if(?:n?def)?\b(.*)', line)     # #if #ifdef #ifndef #elif #elifdef #elifndef
+            if m:
+                for macro in re.findall(r'\bDCA_\w+', m.group(1)):
+                    found.setdefault(macro, []).append('%s:%d' % (name, no))
+    assert set(found) == {'DCA_EXP_H2_TWO'}, found
 
 
 def test_product_path_fails_loudly_without_gpu():

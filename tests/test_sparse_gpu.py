@@ -137,17 +137,6 @@ def test_sparse_first_layer_vs_numpy(ops, B, G, H1, gather, use_fac, do_log, sca
     dcur = torch.tensor([cur if gather else 0], dtype=torch.int64, device='cuda')
     base = 0 if gather else cur
     dW_, db_, ddZ = dev(W), dev(b), dev(dZ)
-    # ---- forward over the non-zero counts only: an EXPERIMENT build of the library (-DDCA_EXP_ENC0_SPARSE_FWD; it lost to the
-    # dense product) -- checked when such a build is the one loaded (run twice: the arrival counter of the bias correction
-    # must be back at zero)
-    if ops.has('dcahip_enc0_fwd_sparse'):
-        Zd = torch.full((B, H1), 7.0, device='cuda')
-        wsf = torch.zeros(ops.enc0_fwd_sparse_workspace_bytes(H1) // 4 + 4, device='cuda')
-        for _ in range(2):
-            ops.enc0_fwd_sparse(cc, dperm, dcur, base, B, G, H1, dW_, H1, db_, Zd, H1, wsf)
-        torch.cuda.synchronize()
-        err = np.abs(Zd.cpu().numpy() - Z_ref)
-        assert (err <= 1e-6 * Z_abs + 1e-30).all(), float((err / Z_abs).max())
     # ---- the product on the matrix pipe (looked-up operand), where the width is taken; twice, bit for bit
     nb = ops.enc0_fwd_lut_workspace_bytes(B, G, H1)
     assert (nb > 0) == (H1 in (32, 64))
@@ -287,55 +276,6 @@ def test_step_with_compact_counts_matches_oracle(ops, ae_type, B):
     loss2, g2, _ = run_single_step(eng2, rows)
     assert abs(loss - loss2) < 2e-6 * abs(loss2)
     assert_grads_close(g, {k: np.asarray(v, np.float64) for k, v in g2.items()}, rtol=5e-4, atol_scale=5e-6, skip=zero_b)
-
-
-@pytest.mark.parametrize('B,G,H1,gather,use_fac,do_log,scale,esc', [
-    (32, 200, 64, True, True, True, True, False), (32, 20000, 64, True, True, True, True, True), (25, 333, 64, True, True, True, True, True),
-    (64, 77, 32, False, True, True, False, True), (1, 50, 64, True, True, True, True, False), (33, 90, 16, True, False, False, False, True),
-    (40, 130, 48, False, True, False, True, False)])
-def test_small_batch_weight_gradient_kernel_vs_numpy(ops, B, G, H1, gather, use_fac, do_log, scale, esc):
-    """(EXPERIMENT build -DDCA_EXP_DW_SMALL only: the kernel measured slower than the GEMM it would replace and is not in the
-    product library.)  dcahip_enc0_dw_small: the first layer's weight + bias gradient of a batch of at most 64 rows (the reference's default
-    32, its 25-row last batch of C3, a single row) over the non-zero counts of the byte store, against fp64 numpy on the
-    dense input: |err| <= 1e-6 of the summed magnitudes, the bias row to 2e-6; a second launch reproduces every bit."""
-    if not ops.has('dcahip_enc0_dw_small'):
-        pytest.skip('experiment entry point: build the library with -DDCA_EXP_DW_SMALL')
-    rng = np.random.RandomState(B + G + H1)
-    n = B + 9
-    Y = counts_with_escapes(n, G, B + G, big=esc)
-    fac = (rng.lognormal(0, 0.4, n)).astype(np.float32).astype(np.float64) if use_fac else None
-    L = dense_input(Y, fac, do_log, None, None)
-    mean = L.mean(0).astype(np.float32).astype(np.float64) if scale else None
-    std = np.maximum(L.std(0, ddof=1), 1e-3).astype(np.float32).astype(np.float64) if scale else None
-    X = dense_input(Y, fac, do_log, mean, std)
-    if gather:
-        perm = rng.permutation(n)[:B + 3].astype(np.int32); cur = 3
-        rows = perm[cur:cur + B]
-    else:
-        perm = None; cur = 4
-        rows = np.arange(cur, cur + B)
-    dZ = rng.normal(0, 1e-3, (B, H1)).astype(np.float32).astype(np.float64)
-    gW_ref = X[rows].T @ dZ
-    Lr = L[rows] / (std[None, :] if scale else 1.0)
-    gW_abs = np.abs(Lr).T @ np.abs(dZ)
-    if scale:
-        gW_abs = gW_abs + np.abs(mean / std)[:, None] * np.abs(dZ).sum(0)[None, :]
-    _, cc = build_compact(ops, Y)
-    cc = cc.with_input(dev(fac) if use_fac else None, do_log, dev(mean) if scale else None, dev(std) if scale else None, ops=ops)
-    dperm = torch.as_tensor(perm).cuda() if perm is not None else None
-    dcur = torch.tensor([cur if gather else 0], dtype=torch.int64, device='cuda')
-    base = 0 if gather else cur
-    assert B <= ops.enc0_dw_small_max_rows
-    gWd = torch.full((G + 1, H1), 7.0, device='cuda')
-    ops.enc0_dw_small(cc, dperm, dcur, base, B, G, H1, dev(dZ), H1, gWd, H1)
-    torch.cuda.synchronize()
-    got = gWd.cpu().numpy()
-    err = np.abs(got[:G] - gW_ref)
-    assert (err <= 1e-6 * gW_abs + 1e-12 * np.abs(dZ).max()).all(), float((err / np.maximum(gW_abs, 1e-30)).max())
-    np.testing.assert_allclose(got[G], dZ.sum(0), rtol=0, atol=2e-6 * np.abs(dZ).sum(0).max())
-    gW2 = torch.zeros_like(gWd)
-    ops.enc0_dw_small(cc, dperm, dcur, base, B, G, H1, dev(dZ), H1, gW2, H1)
-    assert torch.equal(gW2, gWd)
 
 
 @pytest.mark.parametrize('hs,B', [((16, 8, 16), 512), ((48, 16, 48), 600), ((16, 8, 16), 32)])

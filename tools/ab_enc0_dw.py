@@ -4,9 +4,9 @@ import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if os.environ.get('DCA_DW_LIB'):                    # an experiment build (tools/_dbg/libdcahip_<variant>.so) in place of the product
+if os.environ.get('DCA_AMD_LIB'):                   # another build of the library (an A/B of edited sources) in place of the product
     from dca_amd import build as _b
-    _b.LIB = os.path.join(ROOT, 'tools', '_dbg', os.environ['DCA_DW_LIB'])
+    _b.LIB = os.environ['DCA_AMD_LIB']
     _b.needs_build = lambda: False
 from dca_amd import synth, prep, compact
 from dca_amd.ops import HipOps

@@ -4,16 +4,14 @@ import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if os.environ.get('DCA_DW_LIB'):                    # an experiment build (tools/_dbg/libdcahip_<variant>.so) in place of the product
+if os.environ.get('DCA_AMD_LIB'):                   # another build of the library (an A/B of edited sources) in place of the product
     from dca_amd import build as _b
-    _b.LIB = os.path.join(ROOT, 'tools', '_dbg', os.environ['DCA_DW_LIB'])
+    _b.LIB = os.environ['DCA_AMD_LIB']
     _b.needs_build = lambda: False
 from dca_amd import synth, prep, compact
 from dca_amd.ops import HipOps
 
 ops = HipOps()
-# (the four-wave shape of the matrix-pipe forward and the non-zero-only forward are experiment builds: DCA_DW_LIB = a library built
-# with -DDCA_EXP_FWD_FORM2 / -DDCA_EXP_ENC0_SPARSE_FWD, dca_amd.build.build_hip(defines=..., out=...))
 dev = torch.device('cuda')
 G = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
 h = int(sys.argv[2]) if len(sys.argv) > 2 else 64
@@ -29,8 +27,6 @@ W0 = torch.randn(G + 1, h, device=dev) * 0.01
 W0T = torch.zeros(h, Y.shape[1], device=dev)
 cur = torch.zeros(1, dtype=torch.int64, device=dev)
 ws = torch.zeros(256 * 1024 * 1024 // 4, device=dev)
-HAS_SP = ops.has('dcahip_enc0_fwd_sparse')          # the non-zero-only forward: experiment builds only
-wsf = torch.zeros(ops.enc0_fwd_sparse_workspace_bytes(h) // 4 + 4, device=dev) if HAS_SP else None
 ldx = X.shape[1]
 
 
@@ -48,7 +44,7 @@ def timeit(fn, it=30):
 
 for B in ([int(b) for b in os.environ['BENCH_B'].split(',')] if os.environ.get('BENCH_B') else (32, 128, 512, 1024, 2048, 4096, 8192)):
     perm = torch.randperm(n, device=dev, dtype=torch.int32)[:B].contiguous()
-    Z = torch.zeros(B, h, device=dev); Z2 = torch.zeros(B, h, device=dev)
+    Z = torch.zeros(B, h, device=dev)
     dZ = torch.randn(B, h, device=dev) * 1e-3
     gW = torch.zeros(G + 1, h, device=dev); gW2 = torch.zeros(G + 1, h, device=dev)
     wsd = torch.zeros(ops.enc0_dw_sparse_workspace_bytes(B, G, h) // 4 + 4, device=dev)
@@ -59,9 +55,6 @@ for B in ([int(b) for b in os.environ['BENCH_B'].split(',')] if os.environ.get('
     def fwd_nt():
         ops.transpose(W0, h, G, h, W0T, ldx)
         ops.sgemm(0, 1, B, h, G, X, ldx, W0T, ldx, Z, h, bias=W0[G], perm=perm, cursor=cur, ws=ws)
-
-    def fwd_sp():
-        ops.enc0_fwd_sparse(cc, perm, cur, 0, B, G, h, W0, h, W0[G], Z2, h, wsf)
 
     nbl = ops.enc0_fwd_lut_workspace_bytes(B, G, h)
     wsl = torch.zeros(max(nbl, 16) // 4 + 4, device=dev)
@@ -77,11 +70,11 @@ for B in ([int(b) for b in os.environ['BENCH_B'].split(',')] if os.environ.get('
         ops.enc0_dw_sparse(cc, perm, cur, 0, B, G, h, dZ, h, gW2, h, wsd)
 
     t = {'fwd dense NN': timeit(fwd_nn), 'fwd dense NT+transpose': timeit(fwd_nt) if B >= 256 else float('nan'),
-         'fwd sparse': timeit(fwd_sp) if HAS_SP else float('nan'), 'fwd lut': timeit(fwd_lut) if nbl else float('nan'), 'dW dense TN': timeit(dw_tn), 'dW sparse': timeit(dw_sp)}
-    fwd_nn(); (fwd_sp() if HAS_SP else fwd_lut()); dw_tn(); dw_sp(); torch.cuda.synchronize()
-    ez = (Z - Z2).abs().max().item() / Z.abs().max().item() if HAS_SP else 0.0
+         'fwd lut': timeit(fwd_lut) if nbl else float('nan'), 'dW dense TN': timeit(dw_tn), 'dW sparse': timeit(dw_sp)}
+    fwd_nn(); dw_tn(); dw_sp(); torch.cuda.synchronize()
+    ez = 0.0
     if nbl:
         fwd_lut(); torch.cuda.synchronize()
-        ez = max(ez, (Z - Z3).abs().max().item() / Z.abs().max().item())
+        ez = (Z - Z3).abs().max().item() / Z.abs().max().item()
     eg = (gW - gW2).abs().max().item() / gW.abs().max().item()
     print('B=%5d  ' % B + '  '.join('%s %.4f ms' % kv for kv in t.items()) + '   max diff fwd %.1e dW %.1e' % (ez, eg), flush=True)

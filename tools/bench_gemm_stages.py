@@ -1,4 +1,4 @@
-"""enc0 GEMMs (C3, B = 4096) over split_k; run with DCA_GEMM_STAGES=1 / 2."""
+"""enc0 GEMMs (C3, B = 4096) through dcahip_sgemm over split_k.  DCA_AMD_LIB=<path> times another build of the library."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +29,6 @@ def timeit(fn, it=30):
     return s.elapsed_time(e) / it
 
 
-print('big', os.environ.get('DCA_GEMM_BIG', '0'))
 print('fwd ', ' '.join('S=%d: %.3f' % (sk, timeit(lambda: ops.sgemm(0, 0, B, h, G, X, G, W0, h, Z, h, bias=W0[G], perm=perm, cursor=cur, split_k=sk, ws=ws)))
                        for sk in (0, 0, 16, 24, 32, 48, 64)))
 print('dW  ', ' '.join('S=%d: %.3f' % (sk, timeit(lambda: ops.sgemm(1, 0, G, h, B, X, G, dZ, h, gW, h, perm=perm, cursor=cur, colsum_row=True, split_k=sk, ws=ws)))
