@@ -17,13 +17,18 @@
 // matrix instructions and a fifth of the vector instructions per split (one v_cvt_pk_f16_f32 + two v_fma_mix_f32 + one
 // v_cvt_pk_f16_f32 per pair of values).  The powers of two:
 //   H  per 32-row tile, 2^eH[t] (heads_split_h_kernel)            W  per gene tile (work item), 2^eW (weight prologue)
-//   D  = g 2^kD[t] with g the UNSCALED gradient d nll / d pre-activation (no 1 / n factor) and kD[t] = kD0 - (eH[t] - eHmin):
-//      the weight-gradient accumulators of a wave then carry ONE scale 2^(eHmin + kD0) over all its row tiles.  g is O(1)
-//      on count data (|g| <= max(theta, ~2 y) by the formulas, 0.16 in the median): kD0 = 8 + d_exp keeps |g| <= 117 inside
-//      the fp16 range and every |g| >= 5e-4 at 22 bits.  The likelihood pass keeps the tile's largest |D|; a tile that meets a
-//      larger value (a count in the hundreds, a dispersion at its floor) takes a slow path BEFORE anything is split: its staged
-//      D and the wave's accumulators are scaled down by what the maximum needs, and back afterwards (exact: powers of two).
-//      Nothing saturates, nothing is clamped.
+//   D  = g 2^kD[t] with g the UNSCALED gradient d nll / d pre-activation (no 1 / n factor).  g is O(1) on count data
+//      (|g| <= max(theta, ~2 y) by the formulas, 0.16 in the median): kD0 = 8 + d_exp keeps |g| <= 117 inside the fp16 range
+//      and every |g| >= 5e-4 at 22 bits.  D's scale does NOT follow H's: kD[t] lies in [kD0 - kDSlack, kD0] whatever the
+//      spread of eH over a wave's row tiles (dH = D W^T does not contain H).  The weight-gradient accumulators of a wave carry
+//      2^accE; a tile whose product H^T D has another scale moves them first (exact: a power of two).  kD[t] = accE - eH[t]
+//      where that lies in the window (row tiles of like magnitude: no move), kD0 otherwise.  An all-zero row tile (eH[t] =
+//      kEHZero) takes kD0 and moves nothing: its products are zeros.  The likelihood pass keeps the tile's largest |D|; a tile
+//      that meets a larger value (a count in the hundreds, a dispersion at its floor) takes a slow path BEFORE anything is
+//      split: F and Z are repeated at the scale kDe < kD[t] its maximum needs.  Nothing saturates, nothing is clamped -- but the
+//      scale is the tile's, so every other element of the 32 x 32 tile is carried at 2^kDe: the repeat path meets
+//      |err| <= (fp32 dot product) + 2^-(kDe + 25) sum|b| (the fp16 denormal floor of D's second piece; b = the other operand),
+//      not the product bound alone (tests/test_heads_fused_gpu.py::product_tol, oracle/x3_np.py::heads_wave).
 // Every gradient leaves the kernel in g units; the 1 / n factor (inv_n) is applied ONCE per output element at the end.
 //
 // Work decomposition (gene-stationary):
@@ -90,6 +95,8 @@ constexpr int kHTile = 2 * 32 * 64;     // fp16 elements of one row tile of the 
 constexpr int kTop = 13;                // a scaled block's largest magnitude lies in [2^kTop, 2^(kTop + 1))
 constexpr int kDExp0 = 8;               // D = g 2^kDExp0: |g| <= 117 (kDLim / 256) stays inside the fp16 range, |g| >= 5e-4 keeps 22 bits
 constexpr float kDLim = 30000.f;        // a scaled gradient beyond this sends its tile through the slow path (rescaled as a whole)
+constexpr int kDSlack = 2;              // D's scale may sit this many bits below kD0 to spare the dW accumulators a move
+constexpr int kEHZero = 64;             // eH[t] of an all-zero row tile (outside block_exp's [-60, 60]): no scale of its own
 
 #define MFMAH(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0)
 
@@ -199,7 +206,7 @@ __global__ __launch_bounds__(256) void heads_split_h_kernel(const float* H, long
     if ((tid & 63) == 0) wm[tid >> 6] = m;
     __syncthreads();
     const int e = block_exp(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-    if (tid == 0) eH[t] = e;
+    if (tid == 0) eH[t] = (fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])) > 0.f) ? e : kEHZero;
     const float sc = pow2i(e);
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[j] *= sc;
@@ -266,11 +273,11 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
     const int ngb = p.nitems / p.S;
     const int full = ngb / p.npart, rem = ngb - full * p.npart;          // the last round is partial
     const int nrounds = full + ((rem > 0 && ((full & 1) ? p.npart - 1 - wq : wq) < rem) ? 1 : 0);
-    // the scale of this wave's weight-gradient accumulators: the smallest exponent among ITS row tiles (the same tiles in
-    // every work item) + kD0
+    // the starting scale of this wave's weight-gradient accumulators: the smallest exponent among ITS non-zero row tiles (the
+    // same tiles in every work item) + kD0 -- tiles within kDSlack of it never move the accumulators
     const int kD0 = kDExp0 + p.d_exp;
     int eHmin = 1 << 20;
-    for (int t = s_wg * WR + r; t < p.NT; t += p.S * WR) { const int e = p.eH[t]; eHmin = e < eHmin ? e : eHmin; }
+    for (int t = s_wg * WR + r; t < p.NT; t += p.S * WR) { const int e = p.eH[t]; eHmin = (e != kEHZero && e < eHmin) ? e : eHmin; }
     eHmin = __builtin_amdgcn_readfirstlane(eHmin == (1 << 20) ? 0 : eHmin);
 #pragma unroll 1
     for (int j = 0; j < nrounds; ++j) {
@@ -464,6 +471,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             }
         }
         int rb = 0;                                  // which half of Rt holds the current tile's rows
+        int accE = eHmin + kD0;                      // the exponent the dW accumulators carry
         int tile_no = wave >> 2;
         for (; t < p.NT; t += tstep) {
             if ((tile_no++) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
@@ -471,7 +479,10 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             const int tn = t + tstep < p.NT ? t + tstep : t;
             // the tile's scales (wave-uniform): forward products carry 2^(eH[t] + eW), the gradient D = g 2^kDt
             eHt = __builtin_amdgcn_readfirstlane(eHt);
-            const int kDt = kD0 - (eHt - eHmin);
+            const bool hzero = eHt == kEHZero;       // an all-zero row tile: H^T D = 0 at any scale
+            if (hzero) eHt = 0;
+            const int kDa = accE - eHt;
+            const int kDt = (!hzero && kDa <= kD0 && kDa >= kD0 - kDSlack) ? kDa : kD0;
             const float fscale = pow2i(eHt + eW), funscale = pow2i(-(eHt + eW));
             // F and Z run until the tile's gradients fit the fp16 range at the scale 2^kDe: once, but for a tile that holds a
             // count in the hundreds or a dispersion at its floor (wave-uniform, rare, exact: see Z)
@@ -698,15 +709,15 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             dacc += (double)lacc;
             const float sf_n = p.sf[srow_n];
             wave_sync();
-            const int shift = kDt - kDe;
-            if (shift) {                             // the wave's accumulators to the scale of this tile's D
-                const float down = pow2i(-shift);
+            if (!hzero && accE != eHt + kDe) {       // the wave's accumulators to the scale of this tile's H^T D (exact)
+                const int mv = eHt + kDe - accE;
+                accE = eHt + kDe;
 #pragma unroll
                 for (int h = 0; h < NH; ++h)
 #pragma unroll
                     for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) dW[h][ib][e] *= down;
+                        for (int e = 0; e < 16; ++e) dW[h][ib][e] = __builtin_amdgcn_ldexpf(dW[h][ib][e], mv);
             }
 
             // ---- dH[row, i] = sum_genes D[row, gene] W[i, gene]: A = the D pieces read transposed (row position l31, 8 genes
@@ -775,7 +786,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             __builtin_amdgcn_sched_barrier(0);
             // ---- dW[i, gene] += sum_rows H[row, i] D[row, gene]: B = the lane's own D column as stored (row positions in
             // the order of the MFMA row map = the order of the transposed H image), A = H^T pieces.  The accumulators carry
-            // 2^(eHmin + kD0) = 2^(eH[t] + kDt) in every tile.  The column sums (bias gradients) from the pieces: v_dot2_f32_f16.
+            // 2^accE = 2^(eH[t] + kDe) (an all-zero tile adds zeros).  The column sums (bias gradients) from the pieces: v_dot2_f32_f16.
             float tsum[NH];
 #pragma unroll
             for (int h = 0; h < NH; ++h) tsum[h] = 0.f;
@@ -812,15 +823,6 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                     thsum = fmaf(ts, gun, thsum);
                 }
             }
-            if (shift) {                             // the accumulators back to the wave's scale
-                const float up = pow2i(shift);
-#pragma unroll
-                for (int h = 0; h < NH; ++h)
-#pragma unroll
-                    for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) dW[h][ib][e] *= up;
-            }
             srow_l = srow_n;
             sf_l = sf_n;
             eHt = eHn;
@@ -830,13 +832,12 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         }
         // the wave's weight gradient back to g units x H (exact: a power of two) before the waves are summed
         {
-            const float wun = pow2i(-(eHmin + kD0));
 #pragma unroll
             for (int h = 0; h < NH; ++h)
 #pragma unroll
                 for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) dW[h][ib][e] *= wun;
+                    for (int e = 0; e < 16; ++e) dW[h][ib][e] = __builtin_amdgcn_ldexpf(dW[h][ib][e], -accE);
         }
     }
 

@@ -601,10 +601,11 @@ int dcahip_counts_compact(const float* Y, long ldy, int n, int G, unsigned char*
                           void* stream);
 /* K-HEADS (dcahip_heads_fused_loss) reading the counts from the compact store: yc != NULL selects it (y / ldy are then
  * unused and may be NULL / 0), yc == NULL is dcahip_heads_fused_loss.  4 x fewer count bytes per launch.
- * d_exp (<= 0; 0 for count matrices whose largest count stays below ~8 000, what the other entry points pass): the kernel
- * carries the gradient planes as g 2^(1 + d_exp) in two fp16 pieces, g = the UNSCALED d nll / d pre-activation, |g| <=
- * max(1e4, ~2 y_max).  Values beyond the fp16 range are still exact (their tile is rescaled as a whole: a slow path); a caller
- * that knows its counts reach y_max passes d_exp = -ceil(log2(y_max / 8192)) and keeps every tile on the fast path.
+ * d_exp (in [-24, 0]; 0 is what the other entry points pass): the kernel carries the gradient planes as g 2^(8 + d_exp)
+ * (kDExp0 = 8) in two fp16 pieces, g = the UNSCALED d nll / d pre-activation, |g| <= max(theta, ~2 y): |g| <= 117 fits at
+ * d_exp = 0.  A 32 x 32 tile with a larger value repeats at the exponent its maximum needs (a slow path, exact, but the whole
+ * tile is then carried at that exponent: 2^-(kDe + 25) absolute on every g of it); a caller whose counts reach c throughout
+ * passes d_exp = -ceil(log2(2 c / 117)) (Engine._heads_d_exp) and keeps the tiles on the fast path.
  * ridge must lie in [0, 1e3]. */
 int dcahip_heads_fused_compact(const float* H, long ldh, const float* Wh, long ldw, const float* bh,
                                long plane, const float* theta_w,

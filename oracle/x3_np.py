@@ -76,3 +76,97 @@ def matmul_h2(a, b, products=3, ea=None, eb=None):
     for i, j in terms:
         acc = (acc + (A[i] @ B[j]).astype(np.float32)).astype(np.float32)
     return np.ldexp(acc.astype(np.float64), -(ea + eb))
+
+
+# ---------------------------------------------------------------------------------------- K-HEADS' scale rule, one wave
+K_DEXP0 = 8             # kDExp0: D = g 2^(8 + d_exp)
+K_DLIM = 30000.0        # kDLim: a scaled |D| beyond this repeats the tile at a lower exponent
+K_DSLACK = 2            # kDSlack: D's scale may sit this many bits below kD0 to spare the dW accumulators a move
+
+
+def _h3(a, b):
+    """sum of the three piece products a2 b1 + a1 b2 + a1 b1 (MFMA_H3's order) accumulated in fp32."""
+    acc = np.zeros((a[0].shape[0], b[0].shape[1]), np.float32)
+    for i, j in ((1, 0), (0, 1), (0, 0)):
+        acc = (acc + (a[i] @ b[j]).astype(np.float32)).astype(np.float32)
+    return acc
+
+
+def repeat_exponent(dmax, kd):
+    """The exponent a tile's D ends at from the start kd: the repeat step of heads_fused_h2_kernel (dmax = max |g| of the tile,
+    over the matrix-product planes)."""
+    kde = kd
+    while float(np.float32(dmax) * np.float32(2.0 ** kde)) > K_DLIM and kde >= kd - 200:
+        need = np.frexp(float(np.float32(dmax) * np.float32(2.0 ** kde)))[1] - 1 - 13
+        if need <= 0:
+            break
+        kde -= min(need, 100)
+    return kde
+
+
+def heads_wave(Ht, g, W, d_exp=0, rule='fixed'):
+    """What ONE wave of the persistent K-HEADS kernel computes for its row tiles over every gene tile: dW = H^T g and the rows
+    of dH = g W^T that belong to it, in g units (the unscaled gradient: no 1 / n).
+      Ht [T, 32, K]: the wave's row tiles (H), in the order the wave takes them;  g [NH, 32 T, G]: the unscaled gradient of
+      each matrix-product head;  W [NH, K, G]: the head weights.
+    rule 'fixed': D's scale kD in [kD0 - K_DSLACK, kD0] (kD = accE - eH where that lies in the window, else kD0), the dW
+      accumulators moved to 2^(eH + kDe) where a tile needs it, an all-zero tile moving nothing;
+    rule 'parent': kD = kD0 - (eH - min eH), the accumulators at 2^(min eH + kD0), an all-zero tile counted with eH = 0.
+    Returns eH [T], kD and kDe [T, gene tiles] (kDe < kD: the tile took the repeat path), dW [NH, K, G], dH [32 T, K]."""
+    Ht = np.asarray(Ht, np.float32); g = np.asarray(g, np.float32); W = np.asarray(W, np.float32)
+    T, NH, K, G = Ht.shape[0], g.shape[0], W.shape[1], W.shape[2]
+    ntg = (G + 31) // 32
+    kd0 = K_DEXP0 + d_exp
+    zero = [not np.any(Ht[t]) for t in range(T)]
+    eH = [block_exp(Ht[t]) for t in range(T)]
+    nz = [e for e, z in zip(eH, zero) if not z] if rule == 'fixed' else eH
+    ehmin = min(nz) if nz else 0
+    Hp = [split2(Ht[t].T.copy(), eH[t]) for t in range(T)]
+    kD = np.zeros((T, ntg), int); kDe = np.zeros((T, ntg), int)
+    dW = np.zeros((NH, K, G)); dH = np.zeros((32 * T, K))
+    for j in range(ntg):
+        gs = slice(32 * j, min(G, 32 * j + 32))
+        eW = block_exp(W[:, :, gs])
+        Wp = [split2(W[h][:, gs].T.copy(), eW) for h in range(NH)]          # [genes, K]: the B operand of dH
+        acc = np.zeros((NH, K, gs.stop - gs.start), np.float32)
+        accE = ehmin + kd0
+        for t in range(T):
+            gt = g[:, 32 * t:32 * t + 32, gs]
+            if rule == 'fixed':
+                kda = accE - eH[t]
+                kdt = kda if (not zero[t] and kd0 - K_DSLACK <= kda <= kd0) else kd0
+            else:
+                kdt = kd0 - (eH[t] - ehmin)
+            kde = repeat_exponent(np.abs(gt).max(), kdt)
+            kD[t, j], kDe[t, j] = kdt, kde
+            Dp = [split2(gt[h], kde) for h in range(NH)]
+            dH[32 * t:32 * t + 32] += np.ldexp(sum(_h3(Dp[h], Wp[h]).astype(np.float64) for h in range(NH)), -(kde + eW))
+            if rule == 'fixed':
+                if not zero[t] and accE != eH[t] + kde:
+                    acc = np.ldexp(acc, eH[t] + kde - accE).astype(np.float32)
+                    accE = eH[t] + kde
+            elif kde != kdt:
+                acc = np.ldexp(acc, kde - kdt).astype(np.float32)
+            for h in range(NH):
+                acc[h] = (acc[h] + _h3(Hp[t], Dp[h])).astype(np.float32)
+            if rule == 'parent' and kde != kdt:
+                acc = np.ldexp(acc, kdt - kde).astype(np.float32)
+        dW[:, :, gs] = np.ldexp(acc.astype(np.float64), -accE)
+    return dict(eH=np.array(eH), kD=kD, kDe=kDe, dW=dW, dH=dH)
+
+
+def repeat_floor(kDe, H, W):
+    """The absolute term of the repeat path's bound, in g units: D's second fp16 piece rounds to 2^-25 at D's scale 2^kDe,
+    so an element of a product that sums over tiles carried at 2^kDe gains at most 2^-(kDe + 25) sum |b| from them beyond the
+    fp32 dot-product term (b: the other operand).  kDe [row tiles, gene tiles]; H [32 T, K]; W [NH, K, G].
+    Returns (dW floor [K, G] -- the same for every head, dH floor [32 T, K])."""
+    T, ntg = kDe.shape
+    G = W.shape[2]
+    f = np.ldexp(1.0, -(np.asarray(kDe) + 25))                                        # [T, ntg]
+    Ha = np.abs(np.asarray(H, np.float64)).reshape(T, 32, -1).sum(1)                  # [T, K]: sum over a tile's rows
+    col = np.minimum(np.arange(G) // 32, ntg - 1)
+    fw = Ha.T @ f                                                                     # [K, ntg]
+    Wa = np.abs(np.asarray(W, np.float64)).sum(0)                                     # [K, G] over heads
+    Wt = np.stack([Wa[:, 32 * j:32 * j + 32].sum(1) for j in range(ntg)], 1)         # [K, ntg]
+    fh = f @ Wt.T                                                                     # [T, K]
+    return fw[:, col], np.repeat(fh, 32, axis=0)

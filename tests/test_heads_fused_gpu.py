@@ -54,17 +54,22 @@ def reference(Hm, W, b, tw, y, sf, flags, ridge, n_total, threads=1):
     # sum |a b| of the two backward products: the scale their fp32-dot-product accuracy is stated against
     mag = {'gW_' + h: np.abs(Hm).T @ np.abs(D[h]) for h in heads}
     mag['dH'] = sum(np.abs(D[h]) @ np.abs(W[h]).T for h in heads)
-    return heads, ls / n_total, gW, gb, dH, (dd if cdisp else None), mag
+    return heads, ls / n_total, gW, gb, dH, (dd if cdisp else None), mag, D
 
 
 def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=False, tile_order=None, counts=None,
-             threads=1):
+             threads=1, d_exp=0, hscale=None, compact=False):
+    """d_exp: the kernel's starting gradient exponent (dcahip_heads_fused_compact); hscale: a factor per 32-row tile of H;
+    compact: the counts from the byte store (dca_amd.compact, escapes >= 255 through the overflow list).  out['_ref'] keeps
+    what the scale-rule checks of tests/test_heads_edges_gpu.py need: H, the gradient planes of the products, the weights."""
     has_pi, cdisp = bool(flags & 1), bool(flags & 2)
     rng = np.random.RandomState(seed)
     f = lambda a: a.astype(np.float32).astype(np.float64)
     heads = ['mean'] + ([] if cdisp else ['disp']) + (['pi'] if has_pi else [])
     nh = len(heads)
     Hm = f(np.maximum(rng.normal(0.3, 1.0, (B, hL)), 0))          # post-ReLU activations
+    if hscale is not None:
+        Hm = f(Hm * np.repeat(np.asarray(hscale, np.float64), 32)[:B, None])
     W = {h: f(rng.normal(0, 0.25, (hL, G))) for h in heads}
     b = {h: f(rng.normal(0, 0.3, G)) for h in heads}
     tw = f(rng.normal(0, 1.5, G))
@@ -74,7 +79,7 @@ def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=Fa
         y[1, 1:4] = [16.0, 16.5, 65535.0]
     sf = f(rng.lognormal(0, 0.3, B))
     n_total = float(B * G)
-    _, lm, gW, gb, dH, dth, mag = reference(Hm, W, b, tw, y, sf, flags, ridge, n_total, threads)
+    _, lm, gW, gb, dH, dth, mag, Dref = reference(Hm, W, b, tw, y, sf, flags, ridge, n_total, threads)
 
     Gp = (G + 3) // 4 * 4
     NH = nh * Gp
@@ -96,6 +101,11 @@ def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=Fa
 
     dWh = dev(Wh)
     dHp, dY, dsf = dev(Hp), dev(Yst), dev(sfst)
+    cc = None
+    if compact:
+        from dca_amd import compact as C
+        cc = C.build(ops, dY, n_store, G)
+        assert cc is not None and (cc.ovf_col is not None) == bool((Yst >= 255).any())
     dperm = torch.as_tensor(perm).cuda() if perm is not None else None
     dcur = torch.tensor([cur], dtype=torch.int64, device='cuda')
     dtw = dev(np.concatenate([tw, np.zeros(Gp - G)]))
@@ -109,7 +119,8 @@ def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=Fa
     n = ops.heads_fused(dHp, ldh, dWh, NH, dWh[hL], Gp, dtw if cdisp else None, dY, Gp, dsf, dperm,
                         dcur, B, hL, G, ridge, 1.0 / n_total, flags, gWd, NH,
                         gth if cdisp else None, dHd, ldh, part, ws,
-                        tile_order=None if tile_order is None else torch.as_tensor(tile_order, dtype=torch.int32).cuda())
+                        tile_order=None if tile_order is None else torch.as_tensor(tile_order, dtype=torch.int32).cuda(),
+                        compact=cc, d_exp=d_exp)
     loss = torch.zeros(1, device='cuda')
     ops.loss_finalize(part, n, 1.0 / n_total, loss)
     torch.cuda.synchronize()
@@ -122,6 +133,7 @@ def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=Fa
             out['pad_' + h] = (gWn[:, k * Gp + G:(k + 1) * Gp], np.zeros((hL + 1, Gp - G)))
     out['dH'] = (dHd.cpu().numpy().astype(np.float64)[:, :hL], dH)
     out['_mag'] = mag
+    out['_ref'] = {'H': Hm, 'D': [Dref[h] for h in heads], 'W': np.stack([W[h] for h in heads]), 'n_total': n_total}
     if cdisp:
         # oracle returns d loss / d theta_w already chained when theta_w is given
         out['g_theta'] = (gth.cpu().numpy().astype(np.float64)[:G], dth)
@@ -140,7 +152,12 @@ def product_tol(key, rows, genes=None):
     Round 6's kernel passes them with three fp16 products; a build with TWO (-DDCA_EXP_H2_TWO: one operand's second piece
     dropped, 2^-11 instead of 2^-22) fails every case of this file and the golden-vector cases that go through the kernel --
     39 of 39 (tools/gpu_heads_narrow_check.sh, profiles/r06n_heads_two_product_rejection.txt) -- which the 2e-4 relative
-    tolerance of check() alone would not notice."""
+    tolerance of check() alone would not notice.
+    The bounds assume D = g 2^kD carried at kD >= 5 (d_exp >= -3, kD within K_DSLACK of 8 + d_exp whatever the spread of
+    the row tiles' magnitudes).  Where a tile takes K-HEADS' repeat path (its largest |g| 2^kD beyond the fp16 range: kDe < kD
+    for the whole 32 x 32 tile), below d_exp = -3, and for gradients that fall under D's fp16 floor beside a large H, the
+    kernel's contract is product_tol sum|ab| + 2^-(kDe + 25) sum|b| (b: the other operand; oracle/x3_np.py::repeat_floor,
+    tests/test_heads_edges_gpu.py)."""
     if key == 'dH':
         # (dH sums over heads x genes: the 2e-7 of the benchmark shape is what 60 000 terms average the element errors to;
         #  a launch over fewer genes keeps the bound of the small cases)
@@ -154,7 +171,7 @@ def check(out, edge=False):
     mag = out.get('_mag', {})
     worst = 0.0
     for k, v in out.items():
-        if k in ('loss', '_mag'):
+        if k in ('loss', '_mag', '_ref'):
             continue
         g, r = v
         if k in mag and not edge:
@@ -221,7 +238,7 @@ def test_heads_fused_no_perm_and_determinism(ops):
     check(a)
     b = run_case(ops, 1, 200, 500, 64, seed=3, use_perm=False)
     for k in a:
-        if k == '_mag':
+        if k in ('_mag', '_ref'):
             continue
         assert np.array_equal(np.asarray(a[k][0]), np.asarray(b[k][0])), k
 
@@ -248,7 +265,7 @@ def test_heads_fused_tile_order_changes_nothing(ops, flags, B, G):
         b = run_case(ops, flags, B, G, 64, seed=11, tile_order=order)
         check(b)
         for k in a:
-            if k == '_mag':
+            if k in ('_mag', '_ref'):
                 continue
             if k == 'loss':
                 assert abs(a[k][0] - b[k][0]) <= 1e-6 * abs(a[k][0])

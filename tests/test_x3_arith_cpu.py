@@ -1,6 +1,7 @@
 """The split-bf16 arithmetic of the matrix-pipe kernels, restated in numpy (oracle/x3_np.py), against fp64: the bound the
 GPU tests hold the kernels to, and why three products instead of six cannot meet it."""
 import numpy as np
+import pytest
 
 from oracle import x3_np as X
 
@@ -130,3 +131,117 @@ def test_fp16_pieces_on_the_operands_of_a_training_step():
     assert err(H, W) <= 5e-7                                                           # F
     assert err(g, W.T.copy(), ea=ed) <= 1e-6                                           # dH
     assert err(H.T.copy(), g, eb=ed) <= 1.5e-6                                         # dW
+
+
+# ---------------------------------------------------------------------------------------- K-HEADS' scale rule (one wave)
+def _wave_problem(T, G, seed, scale=None, counts=None, K=64):
+    """A wave's row tiles and the unscaled ZINB gradient (conditional dispersion) of the oracle on synth_counts."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from conftest import synth_counts
+    from oracle import zinb_np as Z
+    rng = np.random.RandomState(seed)
+    B = 32 * T
+    f = lambda a: a.astype(np.float32).astype(np.float64)
+    H = f(np.maximum(rng.normal(0.3, 1.0, (B, K)), 0))
+    if scale is not None:
+        H = f(H * np.repeat(np.asarray(scale, np.float64), 32)[:, None])
+    W = np.stack([f(rng.normal(0, 0.25, (K, G))) for _ in range(3)])
+    b = [f(rng.normal(0, 0.3, G)) for _ in range(3)]
+    y = synth_counts(B, G, seed) if counts is None else counts
+    sf = f(rng.lognormal(0, 0.3, B))
+    A = [H @ W[h] + b[h] for h in range(3)]
+    n = float(B * G)
+    _, _, dm, dd, dp = Z.zinb_loss_and_grads(A[0], A[1], A[2], y, sf, 0.0, n, None)
+    g = (np.stack([dm, dd, dp]) * n).astype(np.float32)
+    return H, g, W
+
+
+def _wave_errors(H, g, W, rule, d_exp=0):
+    """max |err| / sum|ab| of dW and dH of X.heads_wave against fp64, the model's output, and both absolute errors."""
+    T = H.shape[0] // 32
+    o = X.heads_wave(H.reshape(T, 32, -1), g, W, d_exp, rule)
+    g64 = g.astype(np.float64)
+    rW = np.einsum('rk,hrg->hkg', H, g64); mW = np.einsum('rk,hrg->hkg', np.abs(H), np.abs(g64))
+    rH = np.einsum('hrg,hkg->rk', g64, W); mH = np.einsum('hrg,hkg->rk', np.abs(g64), np.abs(W))
+    eW, eH = np.abs(o['dW'] - rW), np.abs(o['dH'] - rH)
+    return (eW / np.maximum(mW, 1e-300)).max(), (eH / np.maximum(mH, 1e-300)).max(), o, (eW, mW, eH, mH)
+
+
+def _product_tol(key, rows):
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_heads_fused_gpu import product_tol
+    return product_tol(key, rows)
+
+
+# (case, wave's row tiles, H scale per tile, the parent rule fails dW, the parent rule fails dH)
+SPREAD_CASES = [
+    ('normal tiles', 2, None, False, False),
+    ('one all-zero row tile of 2', 2, [0.0, 1.0], True, False),
+    ('one all-zero row tile of 4', 4, [1.0, 0.0, 1.0, 1.0], True, False),
+    ('sibling tile at 2^-12', 2, [1.0, 2.0 ** -12], False, False),
+    ('sibling tile at 2^-20', 2, [1.0, 2.0 ** -20], False, True),
+]
+
+
+@pytest.mark.parametrize('case,T,scale,parent_fails_dw,parent_fails_dh', SPREAD_CASES)
+def test_heads_scale_rule_against_row_scale_spread(case, T, scale, parent_fails_dw, parent_fails_dh):
+    """K-HEADS' scale rule for one wave of the persistent kernel (X.heads_wave: G = 1 000, synth_counts, ZINB with a per-cell
+    dispersion) against fp64.  The round-6 rule kD = kD0 - (eH - min eH) scaled D down by the H-magnitude spread of the wave's
+    tiles: an all-zero tile (eH = 0 against ~11) cost the OTHER tiles' D 11 bits, which dW reads, and a tile 2^-20 below its
+    sibling lost 20 bits of D, which dH (= D W^T, no H in it) reads.  The rule the kernel has now keeps kD within
+    K_DSLACK of kD0 and moves the dW accumulators instead: product_tol on every case."""
+    H, g, W = _wave_problem(T, 1000, 3, scale)
+    rows = 32 * T
+    tw, th = _product_tol('gW_mean', rows), _product_tol('dH', rows)
+    pw, ph, po, _ = _wave_errors(H, g, W, 'parent')
+    fw, fh, fo, _ = _wave_errors(H, g, W, 'fixed')
+    print('%s: parent dW %.2e dH %.2e | fixed dW %.2e dH %.2e (bounds %.1e / %.1e)' % (case, pw, ph, fw, fh, tw, th))
+    assert (pw > tw) == parent_fails_dw and (ph > th) == parent_fails_dh, (case, pw, ph)
+    assert fw <= tw and fh <= th, (case, fw, fh)
+    assert ((fo['kD'] <= X.K_DEXP0) & (fo['kD'] >= X.K_DEXP0 - X.K_DSLACK)).all()
+    if parent_fails_dw or parent_fails_dh:
+        assert po['kD'].min() < X.K_DEXP0 - X.K_DSLACK
+
+
+def test_heads_scale_rule_keeps_the_parent_scales_on_like_tiles():
+    """Row tiles of like magnitude (the scale exponents of a training step's decoder output): the fixed rule takes the
+    scales the round-6 rule took wherever no tile repeats -- the same arithmetic, bit for bit."""
+    H, g, W = _wave_problem(2, 300, 5)
+    g = np.clip(g, -100, 100)                                  # no tile beyond the fp16 range: no repeat
+    po = X.heads_wave(H.reshape(2, 32, -1), g, W, 0, 'parent')
+    fo = X.heads_wave(H.reshape(2, 32, -1), g, W, 0, 'fixed')
+    assert abs(int(po['eH'][0]) - int(po['eH'][1])) <= X.K_DSLACK
+    assert (po['kDe'] == po['kD']).all()
+    assert np.array_equal(po['kD'], fo['kD']) and np.array_equal(po['dW'], fo['dW']) and np.array_equal(po['dH'], fo['dH'])
+
+
+@pytest.mark.parametrize('count,d_exp', [(5000, 0), (65535, 0), (70000, 0), (65535, -3), (70000, -3)])
+def test_heads_repeat_path_bound(count, d_exp):
+    """The repeat path rescales a whole 32 x 32 tile by what its largest gradient needs, so the tile's other genes are carried
+    at 2^kDe < 2^kD: D's second fp16 piece rounds to 2^-25 at that scale.  The bound the GPU tests hold such elements to:
+        |err| <= product_tol sum|ab| + 2^-(kDe + 25) sum|b|           (X.repeat_floor; b = the other operand)
+    -- the model meets it with room (< 0.5 of it), and product_tol alone as well at these shapes: the floor is what the
+    repeat path guarantees, not what it typically loses."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from conftest import synth_counts
+    y = synth_counts(64, 1000, 4)
+    gl = int(np.argsort(y.mean(0))[0])                        # the outlier beside the lowest-expressed gene
+    y[5, gl] = count
+    H, g, W = _wave_problem(2, 1000, 4, counts=y)
+    fw, fh, o, (eW, mW, eH, mH) = _wave_errors(H, g, W, 'fixed', d_exp)
+    assert o['kDe'][0, gl // 32] < o['kD'][0, gl // 32]             # the outlier's tile took the repeat path ...
+    assert (o['kDe'] >= o['kD']).any() and (o['kDe'] < o['kD']).any()   # ... and not every tile did
+    floor_w, floor_h = X.repeat_floor(o['kDe'], H, W)
+    rw = (eW / (_product_tol('gW_mean', 64) * mW + floor_w[None])).max()
+    rh = (eH / (_product_tol('dH', 64) * mH + floor_h)).max()
+    print('count %d d_exp %d: dW %.2e dH %.2e of sum|ab|; against the derived bound %.2f / %.2f' % (count, d_exp, fw, fh, rw, rh))
+    assert rw <= 0.5 and rh <= 0.5, (rw, rh)
+    assert fw <= _product_tol('gW_mean', 64) and fh <= _product_tol('dH', 64), (fw, fh)
+    # the floor is exact arithmetic: a single D element at 2^kDe is within 2^-(kDe + 25) of its g
+    Dt = g[:, 0:32, 32 * (gl // 32):32 * (gl // 32) + 32]
+    h1, h2 = X.split2(Dt, int(o['kDe'][0, gl // 32]))
+    err = np.abs(np.ldexp(h1.astype(np.float64) + h2, -int(o['kDe'][0, gl // 32])) - Dt)
+    assert (err <= np.maximum(2.0 ** -22 * np.abs(Dt), 2.0 ** -(o['kDe'][0, gl // 32] + 25))).all()
