@@ -21,6 +21,10 @@ Tested combinations (tests/, all against the same oracle numbers):
   fused_write = False                       test_api_gpu.py::test_fused_predict_writer_writes_the_files_of_predict_then_write
   dp_peer_exchange = True                   test_dp_gpu.py::test_peer_exchange_two_processes_on_one_gpu (raw exchanges, then a fit == the
                                             library-collective fit, bit for bit)
+  resident = 'counts' | 'dense'             test_counts_resident_gpu.py (counts-resident engine == dense engine without the byte
+                                            store, bit for bit; dca() and predict_write files), test_counts_resident_cpu.py
+                                            (the decision and the engine on the CPU oracle).  'auto' (default) keeps the dense
+                                            form whenever its estimate fits into free device memory
 Engine attributes a test sets directly instead (no knob): use_fused (K-HEADS vs separate kernels:
 test_fused_and_separate_heads_agree_stepwise, test_full_size_step_fused_equals_separate).
 """
@@ -56,6 +60,10 @@ class EngineConfig:
     device_prep: bool = True                # DCA_AMD_DEVICE_PREP
     # the command line's predict + write as one streaming pass (gene x cell blocks formatted while the next one computes)
     fused_write: bool = True                # DCA_AMD_FUSED_WRITE
+    # where K-PREP keeps the raw counts: 'dense' = [n, G] fp32 matrices (X, Y, the byte store), 'counts' = the CSR only, each
+    # step gathering its minibatch (dcahip_csr_gather), 'auto' = dense whenever that fits into free device memory
+    # (prep.choose_residency)
+    resident: str = 'auto'                  # DCA_AMD_RESIDENT
     # ---- measured constants (no environment variable; DESIGN.md holds the measurements)
     graph_steps: int = 8                    # consecutive training steps per hipGraph launch (fit loop and bench)
     sparse_dw_min: int = 512                # batch rows from which the first layer's weight gradient reads the byte store
@@ -65,7 +73,7 @@ class EngineConfig:
 
     _ENV = {'stack': 'DCA_AMD_STACK', 'bwd_chain': 'DCA_AMD_BWD_CHAIN', 'wide_planes': 'DCA_AMD_WIDE_PLANES', 'wide_h2': 'DCA_AMD_WIDE_H2',
             'dp_sharded_opt': 'DCA_AMD_DP_SHARDED_OPT', 'dp_graph': 'DCA_AMD_DP_GRAPH', 'device_prep': 'DCA_AMD_DEVICE_PREP',
-            'fused_write': 'DCA_AMD_FUSED_WRITE', 'dp_peer_exchange': 'DCA_AMD_DP_PEER'}
+            'fused_write': 'DCA_AMD_FUSED_WRITE', 'dp_peer_exchange': 'DCA_AMD_DP_PEER', 'resident': 'DCA_AMD_RESIDENT'}
 
     @classmethod
     def from_env(cls):
@@ -80,6 +88,8 @@ class EngineConfig:
                 setattr(c, f.name, type(getattr(c, f.name))(os.environ[env]))
         if c.stack not in ('steps', 'coop', 'off'):
             raise ValueError('DCA_AMD_STACK must be steps, coop or off (got %r)' % c.stack)
+        if c.resident not in ('auto', 'counts', 'dense'):
+            raise ValueError('DCA_AMD_RESIDENT must be auto, counts or dense (got %r)' % c.resident)
         return c
 
 

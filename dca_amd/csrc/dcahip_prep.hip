@@ -220,6 +220,173 @@ __global__ __launch_bounds__(256) void csr_expand_kernel(const int* __restrict__
     if (bad) atomicAdd(status, bad);
 }
 
+// Resident CSR (counts-resident mode: the counts stay in HBM as CSR, each step builds only its own minibatch).
+// indptr is int64 (absolute offsets into indices / values, whose length nnz may exceed 2^31); rows are canonical.
+// The entries of a storage row that malformed input names outside [0, n) or whose indptr leaves [0, nnz] / decreases are
+// clamped and counted, exactly as in csr_expand_kernel: wrong values at worst, never an access outside the buffers.
+struct GatherArgs {
+    const long* indptr; const int* indices; const float* values; long nnz; int n, G;
+    const int* perm; const long long* cursor; long row0; int B;
+    const float* sf; const float* fac; int do_log; const float* mean; const float* stdv;
+    float* Y; long ldy; float* X; long ldx; float* sf_out; int* status;
+};
+
+// x of one element as prep_col_pass + prep_scale write it.  t0: the row's transform of a +0 count (a function of the row
+// only, computed once per row); the scale applies to the G real columns only (prep_scale leaves the pad columns as
+// prep_col_pass wrote them).
+__device__ inline float gather_x(float y, float t0, float f, const GatherArgs& a, long col) {
+    float t = t0;
+    if (__float_as_uint(y) != 0u) {
+        t = y;
+        if (a.fac) t = __fdiv_rn(t, f);
+        if (a.do_log) t = log1pf(t);
+    }
+    if (a.mean && col < a.G) t = __fdiv_rn(t - a.mean[col], a.stdv[col]);
+    return t;
+}
+
+// CSR gather: one workgroup per destination row r < B (grid-stride), storage row perm[*cursor + r] or row0 + r.  The row is
+// built in LDS segments as in csr_expand_kernel; every element of Y[r, 0 .. ldy) and X[r, 0 .. ldx) is written by one
+// plain store (V-float stores when aligned).
+template <int V>
+__global__ __launch_bounds__(256) void csr_gather_kernel(GatherArgs a) {
+    __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
+    __shared__ int found;
+    const int tid = threadIdx.x;
+    int bad = 0;
+    const long base = a.perm ? (long)*a.cursor : a.row0;
+    const long L = (a.X && a.ldx > a.ldy) ? a.ldx : a.ldy;
+    for (int r = blockIdx.x; r < a.B; r += gridDim.x) {
+        const long row = a.perm ? (long)a.perm[base + r] : base + r;
+        const bool ok = row >= 0 && row < a.n;
+        long s = 0, e = 0;
+        if (ok) { s = a.indptr[row]; e = a.indptr[row + 1]; }
+        const long s0 = s < 0 ? 0 : (s > a.nnz ? a.nnz : s);
+        const long e0 = e < s0 ? s0 : (e > a.nnz ? a.nnz : e);
+        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
+        const float f = (a.fac && ok) ? a.fac[row] : 1.f;
+        float t0 = 0.f;
+        if (a.fac) t0 = __fdiv_rn(t0, f);
+        if (a.do_log) t0 = log1pf(t0);
+        if (tid == 0 && a.sf_out) a.sf_out[r] = (ok && a.sf) ? a.sf[row] : 0.f;
+        long p = s0;
+        float* yrow = a.Y + (long)r * a.ldy;
+        float* xrow = a.X ? a.X + (long)r * a.ldx : nullptr;
+        for (long c0 = 0; c0 < L; c0 += kCsrSeg) {
+            const int len = (int)(L - c0 < kCsrSeg ? L - c0 : kCsrSeg);
+            const long c1 = c0 + kCsrSeg < L ? c0 + kCsrSeg : (1L << 40);
+            if (V == 4) {
+                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
+            }
+            if (tid == 0) found = 0;
+            __syncthreads();
+            int mine = 0;
+            for (long j = p + tid; j < e0; j += 256) {
+                const long c = a.indices[j];
+                if (c >= c1) break;
+                ++mine;
+                if (c < 0 || c >= a.G) { ++bad; continue; }
+                const long k = c - c0;
+                if (k >= 0 && k < len) seg[k] = a.values[j];
+            }
+            if (mine) atomicAdd(&found, mine);
+            __syncthreads();
+            p += found;
+            if (p > e0) p = e0;
+            const int ly = (int)(a.ldy - c0 < len ? (a.ldy - c0 > 0 ? a.ldy - c0 : 0) : len);
+            if (V == 4) {
+                for (int i = tid; i < (ly >> 2); i += 256)
+                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
+            } else {
+                for (int i = tid; i < ly; i += 256) yrow[c0 + i] = seg[i];
+            }
+            if (xrow) {
+                const int lx = (int)(a.ldx - c0 < len ? (a.ldx - c0 > 0 ? a.ldx - c0 : 0) : len);
+                if (V == 4) {
+                    for (int i = tid; i < (lx >> 2); i += 256) {
+                        const float4 y = reinterpret_cast<const float4*>(seg)[i];
+                        const long col = c0 + 4 * i;
+                        float4 x;
+                        x.x = gather_x(y.x, t0, f, a, col);
+                        x.y = gather_x(y.y, t0, f, a, col + 1);
+                        x.z = gather_x(y.z, t0, f, a, col + 2);
+                        x.w = gather_x(y.w, t0, f, a, col + 3);
+                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
+                    }
+                } else {
+                    for (int i = tid; i < lx; i += 256) xrow[c0 + i] = gather_x(seg[i], t0, f, a, c0 + i);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (bad) atomicAdd(a.status, bad);
+}
+
+// Per-gene partials of x and x*x over a resident CSR: one workgroup per row chunk (the chunks of col_pass_kernel), rows in
+// ascending order, so every gene receives its non-zero terms in the order col_pass_kernel adds them; the zeros it also adds
+// are +0.0 in fp64 and change nothing.  Within a row the columns are distinct (canonical rows), so the threads of the
+// workgroup update different genes; the barrier after each row orders the updates of one gene across rows.
+__global__ __launch_bounds__(256) void csr_col_pass_kernel(const long* __restrict__ indptr, const int* __restrict__ indices,
+                                                           const float* __restrict__ values, long nnz, int n, int G, int Gp,
+                                                           int R, const float* fac, int do_log, double* part, int* status) {
+    const int tid = threadIdx.x;
+    const int cr = (n + R - 1) / R;
+    const int r0 = blockIdx.x * cr;
+    const int r1 = min(n, r0 + cr);
+    double* p1 = part + (long)blockIdx.x * 2 * Gp;
+    double* p2 = p1 + Gp;
+    for (int g = tid; g < G; g += 256) { p1[g] = 0.0; p2[g] = 0.0; }
+    __syncthreads();
+    int bad = 0;
+    for (int r = r0; r < r1; ++r) {
+        const long s = indptr[r], e = indptr[r + 1];
+        const long s0 = s < 0 ? 0 : (s > nnz ? nnz : s);
+        const long e0 = e < s0 ? s0 : (e > nnz ? nnz : e);
+        if (tid == 0 && (s0 != s || e0 != e)) ++bad;
+        const float f = fac ? fac[r] : 1.f;
+        for (long j = s0 + tid; j < e0; j += 256) {
+            const long c = indices[j];
+            if (c < 0 || c >= G) { ++bad; continue; }
+            float x = values[j];
+            if (fac) x = __fdiv_rn(x, f);
+            if (do_log) x = log1pf(x);
+            p1[c] += (double)x;
+            p2[c] += (double)__fmul_rn(x, x);
+        }
+        __syncthreads();
+    }
+    if (bad) atomicAdd(status, bad);
+}
+
+// Per-cell totals over a resident CSR: one wave per row, fp64 (exact for counts, as row_sums_kernel).
+__global__ __launch_bounds__(256) void csr_row_sums_kernel(const long* __restrict__ indptr, const int* __restrict__ indices,
+                                                           const float* __restrict__ values, long nnz, int n, int G, float* out,
+                                                           int* status) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * 256) >> 6;
+    int bad = 0;
+    for (int r = wave; r < n; r += nwaves) {
+        const long s = indptr[r], e = indptr[r + 1];
+        const long s0 = s < 0 ? 0 : (s > nnz ? nnz : s);
+        const long e0 = e < s0 ? s0 : (e > nnz ? nnz : e);
+        if (lane == 0 && (s0 != s || e0 != e)) ++bad;
+        double acc = 0.0;
+        for (long j = s0 + lane; j < e0; j += 64) {
+            const long c = indices[j];
+            if (c < 0 || c >= G) { ++bad; continue; }
+            acc += (double)values[j];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if (lane == 0) out[r] = (float)acc;
+    }
+    if (bad) atomicAdd(status, bad);
+}
+
 }  // namespace
 
 extern "C" int dcahip_csr_expand(const int* indptr, const int* indices, const float* values, long nnz, int rows, int G,
@@ -284,5 +451,44 @@ extern "C" int dcahip_prep_scale(float* X, long ldx, int n, int G, const float* 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (vec) hipLaunchKernelGGL(scale_kernel<4>, dim3((int)grid), dim3(256), 0, s, X, ldx, n, G, mean, stdv);
     else hipLaunchKernelGGL(scale_kernel<1>, dim3((int)grid), dim3(256), 0, s, X, ldx, n, G, mean, stdv);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_gather(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                 const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                                 const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
+                                 float* X, long ldx, float* sf_out, int* status, void* stream) {
+    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || ldy < G || !status || !Y || !indptr) return DCAHIP_EINVAL;
+    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
+    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf)) return DCAHIP_EINVAL;
+    if (B == 0) return 0;
+    GatherArgs a{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
+                 Y, ldy, X, X ? ldx : 0, sf_out, status};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = B < 16384 ? B : 16384;
+    const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
+    if (vec) hipLaunchKernelGGL(csr_gather_kernel<4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(csr_gather_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_col_pass(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                   const float* fac, int do_log, double* col_part, int* status, void* stream) {
+    if (!indptr || !col_part || !status || n <= 0 || G <= 0 || nnz < 0 || (nnz > 0 && (!indices || !values)))
+        return DCAHIP_EINVAL;
+    const int R = prep_chunks(n);
+    hipLaunchKernelGGL(csr_col_pass_kernel, dim3(R), dim3(256), 0, static_cast<hipStream_t>(stream), indptr, indices, values,
+                       nnz, n, G, (G + 3) & ~3, R, fac, do_log, col_part, status);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_row_sums(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                   float* out, int* status, void* stream) {
+    if (!indptr || !out || !status || n <= 0 || G <= 0 || nnz < 0 || (nnz > 0 && (!indices || !values)))
+        return DCAHIP_EINVAL;
+    int grid = (n + 3) / 4;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(csr_row_sums_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), indptr, indices,
+                       values, nnz, n, G, out, status);
     return (int)hipGetLastError();
 }

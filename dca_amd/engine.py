@@ -319,6 +319,11 @@ class Engine:
         self.Bmax = 0
         self._hl = None             # (tensor, leading dimension) the heads read: the last hidden layer's output, or the input batch
         self.X = self.Y = self.sf = self.perm = None
+        # counts-resident mode (attach_counts): the raw counts as CSR; X / Y / sf are then [Bmax, .] tiles that every step
+        # and every inference chunk gathers first (dcahip_csr_gather), and the kernels read the tiles through an identity
+        # row vector and a zero cursor word (_kperm / _kcur) -- the real perm / cursor select the rows of the gather only
+        self.csr = None
+        self.perm_id = self.cursor0 = None
         self.tile_order = None
         self.hist = None
         self.prof = None            # EventProfiler or None
@@ -374,6 +379,15 @@ class Engine:
 
     def _t(self, name):
         return self.prof.section(name) if self.prof is not None else _NULL
+
+    @property
+    def _kperm(self):
+        """The row vector the kernels gather the minibatch through (counts-resident mode: the identity over the tile)."""
+        return self.perm_id if self.csr is not None else self.perm
+
+    @property
+    def _kcur(self):
+        return self.cursor0 if self.csr is not None else self.cursor
 
     @property
     def _dhl(self):
@@ -554,6 +568,7 @@ class Engine:
         lay = self.lay
         n = X.shape[0]
         assert X.shape[1] == lay.G_in
+        self.csr = None
         self.n = n
         self.ldx = _r4(lay.G_in)
         csr_x = _prep.csr_capable(X, self.dev, self.ops)
@@ -593,11 +608,70 @@ class Engine:
         layer takes the sparse kernels.  compact: a CompactCounts of Y built earlier (else built here)."""
         lay = self.lay
         assert X.shape[1] == _r4(lay.G_in) and (Y is None or Y.shape[1] == lay.Gp)
+        self.csr = None
         self.n, self.ldx, self.ldy = X.shape[0], X.shape[1], lay.Gp
         self.X, self.Y, self.sf = X, Y, sf
         self._set_tile_order()
         self._data_scales()
         self.attach_compact(compact, norm)
+
+    def attach_counts(self, csr, sf, norm):
+        """Counts-resident mode: the raw counts stay on the device as CSR (prep.CsrCounts, [n, G_out]) and every step gathers
+        its minibatch from them -- Y, the input X = (f(y / fac) - mean) / std described by norm (dict(fac, do_log, mean, std),
+        dca/io.py:99-109) and sf [n] -- into [Bmax, .] tiles (dcahip_csr_gather) before the kernels of the dense form run on
+        the tiles.  The byte store stays off (K-HEADS reads the fp32 tile, the first layer takes the dense products).  The
+        once-per-dataset values (tile order, K-HEADS' d_exp, the wide networks' scales) come from the CSR and equal the
+        dense form's."""
+        lay = self.lay
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: counts-resident mode does not apply to data-parallel runs')
+        if norm is None or lay.G_in != lay.G_out or csr.G != lay.G_out:
+            raise ValueError('dca_amd: counts-resident mode needs input genes = output genes and a known input normalisation')
+        if not hasattr(self.ops, 'csr_gather'):
+            raise ValueError('dca_amd: counts-resident mode needs the CSR kernels (ops %s has no csr_gather)' % self.ops.name)
+        self.csr, self.sf_all, self.norm_c = csr, sf, dict(norm)
+        self.n, self.ldx, self.ldy = csr.n, _r4(lay.G_in), lay.Gp
+        self.gather_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.X = self.Y = self.sf = None
+        self._alloc_tiles()
+        self.cc = self.cc_in = None
+        self.cc_verdict = None
+        self._set_tile_order()
+        self._data_scales()
+
+    def _alloc_tiles(self):
+        if self.csr is None or self.Bmax <= 0:
+            return
+        B, f32 = self.Bmax, dict(dtype=torch.float32, device=self.dev)
+        if self.X is None or self.X.shape[0] < B:
+            self.X = torch.zeros(B, self.ldx, **f32)
+            self.Y = torch.zeros(B, self.ldy, **f32)
+            self.sf = torch.zeros(B, **f32)
+            self.perm_id = torch.arange(B, dtype=torch.int32, device=self.dev)
+            self.cursor0 = torch.zeros(1, dtype=torch.int64, device=self.dev)
+
+    def _gather(self, B, row0=None):
+        """Counts-resident mode: the tile of B rows -- perm[cursor + r] (row0 None: the training step's rows, read on the
+        device) or the storage rows row0 + r."""
+        nm = self.norm_c
+        perm, cur = (self.perm, self.cursor) if row0 is None else (None, None)
+        self.ops.csr_gather(self.csr, perm, cur, 0 if row0 is None else row0, B, self.sf_all, nm.get('fac'),
+                            nm.get('do_log', False), nm.get('mean'), nm.get('std'), self.Y, self.ldy, self.X, self.ldx,
+                            self.sf, self.gather_status)
+
+    def _range_rows(self, s, b):
+        """Storage rows [s, s + b) of an inference pass: their first row in X / Y / sf -- s itself, or 0 once the
+        counts-resident mode has gathered them into the tile."""
+        if self.csr is None:
+            return s
+        self._gather(b, row0=s)
+        return 0
+
+    def _csr_rows(self, r0, r1):
+        """Counts-resident mode: (column index, value) of the stored entries of storage rows r0 .. r1 - 1."""
+        c = self.csr
+        a, b = int(c.indptr[r0].item()), int(c.indptr[r1].item())
+        return c.indices[a:b].to(torch.int64), c.values[a:b]
 
     def _data_scales(self):
         """What the fp16 x 2 plane products of the wide networks need to know about the resident data, once per dataset:
@@ -608,6 +682,10 @@ class Engine:
         self.d_exp = None
         self.heads_d_exp = self._heads_d_exp()
         ops = self.ops
+        if self.csr is not None:
+            if self.cfg.wide_h2 and hasattr(ops, 'gemm_h2') and self.lay.hidden and self.lay.hL > 64 and self.dev.type == 'cuda':
+                self._csr_data_scales()
+            return
         if not (self.cfg.wide_h2 and hasattr(ops, 'gemm_h2') and self.lay.hidden and self.lay.hL > 64) or self.X is None:
             return
         if not self.X.is_cuda:
@@ -620,6 +698,31 @@ class Engine:
             self.x_exp = torch.zeros(2, dtype=torch.int32, device=self.dev)
             ops.absmax_exp(self.X, self.ldx, self.X.shape[0], self.lay.G_in, self.x_exp)
 
+    def _csr_data_scales(self):
+        """_data_scales of the dense form from the CSR: y_max over [n, Gp] (the zeros included whenever the matrix has one),
+        and the block exponent of X over all rows, gathered a range at a time."""
+        c, lay = self.csr, self.lay
+        ymax = float(c.values.max().item()) if c.nnz else 0.0
+        if c.nnz and c.nnz < c.n * lay.Gp:
+            ymax = max(ymax, 0.0)                      # (a NaN stays NaN, as in the dense max)
+        bound = max(1e4, 2.0 * ymax + 50.0) + 0.5 * float(self.ridge)
+        self.d_exp = int(np.floor(np.log2(65000.0 / bound)))
+        if lay.hidden[0] >= 128 and c.n > 0:
+            amax = torch.zeros((), dtype=torch.float32, device=self.dev)
+            b = min(4096, c.n)
+            Yt = torch.empty(b, self.ldy, dtype=torch.float32, device=self.dev)
+            Xt = torch.empty(b, self.ldx, dtype=torch.float32, device=self.dev)
+            nm = self.norm_c
+            for s in range(0, c.n, b):
+                e = min(c.n, s + b)
+                self.ops.csr_gather(c, None, None, s, e - s, None, nm.get('fac'), nm.get('do_log', False), nm.get('mean'),
+                                    nm.get('std'), Yt, self.ldy, Xt, self.ldx, None, self.gather_status)
+                amax = torch.maximum(amax, Xt[:e - s, :lay.G_in].abs().max())
+            one = torch.zeros(1, 4, dtype=torch.float32, device=self.dev)
+            one[0, 0] = amax
+            self.x_exp = torch.zeros(2, dtype=torch.int32, device=self.dev)
+            self.ops.absmax_exp(one, 4, 1, 1, self.x_exp)
+
     def _heads_d_exp(self):
         """K-HEADS' starting exponent for its gradient pieces (include/dcahip.h, dcahip_heads_fused_compact: d_exp <= 0), once
         per dataset.  The kernel carries D = g 2^(8 + d_exp) in fp16: |g| <= 117 fits at d_exp = 0, and a 32 x 32 tile with a larger
@@ -629,6 +732,24 @@ class Engine:
         |g| <~ 2 c.  UMI data (the benchmark matrices: c < 58) keeps 0.  Rank-local on purpose (attach is not a collective:
         predict may run on one rank): data-parallel ranks may start at different exponents, which moves their gradients within
         the products' tolerance only."""
+        c = getattr(self, 'csr', None)
+        if c is not None:
+            if self.dev.type != 'cuda' or c.n == 0:
+                return 0
+            rows = min(c.n, max(1, (1 << 24) // max(1, self.ldy)))
+            sel = torch.arange(0, c.n, max(1, c.n // rows), device=self.dev)[:rows]
+            lens = c.indptr[sel + 1] - c.indptr[sel]
+            starts = torch.repeat_interleave(c.indptr[sel] - torch.cumsum(lens, 0) + lens, lens)
+            idx = starts + torch.arange(int(lens.sum().item()), device=self.dev)
+            v = c.values[idx]
+            cnt = torch.bincount(torch.nan_to_num(v, nan=0.0).clamp(0, 65535.0).to(torch.int64), minlength=2)
+            numel = int(sel.numel()) * self.lay.G_out
+            cnt[0] += numel - int(v.numel())                  # the zeros the CSR does not store
+            tail = torch.flip(torch.cumsum(torch.flip(cnt, [0]), 0), [0]).to(torch.float64) / float(numel)
+            over = torch.nonzero(tail > 5e-5)
+            cc = float(over.max().item()) if over.numel() else 0.0
+            need = 2.0 * cc / 117.0
+            return 0 if need <= 1.0 else -min(24, int(np.ceil(np.log2(need))))
         Y = self.Y
         if Y is None or not getattr(Y, 'is_cuda', False) or Y.numel() == 0:
             return 0
@@ -727,15 +848,20 @@ class Engine:
         tiles' cost follows their non-zero counts (the compacted NB pass), so tiles are sorted by the non-zero count
         of their columns (heaviest first) and taken pairwise: one pass over the resident counts per dataset."""
         self.tile_order = None
-        if self.Y is None or not self.use_fused or self.ops.device_type != 'cuda':
+        if (self.Y is None and self.csr is None) or not self.use_fused or self.ops.device_type != 'cuda':
             return
         lay = self.lay
         n_ord = self.ops.heads_tile_order_len(lay.G_out)
         ntg = (lay.G_out + 31) // 32
-        rows = min(self.Y.shape[0], 65536)                       # a sample is enough to rank the tiles
         nz = torch.zeros(ntg * 32, dtype=torch.float32, device=self.dev)
-        for s in range(0, rows, 8192):
-            nz[:lay.G_out] += (self.Y[s:min(rows, s + 8192), :lay.G_out] != 0).sum(dim=0)
+        if self.csr is not None:                                 # the same counts of the same rows, from the CSR
+            rows = min(self.csr.n, 65536)
+            col, val = self._csr_rows(0, rows)
+            nz += torch.bincount(col[val != 0], minlength=ntg * 32).to(torch.float32)
+        else:
+            rows = min(self.Y.shape[0], 65536)                   # a sample is enough to rank the tiles
+            for s in range(0, rows, 8192):
+                nz[:lay.G_out] += (self.Y[s:min(rows, s + 8192), :lay.G_out] != 0).sum(dim=0)
         order = torch.argsort(nz.view(ntg, 32).sum(dim=1), descending=True).to(torch.int32)
         pad = torch.arange(ntg, n_ord, dtype=torch.int32, device=self.dev)
         self.tile_order = torch.cat([order, pad]).contiguous()
@@ -853,6 +979,7 @@ class Engine:
             nb = ops.hidden_stack_workspace_bytes(len(lay.hidden), min(B, ops.hidden_stack_max_rows))
             self.ws_stack = torch.zeros(nb // 4 + 4, **f32) if nb > 0 else None
         self._sparse_workspaces()
+        self._alloc_tiles()
 
     # ------------------------------------------------------------------ forward pieces
     def _hidden_forward(self, B, rows_from, training, counts=None):
@@ -864,7 +991,7 @@ class Engine:
         if not lay.hidden:
             # no hidden layer: the heads read the minibatch of the input (network.py:98-99 input dropout applies)
             if rows_from[0] == 'perm':
-                ops.dropout_apply(self.X, self.ldx, self.perm, self.cursor, B, K, self.in_drop if training else 0.0,
+                ops.dropout_apply(self.X, self.ldx, self._kperm, self._kcur, B, K, self.in_drop if training else 0.0,
                                   self.drop_seed, self.drop_iter, INPUT_DROPOUT_LAYER, self.row0, self.Hin0, self.ldx)
                 self._hl = (self.Hin0, self.ldx)
             else:
@@ -881,7 +1008,7 @@ class Engine:
                         self.cc_in.ensure_lut(ops)
                     gather = rows_from[0] == 'perm'
                     with self._t('gemm_enc0_fwd'):
-                        ops.enc0_fwd_lut(self.cc_in, self.perm if gather else None, self.cursor if gather else None,
+                        ops.enc0_fwd_lut(self.cc_in, self._kperm if gather else None, self._kcur if gather else None,
                                          0 if gather else rows_from[1], B, K, h, Wi, h, bi, self.Z[0], self.ldh[0],
                                          self.ws_enc0l)
                 elif self._planes_enc0(B, training):
@@ -892,14 +1019,14 @@ class Engine:
                         if self._h2_enc0(B, training):
                             # two fp16 planes per operand, three products: X scaled by its dataset-wide exponent, W0 by its own
                             ops.split_planes_h2(self.X if gather else self.X[rows_from[1]:], self.ldx, B, K, self.pl['X'], self.x_exp,
-                                                perm=self.perm if gather else None, cursor=self.cursor if gather else None)
+                                                perm=self._kperm if gather else None, cursor=self._kcur if gather else None)
                             ops.absmax_exp(Wi, h, K, h, self.pl_exp['W0'])
                             ops.split_planes_h2(Wi, h, K, h, self.pl['W0'], self.pl_exp['W0'])
                             ops.gemm_h2(0, 0, B, h, _r16(K), self.pl['X'], self.pl['W0'], self.Z[0], self.ldh[0],
                                         exp_a=self.x_exp, exp_b=self.pl_exp['W0'], bias=bi, ws=self.ws)
                         else:
                             ops.split_planes(self.X if gather else self.X[rows_from[1]:], self.ldx, B, K, self.pl['X'],
-                                             perm=self.perm if gather else None, cursor=self.cursor if gather else None)
+                                             perm=self._kperm if gather else None, cursor=self._kcur if gather else None)
                             ops.split_planes(Wi, h, K, h, self.pl['W0'])
                             ops.gemm_p3(0, 0, B, h, _r16(K), self.pl['X'], self.pl['W0'], self.Z[0], self.ldh[0], bias=bi,
                                         ws=self.ws)
@@ -907,7 +1034,7 @@ class Engine:
                     assert rows_from[0] == 'perm'
                     if self.Xb is None or self.Xb.shape[0] < self.Bmax:
                         self.Xb = torch.zeros(self.Bmax, self.ldx, dtype=torch.float32, device=self.dev)
-                    ops.dropout_apply(self.X, self.ldx, self.perm, self.cursor, B, K, self.in_drop,
+                    ops.dropout_apply(self.X, self.ldx, self._kperm, self._kcur, B, K, self.in_drop,
                                       self.drop_seed, self.drop_iter, INPUT_DROPOUT_LAYER, self.row0,
                                       self.Xb, self.ldx)
                     with self._t('gemm_enc0_fwd'):
@@ -919,11 +1046,11 @@ class Engine:
                     with self._t('gemm_enc0_fwd'):
                         ops.transpose(Wi, h, K, h, self.W0T, self.ldx)
                         ops.sgemm(0, 1, B, h, K, self.X, self.ldx, self.W0T, self.ldx, self.Z[0], self.ldh[0],
-                                  bias=bi, perm=self.perm, cursor=self.cursor, ws=self.ws)
+                                  bias=bi, perm=self._kperm, cursor=self._kcur, ws=self.ws)
                 elif rows_from[0] == 'perm':
                     with self._t('gemm_enc0_fwd'):
                         ops.sgemm(0, 0, B, h, K, self.X, self.ldx, Wi, h, self.Z[0], self.ldh[0],
-                                  bias=bi, perm=self.perm, cursor=self.cursor, ws=self.ws)
+                                  bias=bi, perm=self._kperm, cursor=self._kcur, ws=self.ws)
                 else:
                     ops.sgemm(0, 0, B, h, K, self.X[rows_from[1]:], self.ldx, Wi, h, self.Z[0],
                               self.ldh[0], bias=bi, ws=self.ws)
@@ -1260,6 +1387,9 @@ class Engine:
         if comm.dp:
             self.set_world_counts(world_counts)
         if B > 0:
+            if self.csr is not None:
+                with self._t('csr_gather'):
+                    self._gather(B)
             self._forward_backward(B, Bg, inv_n)
         else:
             self._empty_step()
@@ -1352,7 +1482,7 @@ class Engine:
         self.ops.heads_fused(self._hl[0], self._hl[1], lay.view(w, 'Wh'), lay.NH,
                              lay.view(w, 'bh'), lay.Gp,
                              lay.view(w, 'theta_w') if lay.const_disp else None, self.Y,
-                             self.ldy, self.sf, self.perm, self.cursor, B, KL, lay.G_out,
+                             self.ldy, self.sf, self._kperm, self._kcur, B, KL, lay.G_out,
                              self.ridge, inv_n, self.flags, lay.view(g, 'Wh'), lay.NH,
                              lay.view(g, 'theta_w') if lay.const_disp else None,
                              self._dhl, self._hl[1], self.partials, self.ws_heads,
@@ -1453,7 +1583,7 @@ class Engine:
                         if self.cc_in.lutp is None:              # the per-cell table of the common counts: first use only
                             self._not_capturing('first use of the byte-store weight gradient')
                             self.cc_in.ensure_lut(ops)
-                        ops.enc0_dw_sparse(self.cc_in, self.perm, self.cursor, 0, B, Kp, h, self.dZ[0], self.ldh[0], gW, h,
+                        ops.enc0_dw_sparse(self.cc_in, self._kperm, self._kcur, 0, B, Kp, h, self.dZ[0], self.ldh[0], gW, h,
                                            self.ws_enc0)
                     elif self._h2_enc0(B, True):
                         ops.absmax_exp(self.dZ[0], self.ldh[0], B, h, self.pl_exp['dZ0'])
@@ -1470,13 +1600,13 @@ class Engine:
                     elif self.XT is not None and B >= 256:
                         # X^T dZ with BOTH operands contiguous along the batch (the fastest operand path of K-GEMM): the
                         # gathered minibatch and the (small) dZ transposed; the bias gradient = row sums of dZ^T
-                        ops.transpose(self.X, self.ldx, B, Kp, self.XT, self.ldb_t, perm=self.perm, cursor=self.cursor)
+                        ops.transpose(self.X, self.ldx, B, Kp, self.XT, self.ldb_t, perm=self._kperm, cursor=self._kcur)
                         ops.transpose(self.dZ[0], self.ldh[0], B, h, self.dZT, self.ldb_t)
                         ops.sgemm(0, 1, Kp, h, B, self.XT, self.ldb_t, self.dZT, self.ldb_t, gW, h, ws=self.ws)
                         ops.row_sums_strided(self.dZT, self.ldb_t, h, B, lay.view(g, 'b0'), 1)
                     else:
                         ops.sgemm(1, 0, Kp, h, B, self.X, self.ldx, self.dZ[0], self.ldh[0], gW, h,
-                                  perm=self.perm, cursor=self.cursor, colsum_row=True, ws=self.ws)
+                                  perm=self._kperm, cursor=self._kcur, colsum_row=True, ws=self.ws)
             else:
                 ops.sgemm(1, 0, Kp, h, B, self.Hcur[i - 1], self.ldh[i - 1], self.dZ[i], self.ldh[i], gW,
                           h, colsum_row=True, ws=self.ws)
@@ -1490,7 +1620,7 @@ class Engine:
         w, g = self.w, self.g
         self._heads_forward(B, KL)
         with self._t('zinb_nll'):
-            n = self._nll(B, self.perm, self.cursor, self.Y, self.sf, inv_n, True)
+            n = self._nll(B, self._kperm, self._kcur, self.Y, self.sf, inv_n, True)
         ops.loss_finalize(self.partials, n, inv_n, g[lay.P:])
         gWh, Wh = lay.view(g, 'Wh'), lay.view(w, 'Wh')
         if self.pl is not None and self._wide_planes(B) and B <= self.pl['H'].shape[1] and self._h2(B):
@@ -1550,9 +1680,10 @@ class Engine:
         chunk = chunk or self.Bmax
         for s in range(r0, r1, chunk):
             b = min(chunk, r1 - s)
-            KL = self._hidden_forward(b, ('range', s), False)
+            o = self._range_rows(s, b)
+            KL = self._hidden_forward(b, ('range', o), False)
             self._heads_forward(b, KL)
-            n = self._nll(b, None, None, self.Y[s:], self.sf[s:], 1.0, False)
+            n = self._nll(b, None, None, self.Y[o:], self.sf[o:], 1.0, False)
             ops.loss_finalize(self.partials, n, scale, self.val_loss_tmp)
             ops.step_end(self.val_loss_tmp, 1.0, None, 0, self.acc[1:], None, 0)
 
@@ -1560,6 +1691,7 @@ class Engine:
         """Inference forward over storage rows [r0, r0+b).  Returns device views (valid until
         the next call): dict with 'mean' (mean*sf), 'dispersion', 'dropout', 'latent'."""
         lay, ops = self.lay, self.ops
+        r0 = self._range_rows(r0, b)
         KL = self._hidden_forward(b, ('range', r0), False)
         out = {}
         if 'latent' in want:
@@ -1592,7 +1724,7 @@ class Engine:
         latent = torch.zeros(n, lay.hidden[self.center], dtype=torch.float32, device=self.dev)
         for s in range(0, n, self.Bmax):
             b = min(self.Bmax, n - s)
-            self._hidden_forward(b, ('range', s), False)
+            self._hidden_forward(b, ('range', self._range_rows(s, b)), False)
             self.HL_all[s:s + b].copy_(self.Hcur[-1][:b])
             latent[s:s + b].copy_(self.Z[self.center][:b, :lay.hidden[self.center]])
         return latent
@@ -1622,7 +1754,8 @@ class Engine:
         m = planes.get('mean')
         d = planes.get('disp') if 'dispersion' in want else None
         p = planes.get('pi') if 'dropout' in want else None
-        ops.heads_infer(m, d, p, lda, self.sf, n, gb, m if 'mean' in want else None, d, p, lda, self.flags & 8)
+        sf = self.sf_all if self.csr is not None else self.sf
+        ops.heads_infer(m, d, p, lda, sf, n, gb, m if 'mean' in want else None, d, p, lda, self.flags & 8)
         for key, src in (('mean', m), ('dispersion', d), ('dropout', p)):
             if key in want and src is not None:
                 ops.transpose(src, lda, n, gb, out[key], out[key].shape[1])

@@ -149,6 +149,12 @@ _SIGNATURES = {
     'dcahip_prep_col_finish': (_c.c_int, [_f64p, _c.c_int, _c.c_int, _c.c_double, _f32p, _f32p, _f32p, _vp]),
     'dcahip_prep_scale': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _vp]),
     'dcahip_csr_expand': (_c.c_int, [_i32p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _i32p, _vp]),
+    'dcahip_csr_gather': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
+                                     _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _i32p,
+                                     _vp]),
+    'dcahip_csr_col_pass': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_int, _f64p, _i32p,
+                                       _vp]),
+    'dcahip_csr_row_sums': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _i32p, _vp]),
     'dcahip_rmsprop_clip': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_float,
                                        _c.c_float, _c.c_float, _vp]),
     'dcahip_hidden_stack_max_rows': (_c.c_int, []),

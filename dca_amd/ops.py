@@ -467,6 +467,28 @@ class HipOps:
         hip.check(self.L.dcahip_csr_expand(p(indptr), p(indices), p(values), nnz, rows, G, p(Y), ldy, p(status),
                                            hip.stream()), 'csr_expand')
 
+    def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
+        """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
+        every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];
+        status (int32 device word) += what had to be ignored (include/dcahip.h)."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_csr_gather(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G, p(perm),
+                                           p(cursor), int(row0), B, p(sf), p(fac), int(bool(do_log)), p(mean), p(std),
+                                           p(Y), ldy, p(X), ldx if X is not None else 0, p(sf_out), p(status),
+                                           hip.stream()), 'csr_gather')
+
+    def csr_col_pass(self, csr, fac, do_log, col_part, status):
+        """prep_col_pass's per-gene partials [R][2][Gp] (R = prep_chunks(n)) from a resident CSR, bit for bit."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_csr_col_pass(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G, p(fac),
+                                             int(bool(do_log)), p(col_part), p(status), hip.stream()), 'csr_col_pass')
+
+    def csr_row_sums(self, csr, out, status):
+        """prep_row_sums of a resident CSR (exact for counts)."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_csr_row_sums(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G, p(out),
+                                             p(status), hip.stream()), 'csr_row_sums')
+
     # ------------------------------------------------------------------ optimizer
     def rmsprop_clip_end(self, w, g, ms, n, lr, rho, eps, clip, loss, weight, hist, rows_per_slot, acc, cursor, advance):
         p = hip.ptr

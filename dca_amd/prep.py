@@ -36,10 +36,13 @@ def host_chunk_tensor(a):
 
 class DeviceData:
     """Preprocessed tensors resident on the device: X [n, ldx] (network input), Y [n, ldy]
-    (raw counts, the loss target), sf [n]."""
+    (raw counts, the loss target), sf [n] -- or, in the counts-resident form, the raw counts as CSR (csr: a CsrCounts)
+    with sf and norm and no dense X / Y: the engine gathers each minibatch from it (Engine.attach_counts)."""
 
-    def __init__(self, X, Y, sf, n, G, host_x=None, norm=None):
+    def __init__(self, X, Y, sf, n, G, host_x=None, norm=None, csr=None):
         self.X, self.Y, self.sf, self.n, self.G = X, Y, sf, n, G
+        self.csr = csr
+        self.device = csr.device if csr is not None else getattr(X, 'device', None)
         # how X was made from Y (fac, do_log, mean, std: dca/io.py:99-109) -- lets the engine run the first layer on the
         # non-zero counts (Engine.attach_device_data); the compact byte store of Y is built once and kept here
         self.norm = norm
@@ -50,6 +53,13 @@ class DeviceData:
 
     def matches(self, host_x):
         return self.host_mark is None or fingerprint(host_x) == self.host_mark
+
+    def attach(self, eng):
+        """Hands these tensors to the engine (the dense ones, or the CSR of the counts-resident form)."""
+        if self.csr is not None:
+            eng.attach_counts(self.csr, self.sf, self.norm)
+        else:
+            eng.attach_device_data(self.X, self.Y, self.sf, norm=self.norm, compact=self.compact)
 
 
 def fingerprint(X):
@@ -211,6 +221,220 @@ def upload_sparse(X, dev, ops, ld, nnz_cap=1 << 22, row_cap=1 << 14):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- counts-resident mode
+class CsrCounts:
+    """Raw counts resident on the device as CSR (include/dcahip.h, dcahip_csr_gather): indptr [n + 1] int64 (absolute
+    offsets), indices [nnz] int32, values [nnz] fp32, canonical rows, n x G."""
+
+    def __init__(self, indptr, indices, values, n, G):
+        self.indptr, self.indices, self.values = indptr, indices, values
+        self.n, self.G = int(n), int(G)
+        self.nnz = int(values.numel())
+        self.device = indptr.device
+
+    @property
+    def nbytes(self):
+        return self.indptr.numel() * 8 + self.nnz * 8
+
+
+def dense_bytes(n, G):
+    """Device bytes of the dense form of an n x G dataset: X and Y in fp32 ([n, r4(G)] each), the byte store (about one
+    byte per element) and the first layer's per-cell table (about 1 KB per cell)."""
+    return int(n) * _r4(int(G)) * 9 + int(n) * 1024
+
+
+def counts_bytes(n, nnz):
+    """Device bytes of the counts-resident form: the CSR (int64 row pointer, int32 column + fp32 value per entry)."""
+    return (int(n) + 1) * 8 + int(nnz) * 8
+
+
+RESIDENT_MODES = ('auto', 'counts', 'dense')
+
+
+def choose_residency(mode, dense_need, counts_need, free, world=1, output_subset=False, use_raw_as_output=True,
+                     has_norm=True):
+    """'dense' or 'counts': where the counts of a dataset live on the device (EngineConfig.resident).  'dense' keeps
+    today's [n, G] matrices; 'counts' keeps the CSR and gathers each minibatch.  'auto' stays dense whenever its estimate
+    fits into `free` device bytes, and whenever counts mode cannot apply: data parallel (world > 1), an output_subset,
+    use_raw_as_output=False, an input that is not a known function of the counts (has_norm=False).  Forcing 'counts' in
+    one of those cases raises ValueError saying why."""
+    if mode not in RESIDENT_MODES:
+        raise ValueError('resident must be one of %s (got %r)' % (', '.join(RESIDENT_MODES), mode))
+    if mode == 'dense':
+        return 'dense'
+    why = None
+    if world > 1:
+        why = 'data-parallel runs (%d ranks) keep dense residency' % world
+    elif output_subset:
+        why = 'an output_subset needs the dense count matrix'
+    elif not use_raw_as_output:
+        why = 'use_raw_as_output=False trains on the normalised input, which is not kept'
+    elif not has_norm:
+        why = 'the input is not a known function of the counts (no normalisation description)'
+    if mode == 'counts':
+        if why is not None:
+            raise ValueError('dca_amd: counts-resident mode does not apply: ' + why)
+        return 'counts'
+    if why is not None or dense_need <= free:
+        return 'dense'
+    return 'counts'
+
+
+def device_budget(dev):
+    """Bytes the caching allocator can still hand out on `dev`: the device's free memory plus what the allocator holds
+    unused, within its per-process fraction."""
+    free, total = torch.cuda.mem_get_info(dev)
+    reserved, allocated = torch.cuda.memory_reserved(dev), torch.cuda.memory_allocated(dev)
+    frac = torch.cuda.get_per_process_memory_fraction(dev) if hasattr(torch.cuda, 'get_per_process_memory_fraction') else 1.0
+    return max(0, min(free + reserved - allocated, int(frac * total) - allocated))
+
+
+def _nnz(X):
+    return int(X.nnz) if sp_sparse.issparse(X) else int(np.count_nonzero(np.asarray(X)))
+
+
+def residency(X, dev, ops, mode=None):
+    """The residency of host matrix X on `dev` for K-PREP (choose_residency with the device's budget).  Counts mode needs
+    ops with the CSR kernels; 'auto' without them stays dense."""
+    if mode is None:
+        from . import config as _config
+        mode = _config.current().resident
+    if mode == 'dense':
+        return 'dense'
+    import os
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if not hasattr(ops, 'csr_gather'):
+        if mode == 'counts':
+            raise ValueError('dca_amd: counts-resident mode needs the CSR kernels (ops %s has no csr_gather)'
+                             % getattr(ops, 'name', type(ops).__name__))
+        return 'dense'
+    n, G = X.shape
+    need = dense_bytes(n, G)
+    if mode == 'auto':
+        if dev.type != 'cuda' or world > 1:
+            return 'dense'
+        free = device_budget(dev)
+        if need <= free:
+            return 'dense'
+        return choose_residency(mode, need, counts_bytes(n, _nnz(X)), free, world=world)
+    return choose_residency(mode, need, 0, 0, world=world)
+
+
+def upload_csr(X, dev, ops, nnz_cap=1 << 22, row_cap=1 << 14):
+    """Host matrix [n, G] (scipy.sparse; a dense one is compressed on the host) -> a CsrCounts on `dev`, staged through the
+    page-locked slots of upload_sparse (pack_csr_chunk: canonical rows, fp32 values) without expanding it.  A malformed
+    matrix raises ValueError."""
+    n, G = X.shape
+    if not sp_sparse.issparse(X):
+        X = sp_sparse.csr_matrix(np.asarray(X))
+    if X.format != 'csr':
+        X = X.tocsr()
+    ip = X.indptr.astype(np.int64, copy=False)
+    if len(ip) != n + 1 or ip[0] != 0 or ip[-1] > len(X.indices) or len(X.data) != len(X.indices) or (np.diff(ip) < 0).any():
+        raise ValueError('dca_amd: malformed sparse matrix: indptr is not a non-decreasing row pointer into its %d entries'
+                         % len(X.indices))
+    total = int(ip[-1])
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    indices = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    values = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    base = 0
+    if dev.type != 'cuda':
+        for r0, r1 in plan_csr_chunks(ip, max(int(nnz_cap), G), row_cap):
+            hp = np.empty(r1 - r0 + 1, np.int32)
+            hi = np.empty(int(ip[r1] - ip[r0]), np.int32)
+            hv = np.empty(int(ip[r1] - ip[r0]), np.float32)
+            m = pack_csr_chunk(X, r0, r1, hp, hi, hv)
+            indptr[r0:r1 + 1] = torch.from_numpy(hp.astype(np.int64) + base)
+            indices[base:base + m] = torch.from_numpy(hi[:m])
+            values[base:base + m] = torch.from_numpy(hv[:m])
+            base += m
+    elif n > 0:
+        chunks = plan_csr_chunks(ip, max(int(nnz_cap), G), row_cap)
+        cap = max(int(ip[r1] - ip[r0]) for r0, r1 in chunks)
+        stage = _csr_stage(max(r1 - r0 for r0, r1 in chunks), cap)
+        dptr = [torch.empty(sl[0].numel(), dtype=torch.int32, device=dev) for sl in stage]
+        events = [torch.cuda.Event() for _ in range(2)]
+        for ci, (r0, r1) in enumerate(chunks):
+            slot = ci % 2
+            if ci >= 2:
+                events[slot].synchronize()
+            hp, hi, hv = stage[slot]
+            m = pack_csr_chunk(X, r0, r1, hp.numpy(), hi.numpy(), hv.numpy())
+            dptr[slot][:r1 - r0 + 1].copy_(hp[:r1 - r0 + 1], non_blocking=True)
+            indices[base:base + m].copy_(hi[:m], non_blocking=True)
+            values[base:base + m].copy_(hv[:m], non_blocking=True)
+            torch.add(dptr[slot][:r1 - r0 + 1].to(torch.int64), base, out=indptr[r0:r1 + 1])
+            events[slot].record()
+            base += m
+        torch.cuda.current_stream().synchronize()
+    csr = CsrCounts(indptr, indices[:base], values[:base], n, G)
+    if n > 0:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = torch.zeros(n, dtype=torch.float32, device=dev)
+        ops.csr_row_sums(csr, out, status)
+        bad = int(status.item())
+        if bad:
+            raise ValueError('dca_amd: malformed sparse matrix: %d entries / rows outside the matrix (a column outside '
+                             '[0, %d) or an indptr out of order)' % (bad, G))
+    return csr
+
+
+def csr_gene_counts(ops, csr):
+    """gene_counts of the dense matrix, bit for bit, from the CSR."""
+    dev, n, G = csr.device, csr.n, csr.G
+    R = ops.prep_chunks(n)
+    part = torch.zeros(R * 2 * _r4(G), dtype=torch.float64, device=dev)
+    sums = torch.zeros(G, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ops.csr_col_pass(csr, None, False, part, status)
+    ops.prep_col_finish(part, R, G, float(n), sums, None, None)
+    return sums
+
+
+def csr_cell_counts(ops, csr):
+    """cell_counts of the dense matrix (exact for counts) from the CSR."""
+    out = torch.zeros(csr.n, dtype=torch.float32, device=csr.device)
+    ops.csr_row_sums(csr, out, torch.zeros(1, dtype=torch.int32, device=csr.device))
+    return out
+
+
+def csr_norm(ops, csr, fac, logtrans_input, normalize_input):
+    """The description of transform()'s X for counts held as CSR: dict(fac, do_log, mean, std), mean / std bit for bit
+    those of the dense pass (csr_col_pass's partials -> prep_col_finish)."""
+    mean = std = None
+    if normalize_input:
+        dev, n, G = csr.device, csr.n, csr.G
+        R = ops.prep_chunks(n)
+        Gp = _r4(G)
+        part = torch.zeros(R * 2 * Gp, dtype=torch.float64, device=dev)
+        ops.csr_col_pass(csr, fac, logtrans_input, part, torch.zeros(1, dtype=torch.int32, device=dev))
+        mean = torch.zeros(Gp, dtype=torch.float32, device=dev)
+        std = torch.ones(Gp, dtype=torch.float32, device=dev)
+        ops.prep_col_finish(part, R, G, float(n), None, mean, std)
+    return dict(fac=fac, do_log=bool(logtrans_input), mean=mean, std=std)
+
+
+def download_csr(ops, csr, norm, chunk_rows=2048):
+    """The normalised input X of counts held as CSR -> new host array [n, G]: row ranges gathered into one device tile and
+    copied down (the dense matrix is never resident on the device)."""
+    n, G = csr.n, csr.G
+    dev = csr.device
+    out = np.empty((n, G), dtype=np.float32)
+    if n == 0:
+        return out
+    b = min(chunk_rows, n)
+    ld = _r4(G)
+    Yt = torch.empty(b, ld, dtype=torch.float32, device=dev)
+    Xt = torch.empty(b, ld, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    for s in range(0, n, b):
+        e = min(n, s + b)
+        ops.csr_gather(csr, None, None, s, e - s, None, norm.get('fac'), norm.get('do_log', False), norm.get('mean'),
+                       norm.get('std'), Yt, ld, Xt, ld, None, status)
+        out[s:e] = Xt[:e - s, :G].cpu().numpy()
+    return out
+
+
 def _upload(X, dev, chunk_rows=2048, ops=None):
     """Host matrix -> [n, r4(G)] device tensor.  On a GPU the rows travel through two page-locked staging buffers:
     host threads fill buffer i + 1 (dcahost_parallel_copy) while buffer i crosses PCIe -- a pageable .to(device)
@@ -319,13 +543,17 @@ def transform(ops, Y, n, G, fac, logtrans_input, normalize_input, comm=None, ret
 
 
 def resident_counts(X, ops=None, device=None):
-    """(Y, gene_totals): the host count matrix on the device and the exact integer total of every gene."""
+    """(Y, gene_totals): the host count matrix on the device and the exact integer total of every gene.  Y is a CsrCounts
+    when the counts go counts-resident (residency()), else the dense [n, r4(G)] tensor."""
     if ops is None:
         from .ops import HipOps
         ops = HipOps()
     dev = torch.device(device) if device is not None else (
         torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
     n, G = X.shape
+    if residency(X, dev, ops) == 'counts':
+        csr = upload_csr(X, dev, ops)
+        return csr, csr_gene_counts(ops, csr).cpu().numpy()
     Y = _upload(X, dev, ops=ops)
     return Y, gene_counts(ops, Y, n, G).cpu().numpy()
 
@@ -340,7 +568,13 @@ def normalize_device(adata, filter_min_counts=True, size_factors=True, normalize
     dev = torch.device(device) if device is not None else (
         torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
     n, G = adata.X.shape
-    if Y is None or tuple(Y.shape) != (n, _r4(G)):
+    if isinstance(Y, CsrCounts) and (Y.n, Y.G) == (n, G):
+        return _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, logtrans_input, ops, dev,
+                                 to_host, Y)
+    if Y is None and residency(adata.X, dev, ops) == 'counts':
+        return _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, logtrans_input, ops, dev,
+                                 to_host, None)
+    if Y is None or isinstance(Y, CsrCounts) or tuple(Y.shape) != (n, _r4(G)):
         Y = _upload(adata.X, dev, ops=ops)       # (else: resident_counts() uploaded these counts already)
 
     if filter_min_counts:                                         # io.py:90-92
@@ -394,3 +628,57 @@ def normalize_device(adata, filter_min_counts=True, size_factors=True, normalize
     if to_host:
         adata.X = _download(X, n, G)
     return adata, DeviceData(X, Y, sf_d, n, G, host_x=adata.X if to_host else None, norm=norm)
+
+
+def _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, logtrans_input, ops, dev, to_host, csr):
+    """normalize_device in the counts-resident form: the statistics from the CSR kernels, each filter a subset of the host
+    matrix followed by a new upload of it; the host AnnData ends up exactly as the dense form leaves it."""
+    from . import io as _io
+    n, G = adata.X.shape
+    if csr is None:
+        csr = upload_csr(adata.X, dev, ops)
+    if filter_min_counts:                                         # io.py:90-92
+        gc = csr_gene_counts(ops, csr).cpu().numpy()
+        adata.var['n_counts'] = gc
+        keep = gc >= 1
+        if not keep.all():
+            _io._subset(adata, cols=keep)
+            G = int(keep.sum())
+            csr = upload_csr(adata.X, dev, ops)
+        cc = csr_cell_counts(ops, csr).cpu().numpy()
+        adata.obs['n_counts'] = cc
+        keep = cc >= 1
+        if not keep.all():
+            _io._subset(adata, rows=keep)
+            n = int(keep.sum())
+            csr = upload_csr(adata.X, dev, ops)
+
+    if size_factors or normalize_input or logtrans_input:         # io.py:94-97
+        adata.raw = adata.copy()
+    else:
+        adata.raw = adata
+
+    fac_d = None
+    if size_factors:                                              # io.py:99-101 (normalize_per_cell)
+        counts = csr_cell_counts(ops, csr).cpu().numpy()
+        adata.obs['n_counts'] = counts
+        keep = counts >= 1
+        if not keep.all():
+            _io._subset(adata, rows=keep)
+            counts = counts[keep]
+            n = int(keep.sum())
+            csr = upload_csr(adata.X, dev, ops)
+        after = np.median(counts)
+        c2 = counts + (counts == 0)
+        fac = (c2 / after).astype(np.float32)
+        adata.obs['size_factors'] = adata.obs.n_counts / np.median(adata.obs.n_counts)
+        fac_d = torch.as_tensor(fac).to(dev)
+        sf_d = torch.as_tensor(np.asarray(adata.obs['size_factors'].values, dtype=np.float32)).to(dev)
+    else:
+        adata.obs['size_factors'] = 1.0
+        sf_d = torch.ones(n, dtype=torch.float32, device=dev)
+
+    norm = csr_norm(ops, csr, fac_d, logtrans_input, normalize_input)
+    if to_host:
+        adata.X = download_csr(ops, csr, norm)
+    return adata, DeviceData(None, None, sf_d, n, G, host_x=adata.X if to_host else None, norm=norm, csr=csr)

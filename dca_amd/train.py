@@ -309,11 +309,17 @@ def train(adata, network, output_dir=None, optimizer='RMSprop', learning_rate=No
     v0, nv = ddist.shard(n_val, comm.world, comm.rank)
     rows = np.r_[np.arange(t0, t0 + nt), split_at + np.arange(v0, v0 + nv)]
     dd = getattr(adata, '_dca_device', None)
+    if dd is not None and dd.csr is not None and eng.cfg.resident == 'counts':
+        # forced counts-resident mode: say why it cannot apply instead of falling back to a dense upload
+        from .prep import choose_residency
+        choose_residency('counts', 0, 0, 0, world=comm.world, output_subset=bool(output_subset),
+                         use_raw_as_output=use_raw_as_output, has_norm=dd.norm is not None)
     if comm.world == 1 and dd is not None and not output_subset and use_raw_as_output and \
             dd.n == n and dd.G == X.shape[1] == eng.lay.G_in == eng.lay.G_out and \
-            dd.X.device == eng.dev and dd.matches(X):
-        eng.attach_device_data(dd.X, dd.Y, dd.sf, norm=dd.norm, compact=dd.compact)      # K-PREP left the tensors in HBM
-        dd.compact = eng.cc if eng.cc is not None else (False if eng.cc_verdict is False else None)
+            dd.device == eng.dev and dd.matches(X):
+        dd.attach(eng)                                                                  # K-PREP left the tensors in HBM
+        if dd.csr is None:
+            dd.compact = eng.cc if eng.cc is not None else (False if eng.cc_verdict is False else None)
     elif comm.world == 1:
         eng.load_data(X, Y, sf)
     else:

@@ -504,6 +504,37 @@ int dcahip_csr_expand(const int* indptr, const int* indices, const float* values
                       float* Y, long ldy, int* status, void* stream);
 
 /*
+ * Resident CSR (counts-resident mode): the raw counts stay on the device as CSR -- indptr [n + 1] int64 (absolute offsets),
+ * indices int32, values fp32, canonical rows -- and every step builds only its own minibatch.  The preprocessing is that
+ * of dca/io.py:88-111 (as dcahip_prep_*), the per-batch rows those of the Keras feed, dca/train.py:83-98.  All three
+ * entries share csr_expand's guarantees: a storage row outside [0, n), an indptr entry outside [0, nnz] or decreasing, a
+ * column outside [0, G) is clamped / skipped and counted into *status (one int32, zeroed by the caller); nothing outside
+ * the buffers is read or written.
+ *
+ *   dcahip_csr_gather     the minibatch tile: destination row r < B takes storage row perm[*cursor + r] (perm != NULL) or
+ *                         row0 + r (perm == NULL).  Writes EVERY element of Y[r, 0 .. ldy) (the count or 0) and, when X
+ *                         is given, of X[r, 0 .. ldx): bit for bit what dcahip_prep_col_pass followed by dcahip_prep_scale
+ *                         write for that row, x = (f(y / fac[row]) - mean[g]) / std[g], f = log1p if do_log, each step
+ *                         optional as there (fac, mean / std may be NULL; mean and std together); pad columns g >= G hold
+ *                         f(0 / fac[row]) unscaled, as prep_col_pass leaves them.  sf_out[r] = sf[row] (sf_out may be
+ *                         NULL).  Reads nothing from the host: capturable in a step's graph, valid on every replay.
+ *                         One plain store per element, no atomics on the tiles.  B = 0 launches nothing.
+ *   dcahip_csr_col_pass   the per-gene fp64 partials [R][2][Gp] of x = f(y / fac) and x*x that dcahip_prep_col_pass
+ *                         produces for the dense rows, bit for bit (same row chunks R = dcahip_prep_chunks(n), same row
+ *                         order; the zeros it skips add +0.0): dcahip_prep_col_finish takes them unchanged (gene totals
+ *                         with fac = NULL, do_log = 0; mean / std otherwise).
+ *   dcahip_csr_row_sums   out[r] = sum of row r in fp64, rounded to fp32: dcahip_prep_row_sums for counts (exact).
+ */
+int dcahip_csr_gather(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                      const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                      const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
+                      float* X, long ldx, float* sf_out, int* status, void* stream);
+int dcahip_csr_col_pass(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                        const float* fac, int do_log, double* col_part, int* status, void* stream);
+int dcahip_csr_row_sums(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                        float* out, int* status, void* stream);
+
+/*
  * Keras clipvalue + Keras RMSprop (momentum 0) on one flat parameter buffer:
  *   g = clip(g, -clip, clip); ms = rho*ms + (1-rho)*g*g; w -= lr * g / (sqrt(ms) + eps)
  * (epsilon OUTSIDE the root: standalone keras 2.2 / 2.3 `p - lr * g / (K.sqrt(new_a) + self.epsilon)` and tf.keras
