@@ -23,7 +23,10 @@ constexpr int kApplyRows = 16;   // rows per workgroup in the apply kernels (256
 // Activation codes (the `act` / `relu` arguments of the C ABI): keras.activations names accepted by
 // Activation(self.activation) and LeakyReLU (alpha 0.3), dca/network.py:132-135.
 //   0 linear  1 relu  2 tanh  3 sigmoid  4 elu  5 selu  6 softplus  7 softsign  8 LeakyReLU(0.3)
+//   10 hard_sigmoid  11 exponential  12 swish  13 gelu (exact, erf)          (9 = PReLU: its own layer, never a code here)
 constexpr float kSeluScale = 1.0507009873554805f, kSeluAlpha = 1.6732632423543772f;
+// codes from kActPre up are not monotonic (swish, gelu): their slope is a function of the PRE-activation x, not of h
+constexpr int kActPre = 12;
 
 // relu / linear inline; the other activations out of line: the small-batch kernels unroll over their rows, and eight
 // inlined libm bodies per row made them instruction-fetch bound (10 000-line kernels that run once per step)
@@ -35,6 +38,10 @@ __device__ __attribute__((noinline)) float act_fwd_other(int a, float x) {
         case 5: return kSeluScale * (x > 0.f ? x : kSeluAlpha * expm1f(x));
         case 6: return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
         case 7: return x / (1.f + fabsf(x));
+        case 10: return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
+        case 11: return expf(x);                             // inf beyond x = 88.7, as TensorFlow's exp
+        case 12: { const float e = expf(-fabsf(x)); const float s = 1.f / (1.f + e); return x * (x >= 0.f ? s : e * s); }
+        case 13: return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
         default: return x > 0.f ? x : 0.3f * x;
     }
 }
@@ -44,22 +51,41 @@ __device__ __forceinline__ float act_fwd(int a, float x) {
     return act_fwd_other(a, x);
 }
 
-// derivative expressed through the OUTPUT h = act(x) (what the backward pass has at hand)
-__device__ __attribute__((noinline)) float act_grad_other(int a, float h) {
+// derivative expressed through the OUTPUT v = h = act(x) (what the backward pass has at hand) -- for codes >= kActPre
+// through the PRE-activation v = x instead (see act_slope)
+__device__ __attribute__((noinline)) float act_grad_other(int a, float v) {
     switch (a) {
-        case 2: return 1.f - h * h;
-        case 3: return h * (1.f - h);
-        case 4: return h > 0.f ? 1.f : h + 1.f;
-        case 5: return h > 0.f ? kSeluScale : h + kSeluScale * kSeluAlpha;
-        case 6: return -expm1f(-h);                          // sigmoid(x) = 1 - exp(-softplus(x))
-        case 7: { const float t = 1.f - fabsf(h); return t * t; }
-        default: return h > 0.f ? 1.f : 0.3f;
+        case 2: return 1.f - v * v;
+        case 3: return v * (1.f - v);
+        case 4: return v > 0.f ? 1.f : v + 1.f;
+        case 5: return v > 0.f ? kSeluScale : v + kSeluScale * kSeluAlpha;
+        case 6: return -expm1f(-v);                          // sigmoid(x) = 1 - exp(-softplus(x))
+        case 7: { const float t = 1.f - fabsf(v); return t * t; }
+        case 10: return v > 0.f && v < 1.f ? 0.2f : 0.f;
+        case 11: return v;
+        case 12: {                                           // s (1 + x (1 - s)), s = sigmoid(x)
+            const float e = expf(-fabsf(v)); const float s0 = 1.f / (1.f + e); const float s = v >= 0.f ? s0 : e * s0;
+            return s * (1.f + v * (1.f - s));
+        }
+        case 13:                                             // Phi(x) + x phi(x)
+            return 0.5f * (1.f + erff(v * 0.70710678118654752f)) + v * 0.39894228040143268f * expf(-0.5f * v * v);
+        default: return v > 0.f ? 1.f : 0.3f;
     }
 }
 __device__ __forceinline__ float act_grad(int a, float h) {
     if (a == 1) return h > 0.f ? 1.f : 0.f;
     if (a == 0) return 1.f;
     return act_grad_other(a, h);
+}
+// the slope at an element of a batch-normalised layer: output h, normalised input xh, bc = beta of its column (read only
+// for codes >= kActPre, whose pre-activation is xh + beta: BatchNormalization(center=True, scale=False))
+__device__ __forceinline__ float act_slope(int a, float h, float xh, float bc) {
+    if (a == 1) return h > 0.f ? 1.f : 0.f;
+    if (a == 0) return 1.f;
+    return act_grad_other(a, a >= kActPre ? xh + bc : h);
+}
+__device__ __forceinline__ float pre_beta(int a, const float* beta, int c) {
+    return a >= kActPre ? beta[c] : 0.f;
 }
 
 __host__ __device__ inline int n_chunks(int B) {
@@ -296,7 +322,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(BnApplyArgs a) {
 __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* dH, long ldd,
                                                           const float* Hact, long ldh,
                                                           const float* xhat, long ldx, int B, int H,
-                                                          float* part, int act) {
+                                                          float* part, int act, const float* beta) {
     __shared__ float sm[256];
     const int R = gridDim.x, r = blockIdx.x;
     const int cr = chunk_rows(B, R);
@@ -305,6 +331,7 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* dH, long 
     for (int c0 = blockIdx.y * 64; c0 < H; c0 += 64 * gridDim.y) {
         const int c = c0 + tx;
         float s1 = 0.f, s2 = 0.f;
+        const float bc = c < H ? pre_beta(act, beta, c) : 0.f;
         if (c < H)
             for (int i0 = r0 + ty; i0 < r1; i0 += 32) {      // 8 rows per batch: all 24 loads in flight, then the arithmetic
                 float d[8], h[8], x[8];
@@ -315,7 +342,7 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* dH, long 
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const float dy = i0 + 4 * u < r1 ? d[u] * act_grad(act, h[u]) : 0.f;
+                    const float dy = i0 + 4 * u < r1 ? d[u] * act_slope(act, h[u], x[u], bc) : 0.f;
                     s1 += dy; s2 += dy * x[u];
                 }
             }
@@ -332,6 +359,7 @@ struct BnBwdArgs {
     const float* dH; long ldd; const float* Hact; long ldh; const float* xhat; long ldx;
     const float* inv_std; const float* sums; int E; float n_total; int B, H;
     float* dZ; long ldz; float* dbeta; int act;
+    const float* beta;                  // codes >= kActPre: the offset of the pre-activation xhat + beta (else unused)
 };
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
@@ -361,7 +389,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
     for (int c0 = blockIdx.y * 64; c0 < a.H; c0 += 64 * gridDim.y) {
         const int c = c0 + tx;
         if (c >= a.H) continue;
-        const float m1 = s1[c], m2 = s2[c], inv = a.inv_std[c];
+        const float m1 = s1[c], m2 = s2[c], inv = a.inv_std[c], bc = pre_beta(a.act, a.beta, c);
         float d[kApplyRows / 4], h[kApplyRows / 4], x[kApplyRows / 4];
 #pragma unroll
         for (int u = 0; u < kApplyRows / 4; ++u) {           // loads first: the activation derivative may branch
@@ -371,7 +399,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
 #pragma unroll
         for (int u = 0; u < kApplyRows / 4; ++u) {
             const int i = r0 + ty + 4 * u;
-            if (i < r1) a.dZ[(long)i * a.ldz + c] = inv * (d[u] * act_grad(a.act, h[u]) - m1 - x[u] * m2);
+            if (i < r1) a.dZ[(long)i * a.ldz + c] = inv * (d[u] * act_slope(a.act, h[u], x[u], bc) - m1 - x[u] * m2);
         }
     }
 }
@@ -440,7 +468,7 @@ __global__ __launch_bounds__(256) void bn_bwd_small_kernel(BnBwdArgs a) {
     float dy[RPT], xh[RPT], ha[RPT];
     float s1 = 0.f, s2 = 0.f;
     const int ccl = cv ? c : a.H - 1;
-    const float inv_in = a.inv_std[ccl];
+    const float inv_in = a.inv_std[ccl], bc = pre_beta(a.act, a.beta, ccl);
     // every load first (unconditional, clamped addresses), then the arithmetic: see dense_bn_bwd_small_kernel
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
@@ -453,7 +481,7 @@ __global__ __launch_bounds__(256) void bn_bwd_small_kernel(BnBwdArgs a) {
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const bool ok = cv && ty + 4 * k < a.B;
-        dy[k] = ok ? dy[k] * act_grad(a.act, ha[k]) : 0.f;
+        dy[k] = ok ? dy[k] * act_slope(a.act, ha[k], xh[k], bc) : 0.f;
         xh[k] = ok ? xh[k] : 0.f;
         s1 += dy[k]; s2 += dy[k] * xh[k];
     }
@@ -769,6 +797,7 @@ struct DenseSmallBwdArgs {
     float* gW; long ldg;                // [K + 1, h]: weight gradient, row K = bias gradient
     float* dbeta;
     float* dHp; long lddp;              // gradient w.r.t. the layer input [B, K]
+    const float* beta;                  // batch norm, codes >= kActPre: pre-activation = xhat + beta (else unused)
 };
 
 constexpr int kBwdWGs = 8;      // workgroups of the small-batch layer backward: each recomputes dZ (cheap) and takes 1/8 of the products
@@ -790,6 +819,7 @@ __global__ __launch_bounds__(256) void dense_bn_bwd_small_kernel(DenseSmallBwdAr
         const bool cv = c < a.H;
         float dy[RPT], xh[RPT], ha[RPT];
         float s1 = 0.f, s2 = 0.f;
+        const float bc = a.batchnorm ? pre_beta(a.act, a.beta, cv ? c : a.H - 1) : 0.f;
         // every load first (unconditional, clamped addresses): the activation derivative below may branch, and a branch
         // between two loads costs a memory round trip per row
 #pragma unroll
@@ -803,7 +833,8 @@ __global__ __launch_bounds__(256) void dense_bn_bwd_small_kernel(DenseSmallBwdAr
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
             const bool ok = cv && ty + 4 * k < a.B;
-            dy[k] = ok ? dy[k] * act_grad(a.act, ha[k]) : 0.f;
+            // (without batch norm the Hact operand of codes >= kActPre is the pre-activation Z: act_grad reads it as x)
+            dy[k] = ok ? dy[k] * (a.batchnorm ? act_slope(a.act, ha[k], xh[k], bc) : act_grad(a.act, ha[k])) : 0.f;
             xh[k] = ok ? xh[k] : 0.f;
             s1 += dy[k]; s2 += dy[k] * xh[k];
         }
@@ -1043,6 +1074,7 @@ struct StackBwdLayer {                  // = dcahip_stack_bwd_layer (include/dca
     const float* Hprev; long ldp;
     float* gW; long ldg; float* dbeta;
     float* dHin; long lddh;             // gradient w.r.t. this layer's output (read at the start of a launch; written for the layer below)
+    const float* beta;                  // codes >= kActPre: pre-activation = xhat + beta (else unused)
 };
 
 struct StackFwdArgs {
@@ -1284,11 +1316,12 @@ __global__ __launch_bounds__(256) void hidden_stack_bwd_kernel(StackBwdArgs a) {
                 dyt[r * kStackLd + tx] = (r < nrows && tx < H) ? L.dHin[(long)(r0 + r) * L.lddh + tx] : 0.f;
         }
         float s1 = 0.f, s2 = 0.f;
+        const float bc = c < H ? pre_beta(a.act, L.beta, c) : 0.f;
         if (c < H)
             for (int r = ty; r < nrows; r += 4) {
                 const float h = L.Hact[(long)(r0 + r) * L.ldh + c];
                 const float xh = L.xhat[(long)(r0 + r) * L.ldx + c];
-                const float dy = dyt[r * kStackLd + c] * act_grad(a.act, h);
+                const float dy = dyt[r * kStackLd + c] * act_slope(a.act, h, xh, bc);
                 dyt[r * kStackLd + c] = dy;
                 xt[r * kStackLd + c] = xh;
                 s1 += dy; s2 += dy * xh;
@@ -1663,11 +1696,12 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
         dh[j] = L.dHin[row * L.lddh + cc]; hv[j] = L.Hact[row * L.ldh + cc]; xv[j] = L.xhat[row * L.ldx + cc];
     }
     float dy[kStepRows / 4];
+    const float bc = pre_beta(a.act, L.beta, cc);
     if (a.sums_only) {
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < kStepRows / 4; ++j) {
-            const float d = (ty + 4 * j < nrows && c < H) ? dh[j] * act_grad(a.act, hv[j]) : 0.f;
+            const float d = (ty + 4 * j < nrows && c < H) ? dh[j] * act_slope(a.act, hv[j], xv[j], bc) : 0.f;
             s1 += d; s2 += d * xv[j];
         }
         const float t1 = wg_rowlane_sum(s1, smf), t2 = wg_rowlane_sum(s2, smf);
@@ -1719,7 +1753,7 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
         const int r = ty + 4 * j;
         float dz = 0.f;
         if (r < nrows && c < H) {
-            dz = inv * (dh[j] * act_grad(a.act, hv[j]) - m1 - xv[j] * m2);
+            dz = inv * (dh[j] * act_slope(a.act, hv[j], xv[j], bc) - m1 - xv[j] * m2);
             if (!has_low) a.dZ0[(long)(r0 + r) * a.ldz0 + c] = dz;
         }
         dyt[r * kStackLd + c] = dz;
@@ -1778,13 +1812,14 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
     }
     // the layer below (k = its column): dH handed on through memory, dy and its block sums
     const StackBwdLayer& P = a.low;
+    const float pbc = pre_beta(a.act, P.beta, tx < K ? tx : (K > 0 ? K - 1 : 0));
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < kStepRows / 4; ++j) {
         const int r = ty + 4 * j;
         if (r < nrows && tx < K) {
             P.dHin[(long)(r0 + r) * P.lddh + tx] = acc[j];
-            const float d = acc[j] * act_grad(a.act, lh[j]);
+            const float d = acc[j] * act_slope(a.act, lh[j], lx[j], pbc);
             s1 += d; s2 += d * lx[j];
         }
     }
@@ -1847,8 +1882,9 @@ __global__ __launch_bounds__(256) void stack_bwd_chain_kernel(ChainBwdArgs a) {
 #pragma unroll
             for (int j = 0; j < R; ++j) dy[j] = hv[i][j] > 0.f ? dh[j] : 0.f;
         } else {
+            const float bc = pre_beta(a.act, L.beta, c < H ? c : H - 1);
 #pragma unroll
-            for (int j = 0; j < R; ++j) dy[j] = dh[j] * act_grad(a.act, hv[i][j]);
+            for (int j = 0; j < R; ++j) dy[j] = dh[j] * act_slope(a.act, hv[i][j], xv[i][j], bc);
         }
 #pragma unroll
         for (int j = 0; j < R; ++j) {
@@ -1990,12 +2026,31 @@ extern "C" int dcahip_bn_relu_apply(const float* Z, long ldz, int B, int H, cons
     return (int)hipGetLastError();
 }
 
+extern "C" int dcahip_bn_bwd_sums_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                                      const float* xhat, long ldx, int B, int H, float* part,
+                                      int act, const float* beta, void* stream) {
+    if (!dH || !Hact || !xhat || !part || B <= 0 || H <= 0 || (act >= kActPre && !beta)) return DCAHIP_EINVAL;
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(n_chunks(B), strip_blocks(H, n_chunks(B))), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act, beta);
+    return (int)hipGetLastError();
+}
+
 extern "C" int dcahip_bn_bwd_sums(const float* dH, long ldd, const float* Hact, long ldh,
                                   const float* xhat, long ldx, int B, int H, float* part,
                                   int act, void* stream) {
-    if (!dH || !Hact || !xhat || !part || B <= 0 || H <= 0) return DCAHIP_EINVAL;
-    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(n_chunks(B), strip_blocks(H, n_chunks(B))), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act);
+    return dcahip_bn_bwd_sums_pre(dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act, nullptr, stream);
+}
+
+extern "C" int dcahip_bn_bwd_apply_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                                       const float* xhat, long ldx, const float* inv_std,
+                                       const float* sums, int E, float n_total, int B, int H, float* dZ,
+                                       long ldz, float* dbeta, int act, const float* beta, void* stream) {
+    if (!dH || !Hact || !xhat || !inv_std || !sums || !dZ || E <= 0 || B <= 0 || H <= 0 || (act >= kActPre && !beta))
+        return DCAHIP_EINVAL;
+    BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz, dbeta, act, beta};
+    const int grid = (B + kApplyRows - 1) / kApplyRows;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid, strip_blocks(H, grid)), dim3(256), 2 * H * sizeof(float),
+                       static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
 }
 
@@ -2003,13 +2058,8 @@ extern "C" int dcahip_bn_bwd_apply(const float* dH, long ldd, const float* Hact,
                                    const float* xhat, long ldx, const float* inv_std,
                                    const float* sums, int E, float n_total, int B, int H, float* dZ,
                                    long ldz, float* dbeta, int act, void* stream) {
-    if (!dH || !Hact || !xhat || !inv_std || !sums || !dZ || E <= 0 || B <= 0 || H <= 0)
-        return DCAHIP_EINVAL;
-    BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz, dbeta, act};
-    const int grid = (B + kApplyRows - 1) / kApplyRows;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid, strip_blocks(H, grid)), dim3(256), 2 * H * sizeof(float),
-                       static_cast<hipStream_t>(stream), a);
-    return (int)hipGetLastError();
+    return dcahip_bn_bwd_apply_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz, dbeta, act,
+                                   nullptr, stream);
 }
 
 extern "C" int dcahip_bn_fused_max_rows() { return kFusedRows; }
@@ -2026,14 +2076,23 @@ extern "C" int dcahip_bn_relu_train_small(const float* Z, long ldz, int B, int H
     return (int)hipGetLastError();
 }
 
-extern "C" int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
-                                   const float* xhat, long ldx, const float* inv_std, float n_total,
-                                   int B, int H, float* dZ, long ldz, float* dbeta, int act, void* stream) {
-    if (!dH || !Hact || !xhat || !inv_std || !dZ || B <= 0 || B > kFusedRows || H <= 0) return DCAHIP_EINVAL;
-    BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, nullptr, 0, n_total, B, H, dZ, ldz, dbeta, act};
+extern "C" int dcahip_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                                       const float* xhat, long ldx, const float* inv_std, float n_total,
+                                       int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta,
+                                       void* stream) {
+    if (!dH || !Hact || !xhat || !inv_std || !dZ || B <= 0 || B > kFusedRows || H <= 0 || (act >= kActPre && !beta))
+        return DCAHIP_EINVAL;
+    BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, nullptr, 0, n_total, B, H, dZ, ldz, dbeta, act, beta};
     if (B <= 32) hipLaunchKernelGGL(bn_bwd_small_kernel<8>, dim3((H + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(bn_bwd_small_kernel<kFusedRows / 4>, dim3((H + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
+                                   const float* xhat, long ldx, const float* inv_std, float n_total,
+                                   int B, int H, float* dZ, long ldz, float* dbeta, int act, void* stream) {
+    return dcahip_bn_bwd_small_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, n_total, B, H, dZ, ldz, dbeta, act, nullptr,
+                                   stream);
 }
 
 extern "C" int dcahip_dense_small_max_k() { return kSmallK; }
@@ -2074,19 +2133,29 @@ extern "C" int dcahip_hidden_small_chain(const dcahip_small_layer* layers, int n
     return (int)hipGetLastError();
 }
 
+extern "C" int dcahip_dense_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                                             const float* xhat, long ldx, const float* inv_std,
+                                             const float* Hp, long ldp, const float* W, long ldw,
+                                             int B, int K, int H, int batchnorm, float n_total, int act,
+                                             float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
+                                             void* stream) {
+    if (!dH || !Hact || !Hp || !W || !gW || B <= 0 || B > kFusedRows || K <= 0 || K > kSmallK || H <= 0 || H > kSmallK)
+        return DCAHIP_EINVAL;
+    if (batchnorm && (!xhat || !inv_std || (act >= kActPre && !beta))) return DCAHIP_EINVAL;
+    DenseSmallBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm, n_total, act,
+                        gW, ldg, dbeta, dHp, lddp, beta};
+    if (B <= 32) hipLaunchKernelGGL(dense_bn_bwd_small_kernel<8>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(dense_bn_bwd_small_kernel<16>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return (int)hipGetLastError();
+}
+
 extern "C" int dcahip_dense_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
                                          const float* xhat, long ldx, const float* inv_std,
                                          const float* Hp, long ldp, const float* W, long ldw,
                                          int B, int K, int H, int batchnorm, float n_total, int act,
                                          float* gW, long ldg, float* dbeta, float* dHp, long lddp, void* stream) {
-    if (!dH || !Hact || !Hp || !W || !gW || B <= 0 || B > kFusedRows || K <= 0 || K > kSmallK || H <= 0 || H > kSmallK)
-        return DCAHIP_EINVAL;
-    if (batchnorm && (!xhat || !inv_std)) return DCAHIP_EINVAL;
-    DenseSmallBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm, n_total, act,
-                        gW, ldg, dbeta, dHp, lddp};
-    if (B <= 32) hipLaunchKernelGGL(dense_bn_bwd_small_kernel<8>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL(dense_bn_bwd_small_kernel<16>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return (int)hipGetLastError();
+    return dcahip_dense_bn_bwd_small_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm,
+                                         n_total, act, gW, ldg, dbeta, dHp, lddp, nullptr, stream);
 }
 
 extern "C" int dcahip_relu_bwd(const float* dH, long ldd, const float* Hact, long ldh, int B, int H,
@@ -2420,10 +2489,10 @@ extern "C" int dcahip_hidden_stack_bwd_sync(const dcahip_stack_bwd_layer* layers
     StackBwdLayer l[kStackMaxLayers];
     for (int i = 0; i < n; ++i) {
         const dcahip_stack_bwd_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || !q.dH) return DCAHIP_EINVAL;
+        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || !q.dH || (act >= kActPre && !q.beta)) return DCAHIP_EINVAL;
         if (i > 0 && (!q.W || !q.Hprev || !q.gW || q.K != layers[i - 1].H || q.K > 64)) return DCAHIP_EINVAL;
         l[i] = StackBwdLayer{q.W, q.ldw, q.K, q.H, q.Hact, q.ldh, q.xhat, q.ldx, q.inv_std, q.Hprev, q.ldp, q.gW, q.ldg,
-                             q.dbeta, q.dH, q.lddh};
+                             q.dbeta, q.dH, q.lddh, q.beta};
     }
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
     float* gwp = part + (long)n * nwg * 2 * 64;
@@ -2458,11 +2527,11 @@ extern "C" int dcahip_hidden_stack_bwd(const dcahip_stack_bwd_layer* layers, int
     if (stack_plan(n, B, rows_per_wg, first_step, last_step, n + 2, &a.nwg)) return DCAHIP_EINVAL;
     for (int i = 0; i < n; ++i) {
         const dcahip_stack_bwd_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std) return DCAHIP_EINVAL;
+        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || (act >= kActPre && !q.beta)) return DCAHIP_EINVAL;
         if (i > 0 && (!q.W || !q.Hprev || !q.gW || q.K != layers[i - 1].H || q.K > 64)) return DCAHIP_EINVAL;
         if (!q.dH && (i == n - 1 || !one_launch)) return DCAHIP_EINVAL;
         a.l[i] = StackBwdLayer{q.W, q.ldw, q.K, q.H, q.Hact, q.ldh, q.xhat, q.ldx, q.inv_std, q.Hprev, q.ldp, q.gW, q.ldg,
-                               q.dbeta, q.dH, q.lddh};
+                               q.dbeta, q.dH, q.lddh, q.beta};
     }
     a.n = n; a.B = B; a.act = act; a.first = first_step; a.last = last_step; a.n_total = n_total;
     a.dZ0 = dZ0; a.ldz0 = ldz0;

@@ -47,7 +47,19 @@ AE_FORK = ('nb-fork', 'zinb-fork')
 AE_HEADS['zinb-elempi'] = (('mean', 'disp', 'pi'), False, ())
 AE_ELEMPI = ('zinb-elempi',)
 ACT_CODES = {'linear': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'elu': 4, 'selu': 5, 'softplus': 6,
-             'softsign': 7, 'LeakyReLU': 8, 'PReLU': 9}      # 9: own element-wise layer with trainable slopes
+             'softsign': 7, 'LeakyReLU': 8, 'PReLU': 9,      # 9: own element-wise layer with trainable slopes
+             'hard_sigmoid': 10, 'exponential': 11, 'swish': 12, 'gelu': 13}
+# codes from here up (swish, gelu) are not monotonic: the backward takes their slope from the pre-activation
+ACT_PRE = 12
+
+
+def unsupported_activation(activation):
+    """The NotImplementedError for an activation name outside ACT_CODES."""
+    if activation == 'softmax':
+        return NotImplementedError("activation 'softmax' is not available on the MI355X path: it normalises over a layer's "
+                                   "units (a row reduction), not element by element like the other Activation names")
+    return NotImplementedError('activation %r is not available on the MI355X path (supported: %s)'
+                               % (activation, ', '.join(ACT_CODES)))
 INPUT_DROPOUT_LAYER = 255     # Philox counter word 3 of the input dropout (hidden layer i uses i)
 AE_LOSS_FLAG = {'poisson': 4, 'normal': 8}              # DCAHIP_NLL_POISSON / DCAHIP_NLL_MSE
 
@@ -281,9 +293,11 @@ class Engine:
         self.lay = ParamLayout(ae_type, input_size, output_size, hidden_size, batchnorm, prelu=(activation == 'PReLU'))
         self.ridge = float(ridge)
         if activation not in ACT_CODES:
-            raise NotImplementedError('activation %r is not available on the MI355X path (supported: %s)'
-                                      % (activation, ', '.join(ACT_CODES)))
+            raise unsupported_activation(activation)
         self.act = ACT_CODES[activation]       # Activation(self.activation), network.py:132-135
+        # swish / gelu: the backward reads the pre-activation -- xhat + beta with batch norm (beta handed to the kernels
+        # below through _pre_kw), the Z buffer of the layer without (passed where the others pass the output H)
+        self.act_pre = self.act >= ACT_PRE
         self.prelu = activation == 'PReLU'
         if self.prelu:                         # the BN / bias kernels stay linear, PReLU is its own layer behind them
             self.act = 0
@@ -1215,6 +1229,18 @@ class Engine:
             d.update(W=lay.view(w, 'W%d' % j), ldw=lay.hidden[j], bias=lay.view(w, 'b%d' % j), K=lay.hidden[j - 1])
         return d
 
+    def _pre_kw(self, i):
+        """Extra arguments of the batch-norm backward kernels of layer i: its beta for the codes whose slope is a function of
+        the pre-activation xhat + beta (include/dcahip.h, conventions), nothing for the others."""
+        if not (self.act_pre and self.lay.batchnorm):
+            return {}
+        return {'beta': self.lay.view(self.w, 'beta%d' % i)}
+
+    def _slope_in(self, i):
+        """The operand a backward kernel of layer i takes its slope from: the output H, or the pre-activation Z for
+        swish / gelu without batch norm (Z is written by the forward pass and not reused before the backward reads it)."""
+        return self.Z[i] if self.act_pre and not self.lay.batchnorm else self.H[i]
+
     def _layer_small(self, B, i):
         """Hidden layer i >= 1 at a small batch on one GPU: whole-layer kernels (forward and backward)."""
         if i < 1 or not self._bn_small(B) or self.prelu or self.has_dropout or not hasattr(self.ops, 'dense_bn_small'):
@@ -1508,7 +1534,7 @@ class Engine:
             layers = []
             for i, h in enumerate(lay.hidden):
                 d = dict(H=h, Hact=self.H[i], ldh=self.ldh[i], xhat=self.XH[i], ldx=self.ldh[i], inv_std=self.inv_std[i],
-                         dbeta=lay.view(g, 'beta%d' % i), dH=self.dH[i], lddh=self.ldh[i])
+                         dbeta=lay.view(g, 'beta%d' % i), dH=self.dH[i], lddh=self.ldh[i], **self._pre_kw(i))
                 if i > 0:
                     d.update(W=lay.view(w, 'W%d' % i), ldw=h, K=lay.hidden[i - 1], Hprev=self.H[i - 1], ldp=self.ldh[i - 1],
                              gW=lay.view(g, 'W%d' % i), ldg=h)
@@ -1548,20 +1574,20 @@ class Engine:
                 if self._layer_small(B, i):
                     # the layer's whole backward in one launch: d beta, dZ, weight / bias gradient, input gradient
                     Kp = lay.hidden[i - 1]
-                    ops.dense_bn_bwd_small(self.dH[i], self.ldh[i], self.H[i], self.ldh[i],
+                    ops.dense_bn_bwd_small(self.dH[i], self.ldh[i], self._slope_in(i), self.ldh[i],
                                            self.XH[i] if lay.batchnorm else None, self.ldh[i], self.inv_std[i],
                                            self.Hcur[i - 1], self.ldh[i - 1], lay.view(w, 'W%d' % i), h, B, Kp, h,
                                            lay.batchnorm, float(Bg), self.act, lay.view(g, 'W%d' % i), h,
                                            lay.view(g, 'beta%d' % i) if lay.batchnorm else None,
-                                           self.dH[i - 1], self.ldh[i - 1])
+                                           self.dH[i - 1], self.ldh[i - 1], **self._pre_kw(i))
                     continue
                 if lay.batchnorm and self._bn_small(B):
                     ops.bn_bwd_small(self.dH[i], self.ldh[i], self.H[i], self.ldh[i], self.XH[i], self.ldh[i],
                                      self.inv_std[i], float(Bg), B, h, self.dZ[i], self.ldh[i],
-                                     lay.view(g, 'beta%d' % i), self.act)
+                                     lay.view(g, 'beta%d' % i), self.act, **self._pre_kw(i))
                 elif lay.batchnorm:
                     ops.bn_bwd_sums(self.dH[i], self.ldh[i], self.H[i], self.ldh[i], self.XH[i],
-                                    self.ldh[i], B, h, self.bpart[i], self.act)
+                                    self.ldh[i], B, h, self.bpart[i], self.act, **self._pre_kw(i))
                     E = ops.col_moments_chunks(B)
                     sums, dbeta = self.bpart[i], lay.view(g, 'beta%d' % i)
                     if comm.dp:
@@ -1571,9 +1597,9 @@ class Engine:
                         dbeta = None
                     ops.bn_bwd_apply(self.dH[i], self.ldh[i], self.H[i], self.ldh[i], self.XH[i],
                                      self.ldh[i], self.inv_std[i], sums, E, float(Bg), B, h,
-                                     self.dZ[i], self.ldh[i], dbeta, self.act)
+                                     self.dZ[i], self.ldh[i], dbeta, self.act, **self._pre_kw(i))
                 else:
-                    ops.relu_bwd(self.dH[i], self.ldh[i], self.H[i], self.ldh[i], B, h, self.dZ[i],
+                    ops.relu_bwd(self.dH[i], self.ldh[i], self._slope_in(i), self.ldh[i], B, h, self.dZ[i],
                                  self.ldh[i], self.act)
             Kp = lay.G_in if i == 0 else lay.hidden[i - 1]
             gW = lay.view(g, 'W%d' % i)

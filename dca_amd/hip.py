@@ -35,7 +35,8 @@ class StackBwdLayer(_c.Structure):
     _fields_ = [('W', _c.c_void_p), ('ldw', _c.c_long), ('K', _c.c_int), ('H', _c.c_int),
                 ('Hact', _c.c_void_p), ('ldh', _c.c_long), ('xhat', _c.c_void_p), ('ldx', _c.c_long),
                 ('inv_std', _c.c_void_p), ('Hprev', _c.c_void_p), ('ldp', _c.c_long),
-                ('gW', _c.c_void_p), ('ldg', _c.c_long), ('dbeta', _c.c_void_p), ('dH', _c.c_void_p), ('lddh', _c.c_long)]
+                ('gW', _c.c_void_p), ('ldg', _c.c_long), ('dbeta', _c.c_void_p), ('dH', _c.c_void_p), ('lddh', _c.c_long),
+                ('beta', _c.c_void_p)]
 
 
 class RegDesc(_c.Structure):
@@ -45,7 +46,8 @@ class RegDesc(_c.Structure):
 
 
 ACT_CODES = {'linear': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'elu': 4, 'selu': 5, 'softplus': 6,
-             'softsign': 7, 'LeakyReLU': 8}
+             'softsign': 7, 'LeakyReLU': 8, 'hard_sigmoid': 10, 'exponential': 11, 'swish': 12, 'gelu': 13}
+ACT_PRE = 12        # codes from here up take their slope from the pre-activation (include/dcahip.h, conventions)
 
 OPT_KINDS = {'sgd': 0, 'rmsprop': 1, 'adagrad': 2, 'adadelta': 3, 'adam': 4, 'adamax': 5}
 
@@ -107,6 +109,11 @@ _SIGNATURES = {
     'dcahip_bn_bwd_apply': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
                                        _f32p, _c.c_int, _c.c_float, _c.c_int, _c.c_int, _f32p,
                                        _c.c_long, _f32p, _c.c_int, _vp]),
+    'dcahip_bn_bwd_sums_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _c.c_int,
+                                          _c.c_int, _f32p, _c.c_int, _f32p, _vp]),
+    'dcahip_bn_bwd_apply_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
+                                           _f32p, _c.c_int, _c.c_float, _c.c_int, _c.c_int, _f32p,
+                                           _c.c_long, _f32p, _c.c_int, _f32p, _vp]),
     'dcahip_bn_fused_max_rows': (_c.c_int, []),
     'dcahip_dense_small_max_k': (_c.c_int, []),
     'dcahip_dense_bn_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
@@ -115,10 +122,16 @@ _SIGNATURES = {
     'dcahip_dense_bn_bwd_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p, _c.c_long,
                                              _f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int,
                                              _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _vp]),
+    'dcahip_dense_bn_bwd_small_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p,
+                                                 _c.c_long, _f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                                 _c.c_float, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
+                                                 _vp]),
     'dcahip_bn_relu_train_small': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _f32p, _c.c_float,
                                               _c.c_float, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _vp]),
     'dcahip_bn_bwd_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_float,
                                        _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_int, _vp]),
+    'dcahip_bn_bwd_small_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_float,
+                                           _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_int, _f32p, _vp]),
     'dcahip_rmsprop_clip_end': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_float, _c.c_float, _c.c_float,
                                            _f32p, _c.c_double, _f32p, _c.c_int, _f64p, _i64p, _c.c_int, _vp]),
     'dcahip_relu_bwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p,

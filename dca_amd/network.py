@@ -131,6 +131,8 @@ class Autoencoder():
         unsupported = []
         if self.ae_type not in _engine.AE_HEADS:
             unsupported.append('ae_type=%r' % self.ae_type)
+        if self.activation == 'softmax':
+            raise _engine.unsupported_activation(self.activation)
         if self.activation not in _engine.ACT_CODES:
             unsupported.append('activation=%r' % self.activation)
         if not isinstance(self.init, str) or self.init.lower() not in _engine.KERAS_INITIALIZERS:

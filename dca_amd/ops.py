@@ -231,14 +231,25 @@ class HipOps:
                                               p(mm), p(mv), momentum, eps, int(relu), p(Hout), ldh,
                                               p(xhat), ldx, p(inv_std), hip.stream()), 'bn_relu_apply')
 
-    def bn_bwd_sums(self, dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act=1):
+    # beta (the batch-backward entries below): the layer's batch-norm offset, which codes >= hip.ACT_PRE need for their
+    # pre-activation xhat + beta; given, the *_pre entry point is called
+    def bn_bwd_sums(self, dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act=1, beta=None):
         p = hip.ptr
+        if beta is not None:
+            hip.check(self.L.dcahip_bn_bwd_sums_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, B, H, p(part),
+                                                    act, p(beta), hip.stream()), 'bn_bwd_sums_pre')
+            return
         hip.check(self.L.dcahip_bn_bwd_sums(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, B, H, p(part),
                                             act, hip.stream()), 'bn_bwd_sums')
 
     def bn_bwd_apply(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz,
-                     dbeta, act=1):
+                     dbeta, act=1, beta=None):
         p = hip.ptr
+        if beta is not None:
+            hip.check(self.L.dcahip_bn_bwd_apply_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std),
+                                                     p(sums), E, float(n_total), B, H, p(dZ), ldz, p(dbeta),
+                                                     act, p(beta), hip.stream()), 'bn_bwd_apply_pre')
+            return
         hip.check(self.L.dcahip_bn_bwd_apply(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std),
                                              p(sums), E, float(n_total), B, H, p(dZ), ldz, p(dbeta),
                                              act, hip.stream()), 'bn_bwd_apply')
@@ -253,8 +264,12 @@ class HipOps:
                                                     p(Hout), ldh, p(xhat), ldx, p(inv_std), hip.stream()),
                   'bn_relu_train_small')
 
-    def bn_bwd_small(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, n_total, B, H, dZ, ldz, dbeta, act=1):
+    def bn_bwd_small(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, n_total, B, H, dZ, ldz, dbeta, act=1, beta=None):
         p = hip.ptr
+        if beta is not None:
+            hip.check(self.L.dcahip_bn_bwd_small_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), float(n_total), B,
+                                                     H, p(dZ), ldz, p(dbeta), act, p(beta), hip.stream()), 'bn_bwd_small_pre')
+            return
         hip.check(self.L.dcahip_bn_bwd_small(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), float(n_total), B, H,
                                              p(dZ), ldz, p(dbeta), act, hip.stream()), 'bn_bwd_small')
 
@@ -306,7 +321,7 @@ class HipOps:
         A whole pass over a batch of at most 64 rows is one workgroup's work and needs no workspace (ws=None)."""
         arr = (hip.StackBwdLayer * len(layers))()
         for q, d in zip(arr, layers):
-            for k in ('W', 'Hact', 'xhat', 'inv_std', 'Hprev', 'gW', 'dbeta', 'dH'):
+            for k in ('W', 'Hact', 'xhat', 'inv_std', 'Hprev', 'gW', 'dbeta', 'dH', 'beta'):
                 setattr(q, k, hip.ptr(d.get(k)))
             for k in ('ldw', 'K', 'H', 'ldh', 'ldx', 'ldp', 'ldg', 'lddh'):
                 setattr(q, k, int(d.get(k, 0)))
@@ -329,7 +344,7 @@ class HipOps:
     def _bwd_layers(self, layers):
         arr = (hip.StackBwdLayer * len(layers))()
         for q, d in zip(arr, layers):
-            for k in ('W', 'Hact', 'xhat', 'inv_std', 'Hprev', 'gW', 'dbeta', 'dH'):
+            for k in ('W', 'Hact', 'xhat', 'inv_std', 'Hprev', 'gW', 'dbeta', 'dH', 'beta'):
                 setattr(q, k, hip.ptr(d.get(k)))
             for k in ('ldw', 'K', 'H', 'ldh', 'ldx', 'ldp', 'ldg', 'lddh'):
                 setattr(q, k, int(d.get(k, 0)))
@@ -351,8 +366,14 @@ class HipOps:
                                                       ws.numel() * ws.element_size(), hip.stream()), 'hidden_stack_bwd_sync')
 
     def dense_bn_bwd_small(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm, n_total, act,
-                           gW, ldg, dbeta, dHp, lddp):
+                           gW, ldg, dbeta, dHp, lddp, beta=None):
         p = hip.ptr
+        if beta is not None:
+            hip.check(self.L.dcahip_dense_bn_bwd_small_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), p(Hp), ldp,
+                                                           p(W), ldw, B, K, H, int(batchnorm), float(n_total), int(act),
+                                                           p(gW), ldg, p(dbeta), p(dHp), lddp, p(beta), hip.stream()),
+                      'dense_bn_bwd_small_pre')
+            return
         hip.check(self.L.dcahip_dense_bn_bwd_small(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), p(Hp), ldp, p(W), ldw,
                                                    B, K, H, int(batchnorm), float(n_total), int(act), p(gW), ldg, p(dbeta),
                                                    p(dHp), lddp, hip.stream()), 'dense_bn_bwd_small')

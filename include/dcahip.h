@@ -25,6 +25,11 @@
  *     copies, dca/train.py:91-98).  perm == NULL means identity (row r); cursor == NULL
  *     means offset 0.  `cursor` lives in device memory so a captured step graph can be
  *     replayed for every batch of an epoch.
+ *   - activation slopes: the backward entries of the hidden layers derive the slope of codes 0-11 from the
+ *     layer's OUTPUT h, and of the non-monotonic codes 12 (swish) and 13 (gelu) from its PRE-activation:
+ *     xhat + beta with batch norm (the `beta` argument of the *_pre entries, the `beta` field of
+ *     dcahip_stack_bwd_layer; NULL allowed for codes 0-11), Z in the `Hact` slot without (see
+ *     dcahip_bn_relu_apply for the code list).
  */
 #ifndef DCAHIP_H
 #define DCAHIP_H
@@ -296,10 +301,19 @@ int dcahip_transpose_rows(const float* src, long ld_src, const int* perm, const 
  *        moving = moving - (moving - batch) * (1 - momentum)   (biased variance).
  *     With entries == NULL it runs in INFERENCE mode on moving_mean / moving_var.
  *     `relu` is the activation code: 0 linear, 1 relu, 2 tanh, 3 sigmoid, 4 elu, 5 selu, 6 softplus,
- *     7 softsign, 8 LeakyReLU(0.3) (Activation(self.activation) / advanced activations,
- *     dca/network.py:132-135); the backward entry points take the same code as `act` and derive
- *     the slope from the forward OUTPUT h.  B == 0 is legal (only the moving statistics are
- *     updated): a data-parallel rank with an exhausted shard still joins the exchange.
+ *     7 softsign, 8 LeakyReLU(0.3), 10 hard_sigmoid, 11 exponential, 12 swish, 13 gelu (exact, erf)
+ *     (Activation(self.activation) / advanced activations, dca/network.py:132-135; 9 is PReLU, a
+ *     layer of its own behind code 0).  The backward entry points take the same code as `act`.
+ *     Codes 0-11 derive the slope from the forward OUTPUT h.  Codes 12 and 13 are not monotonic,
+ *     so h does not determine the slope: they derive it from the PRE-activation x instead --
+ *       with batch norm    x = xhat + beta[c]: the entries named *_pre take `beta` as an extra
+ *                          argument (and dcahip_stack_bwd_layer its `beta` field); for codes 12, 13
+ *                          it must be non-NULL (DCAHIP_EINVAL otherwise, so the entries without
+ *                          the suffix refuse them), for the other codes it is not read;
+ *       without batch norm x = Z, which the caller passes in the `Hact` slot of dcahip_relu_bwd /
+ *                          dcahip_dense_bn_bwd_small(batchnorm = 0) (the slope is its only use there).
+ *     B == 0 is legal (only the moving statistics are updated): a data-parallel rank with an
+ *     exhausted shard still joins the exchange.
  */
 int dcahip_col_moments_chunks(int B);
 int dcahip_col_moments(const float* Z, long ldz, int B, int H, float* part, void* stream);
@@ -334,6 +348,12 @@ int dcahip_dense_bn_bwd_small(const float* dH, long ldd, const float* Hact, long
                               const float* Hp, long ldp, const float* W, long ldw,
                               int B, int K, int H, int batchnorm, float n_total, int act,
                               float* gW, long ldg, float* dbeta, float* dHp, long lddp, void* stream);
+int dcahip_dense_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                                  const float* xhat, long ldx, const float* inv_std,
+                                  const float* Hp, long ldp, const float* W, long ldw,
+                                  int B, int K, int H, int batchnorm, float n_total, int act,
+                                  float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
+                                  void* stream);
 /* The hidden stack behind the first layer's product in ONE launch (every layer <= 64 units, B <= dcahip_bn_fused_max_rows()):
  * entry 0 with W == NULL normalises + activates its own Z (written by dcahip_sgemm), every entry with a kernel is
  * Dense -> BatchNormalization -> activation on the previous entry's Hout (entry 0 with a kernel reads Hin).  Same
@@ -368,6 +388,8 @@ typedef struct dcahip_stack_bwd_layer {
     float* gW; long ldg; float* dbeta;              /* OUT (gW unused for the first layer) */
     float* dH; long lddh;                           /* gradient w.r.t. the layer's output: IN for the last layer, scratch
                                                        (written, then read by the next launch) for the others */
+    const float* beta;                              /* the layer's batch-norm offset: read for codes 12, 13 only (see
+                                                       dcahip_bn_relu_apply), may be NULL otherwise */
 } dcahip_stack_bwd_layer;
 /* Both passes are a sequence of STEPS separated by a batch-wide dependency (the batch-norm statistics):
  *   forward  (n + 1 steps): 0 = partial statistics of the first layer's pre-activation; 1 + i = layer i (merge the
@@ -415,6 +437,9 @@ int dcahip_bn_relu_train_small(const float* Z, long ldz, int B, int H, const flo
 int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
                         const float* xhat, long ldx, const float* inv_std, float n_total,
                         int B, int H, float* dZ, long ldz, float* dbeta, int act, void* stream);
+int dcahip_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                            const float* xhat, long ldx, const float* inv_std, float n_total,
+                            int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
 
 /*
  * Backward of ReLU + batch norm.  mask = the forward output h (h > 0 <=> pre-ReLU > 0).
@@ -423,6 +448,7 @@ int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
  *  3. dcahip_bn_bwd_apply: dz = inv_std * (dy - S1/n - xhat * S2/n), dbeta = S1
  *     (sums: E entries [E][2][H] are added in order; n_total = global batch rows).
  * Without batch norm use dcahip_relu_bwd (dz = dh*[h>0]).
+ * The *_pre forms take `beta` as their last argument before `stream` (codes 12, 13: pre-activation = xhat + beta).
  */
 int dcahip_bn_bwd_sums(const float* dH, long ldd, const float* Hact, long ldh,
                        const float* xhat, long ldx, int B, int H, float* part, int act, void* stream);
@@ -430,6 +456,13 @@ int dcahip_bn_bwd_apply(const float* dH, long ldd, const float* Hact, long ldh,
                         const float* xhat, long ldx, const float* inv_std,
                         const float* sums, int E, float n_total, int B, int H,
                         float* dZ, long ldz, float* dbeta, int act, void* stream);
+int dcahip_bn_bwd_sums_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                           const float* xhat, long ldx, int B, int H, float* part, int act, const float* beta,
+                           void* stream);
+int dcahip_bn_bwd_apply_pre(const float* dH, long ldd, const float* Hact, long ldh,
+                            const float* xhat, long ldx, const float* inv_std,
+                            const float* sums, int E, float n_total, int B, int H,
+                            float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
 int dcahip_relu_bwd(const float* dH, long ldd, const float* Hact, long ldh, int B, int H,
                     float* dZ, long ldz, int act, void* stream);
 /* h = max(z, 0): Activation('relu') of a stack built with batchnorm=False (network.py:132-135). */
