@@ -70,3 +70,59 @@ def build(ops, Y, n, G, chunk_rows=16384):
         ovf_col = cols.to(torch.int32).contiguous()
         ovf_val = vals.to(torch.float32).contiguous()
     return CompactCounts(Yc, ldc, ovf_ptr, ovf_col, ovf_val)
+
+
+# ---------------------------------------------------------------------------------------------------- counts-resident mode
+class CsrVerdict:
+    """What build() learns from a full pass over the dense counts, learnt from the resident CSR instead (once per dataset,
+    kept on the CsrCounts): bad = some stored value is not a count, n_esc = stored counts >= 255, and the rows' escape
+    counts in descending order (their first B bound the overflow list of any tile of B rows)."""
+
+    def __init__(self, bad, n_esc, row_esc):
+        self.bad, self.n_esc, self.row_esc = bool(bad), int(n_esc), row_esc
+
+    def capacity(self, B):
+        return int(self.row_esc[:B].sum().item()) if self.n_esc else 0
+
+
+def csr_verdict(csr, chunk=1 << 27):
+    if getattr(csr, 'compact_verdict', None) is not None:
+        return csr.compact_verdict
+    bad, rows = False, []
+    for s in range(0, csr.nnz, chunk):
+        v = csr.values[s:s + chunk]
+        bad = bad or bool((~(v >= 0) | (v != torch.floor(v)) | (v > 16777216.0)).any().item())
+        at = (v >= 255).nonzero().reshape(-1)
+        if at.numel():
+            rows.append(torch.searchsorted(csr.indptr, at + s, right=True) - 1)
+    n_esc, row_esc = 0, None
+    if rows:
+        rows = torch.cat(rows)
+        n_esc = int(rows.numel())
+        per_row = torch.bincount(rows)
+        row_esc = torch.sort(per_row[per_row > 0], descending=True).values
+    csr.compact_verdict = CsrVerdict(bad, n_esc, row_esc)
+    return csr.compact_verdict
+
+
+def tile(ops, B, G, capacity, dev):
+    """The byte store of one minibatch (ops.csr_gather_compact fills it every step): storage row = tile row; the overflow
+    list holds `capacity` entries (None when no count of the dataset reaches 255)."""
+    ldc = ops.counts_compact_ld(G)
+    Yc = torch.zeros(B, ldc, dtype=torch.uint8, device=dev)
+    ovf_ptr = ovf_col = ovf_val = None
+    if capacity > 0:
+        ovf_ptr = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        ovf_col = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        ovf_val = torch.zeros(capacity, dtype=torch.float32, device=dev)
+    return CompactCounts(Yc, ldc, ovf_ptr, ovf_col, ovf_val)
+
+
+def tile_with_input(ops, cc, use_fac, do_log, mean, std):
+    """The tile with the description of the network input: fac is the tile's own [B] vector (the gather writes the rows'
+    factors there) and the per-cell table is remade from it every step (dcahip_enc0_lut on B cells)."""
+    B, dev = cc.Yc.shape[0], cc.Yc.device
+    fac = torch.ones(B, dtype=torch.float32, device=dev) if use_fac else None
+    t = CompactCounts(cc.Yc, cc.ldc, cc.ovf_ptr, cc.ovf_col, cc.ovf_val, fac, do_log, mean, std)
+    t.lutp = torch.zeros(B, ops.enc0_lut_entries(), 2, dtype=torch.int32, device=dev)
+    return t

@@ -25,6 +25,9 @@ Tested combinations (tests/, all against the same oracle numbers):
                                             store, bit for bit; dca() and predict_write files), test_counts_resident_cpu.py
                                             (the decision and the engine on the CPU oracle).  'auto' (default) keeps the dense
                                             form whenever its estimate fits into free device memory
+  counts_compact = True                     test_counts_compact_gpu.py (counts mode gathering a byte tile per step == the dense
+                                            engine WITH its byte store, bit for bit; the tile == the dense store's rows),
+                                            test_counts_compact_cpu.py (the field; the fallback of ops without the entry)
 Engine attributes a test sets directly instead (no knob): use_fused (K-HEADS vs separate kernels:
 test_fused_and_separate_heads_agree_stepwise, test_full_size_step_fused_equals_separate).
 """
@@ -64,6 +67,9 @@ class EngineConfig:
     # step gathering its minibatch (dcahip_csr_gather), 'auto' = dense whenever that fits into free device memory
     # (prep.choose_residency)
     resident: str = 'auto'                  # DCA_AMD_RESIDENT
+    # counts-resident mode: a training step gathers its minibatch as a byte tile (dcahip_csr_gather_compact) and runs the
+    # byte-store kernels of the dense form on it, instead of gathering fp32 X and Y tiles for the dense products
+    counts_compact: bool = False            # DCA_AMD_COUNTS_COMPACT
     # ---- measured constants (no environment variable; DESIGN.md holds the measurements)
     graph_steps: int = 8                    # consecutive training steps per hipGraph launch (fit loop and bench)
     sparse_dw_min: int = 512                # batch rows from which the first layer's weight gradient reads the byte store
@@ -73,7 +79,8 @@ class EngineConfig:
 
     _ENV = {'stack': 'DCA_AMD_STACK', 'bwd_chain': 'DCA_AMD_BWD_CHAIN', 'wide_planes': 'DCA_AMD_WIDE_PLANES', 'wide_h2': 'DCA_AMD_WIDE_H2',
             'dp_sharded_opt': 'DCA_AMD_DP_SHARDED_OPT', 'dp_graph': 'DCA_AMD_DP_GRAPH', 'device_prep': 'DCA_AMD_DEVICE_PREP',
-            'fused_write': 'DCA_AMD_FUSED_WRITE', 'dp_peer_exchange': 'DCA_AMD_DP_PEER', 'resident': 'DCA_AMD_RESIDENT'}
+            'fused_write': 'DCA_AMD_FUSED_WRITE', 'dp_peer_exchange': 'DCA_AMD_DP_PEER', 'resident': 'DCA_AMD_RESIDENT',
+            'counts_compact': 'DCA_AMD_COUNTS_COMPACT'}
 
     @classmethod
     def from_env(cls):

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "dcahip.h"
 
 namespace {
@@ -325,6 +326,209 @@ __global__ __launch_bounds__(256) void csr_gather_kernel(GatherArgs a) {
     if (bad) atomicAdd(a.status, bad);
 }
 
+// CSR gather into the byte-store format (the tile the byte-store kernels of K-HEADS and K-SPARSE read): Yc [B, ldc] bytes
+// as counts_compact_kernel makes them from csr_gather_kernel's fp32 tile, the tile's overflow list, sf / fac per tile row
+// and, optionally, the fp32 X tile of csr_gather_kernel.  Three launches: the gather (which leaves every row's number of
+// escapes in ovf_ptr[r + 1]), a one-workgroup prefix sum over them, and the list fill (one wave per row); a caller whose
+// dataset holds no count >= 255 passes no list and gets the first launch only.
+struct CompactGatherArgs {
+    GatherArgs g;                       // the CSR, the rows, the normalisation, X / sf_out / status (g.Y is not used)
+    unsigned char* Yc; long ldc;
+    int* ovf_ptr; int* ovf_col; float* ovf_val; int cap;
+    float* fac_out;
+};
+
+constexpr int kCsrSegB = 4 * kCsrSeg;   // columns per LDS segment of the byte-only form (the same 31.5 KiB)
+
+// the byte of one count, as counts_compact_kernel codes it: 0 .. 254, 255 = escape; not a count -> 0 and ++bad
+__device__ inline unsigned count_code(float x, int& bad) {
+    if (!(x >= 0.f) || x != floorf(x) || x > 16777216.f) { ++bad; return 0u; }
+    return x >= 255.f ? 255u : (unsigned)x;
+}
+
+__device__ inline int lane_rank64(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// One workgroup per destination row, LDS column segments as in csr_gather_kernel.  XV = 0: no X tile, the segment holds
+// the bytes themselves (four times the columns per segment); XV = 4 / 1: the segment holds the fp32 counts, X is written
+// from them as csr_gather_kernel writes it (V-float stores) and the bytes are coded on the way out.  16-byte stores of Yc.
+template <int XV>
+__global__ __launch_bounds__(256) void csr_gather_compact_kernel(CompactGatherArgs a) {
+    using T = typename std::conditional<XV != 0, float, unsigned char>::type;
+    constexpr int kSeg = XV ? kCsrSeg : kCsrSegB;
+    __shared__ __attribute__((aligned(16))) T seg[kSeg];
+    __shared__ int found, nesc;
+    const GatherArgs& g = a.g;
+    const int tid = threadIdx.x;
+    int bad = 0;
+    const long base = g.perm ? (long)*g.cursor : g.row0;
+    const long L = (XV && g.ldx > a.ldc) ? g.ldx : a.ldc;
+    for (int r = blockIdx.x; r < g.B; r += gridDim.x) {
+        const long row = g.perm ? (long)g.perm[base + r] : base + r;
+        const bool ok = row >= 0 && row < g.n;
+        long s = 0, e = 0;
+        if (ok) { s = g.indptr[row]; e = g.indptr[row + 1]; }
+        const long s0 = s < 0 ? 0 : (s > g.nnz ? g.nnz : s);
+        const long e0 = e < s0 ? s0 : (e > g.nnz ? g.nnz : e);
+        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
+        const float f = (g.fac && ok) ? g.fac[row] : 1.f;
+        float t0 = 0.f;
+        if (XV) {
+            if (g.fac) t0 = __fdiv_rn(t0, f);
+            if (g.do_log) t0 = log1pf(t0);
+        }
+        if (tid == 0) {
+            if (g.sf_out) g.sf_out[r] = (ok && g.sf) ? g.sf[row] : 0.f;
+            if (a.fac_out) a.fac_out[r] = f;
+            nesc = 0;                   // (the first segment's barrier orders it before the row's additions)
+        }
+        long p = s0;
+        unsigned char* crow = a.Yc + (long)r * a.ldc;
+        float* xrow = (XV && g.X) ? g.X + (long)r * g.ldx : nullptr;
+        for (long c0 = 0; c0 < L; c0 += kSeg) {
+            const int len = (int)(L - c0 < kSeg ? L - c0 : kSeg);
+            const long c1 = c0 + kSeg < L ? c0 + kSeg : (1L << 40);
+            if (XV == 1) {
+                for (int i = tid; i < len; i += 256) seg[i] = T(0);
+            } else {                    // len * sizeof(T) is a multiple of 16 (ldc % 16 == 0, ldx % 4 == 0)
+                const int nq = (int)((len * sizeof(T)) >> 4);
+                for (int i = tid; i < nq; i += 256) reinterpret_cast<uint4*>(seg)[i] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (tid == 0) found = 0;
+            __syncthreads();
+            int mine = 0, esc = 0;
+            for (long j = p + tid; j < e0; j += 256) {
+                const long c = g.indices[j];
+                if (c >= c1) break;
+                ++mine;
+                if (c < 0 || c >= g.G) { ++bad; continue; }
+                const long k = c - c0;
+                if (k >= 0 && k < len) {
+                    const float v = g.values[j];
+                    const unsigned code = count_code(v, bad);
+                    esc += code == 255u;
+                    if (XV) seg[k] = (T)v; else seg[k] = (T)code;
+                }
+            }
+            if (mine) atomicAdd(&found, mine);
+            if (esc) atomicAdd(&nesc, esc);
+            __syncthreads();
+            p += found;
+            if (p > e0) p = e0;
+            const int lb = (int)(a.ldc - c0 < len ? (a.ldc - c0 > 0 ? a.ldc - c0 : 0) : len);
+            if (XV == 0) {
+                for (int i = tid; i < (lb >> 4); i += 256)
+                    reinterpret_cast<uint4*>(crow + c0)[i] = reinterpret_cast<const uint4*>(seg)[i];
+            } else {
+                for (int i = tid; i < (lb >> 4); i += 256) {
+                    unsigned w[4];
+                    int skip = 0;       // (what is not a count was counted when it was scattered)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 y = reinterpret_cast<const float4*>(seg)[4 * i + q];
+                        w[q] = count_code(y.x, skip) | count_code(y.y, skip) << 8 | count_code(y.z, skip) << 16 |
+                               count_code(y.w, skip) << 24;
+                    }
+                    reinterpret_cast<uint4*>(crow + c0)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+            if (XV && xrow) {
+                const float* fs = reinterpret_cast<const float*>(seg);
+                const int lx = (int)(g.ldx - c0 < len ? (g.ldx - c0 > 0 ? g.ldx - c0 : 0) : len);
+                if (XV == 4) {
+                    for (int i = tid; i < (lx >> 2); i += 256) {
+                        const float4 y = reinterpret_cast<const float4*>(fs)[i];
+                        const long col = c0 + 4 * i;
+                        float4 x;
+                        x.x = gather_x(y.x, t0, f, g, col);
+                        x.y = gather_x(y.y, t0, f, g, col + 1);
+                        x.z = gather_x(y.z, t0, f, g, col + 2);
+                        x.w = gather_x(y.w, t0, f, g, col + 3);
+                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
+                    }
+                } else {
+                    for (int i = tid; i < lx; i += 256) xrow[c0 + i] = gather_x(fs[i], t0, f, g, c0 + i);
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (a.ovf_ptr) a.ovf_ptr[r + 1] = nesc;
+            else bad += nesc;           // an escape and no list to hold its value
+        }
+    }
+    if (bad) atomicAdd(g.status, bad);
+}
+
+// ovf_ptr[1 .. B] hold the rows' escape counts: -> ovf_ptr[0] = 0, ovf_ptr[r + 1] = their running sum, cut at the list's
+// capacity (what does not fit is counted, and no consumer is led beyond the list).  One workgroup, in place.
+__global__ __launch_bounds__(1024) void ovf_scan_kernel(int* ovf_ptr, int B, int cap, int* status) {
+    __shared__ long part[1024];
+    const int tid = threadIdx.x;
+    const int per = (B + 1023) / 1024;
+    const int i0 = min(B, tid * per), i1 = min(B, i0 + per);
+    long s = 0;
+    for (int i = i0; i < i1; ++i) { const int c = ovf_ptr[i + 1]; s += c > 0 ? c : 0; }
+    part[tid] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const long v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    long run = part[tid] - s;
+    for (int i = i0; i < i1; ++i) {
+        const int c = ovf_ptr[i + 1];
+        run += c > 0 ? c : 0;
+        ovf_ptr[i + 1] = (int)(run > cap ? cap : run);
+    }
+    if (tid == 0) ovf_ptr[0] = 0;
+    if (tid == 1023 && part[1023] > cap) {
+        const long over = part[1023] - cap;
+        atomicAdd(status, (int)(over > 0x3fffffffL ? 0x3fffffffL : over));
+    }
+}
+
+// The tile's overflow list: one wave per destination row walks the row in column order and stores its escapes at
+// ovf_ptr[r] ..., never beyond ovf_ptr[r + 1] (<= the capacity).  Rows without an escape leave at once.
+__global__ __launch_bounds__(256) void csr_gather_ovf_kernel(CompactGatherArgs a) {
+    const GatherArgs& g = a.g;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= g.B) return;
+    const int lo = a.ovf_ptr[r], hi = min(a.ovf_ptr[r + 1], a.cap);
+    if (lo < 0 || hi <= lo) return;
+    const long base = g.perm ? (long)*g.cursor : g.row0;
+    const long row = g.perm ? (long)g.perm[base + r] : base + r;
+    if (row < 0 || row >= g.n) return;
+    const long s = g.indptr[row], e = g.indptr[row + 1];
+    const long s0 = s < 0 ? 0 : (s > g.nnz ? g.nnz : s);
+    const long e0 = e < s0 ? s0 : (e > g.nnz ? g.nnz : e);
+    int pos = lo;
+    for (long j0 = s0; j0 < e0 && pos < hi; j0 += 64) {
+        const long j = j0 + lane;
+        bool is = false;
+        int c = 0;
+        float v = 0.f;
+        if (j < e0) {
+            c = g.indices[j];
+            if (c >= 0 && c < g.G) {
+                v = g.values[j];
+                int skip = 0;
+                is = count_code(v, skip) == 255u;
+            }
+        }
+        const unsigned long long m = __ballot(is);
+        if (is) {
+            const int q = pos + lane_rank64(m);
+            if (q < hi) { a.ovf_col[q] = c; a.ovf_val[q] = v; }
+        }
+        pos += __popcll(m);
+    }
+}
+
 // Per-gene partials of x and x*x over a resident CSR: one workgroup per row chunk (the chunks of col_pass_kernel), rows in
 // ascending order, so every gene receives its non-zero terms in the order col_pass_kernel adds them; the zeros it also adds
 // are +0.0 in fp64 and change nothing.  Within a row the columns are distinct (canonical rows), so the threads of the
@@ -469,6 +673,33 @@ extern "C" int dcahip_csr_gather(const long* indptr, const int* indices, const f
     const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
     if (vec) hipLaunchKernelGGL(csr_gather_kernel<4>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(csr_gather_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_gather_compact(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                         const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                                         const float* fac, int do_log, const float* mean, const float* stdv,
+                                         unsigned char* Yc, long ldc, int* ovf_ptr, int* ovf_col, float* ovf_val, int ovf_cap,
+                                         float* X, long ldx, float* sf_out, float* fac_out, int* status, void* stream) {
+    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || ldc < G || (ldc & 15) || !status || !Yc || !al16(Yc) || !indptr)
+        return DCAHIP_EINVAL;
+    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
+    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf) || (fac_out && !fac))
+        return DCAHIP_EINVAL;
+    if (ovf_ptr && (!ovf_col || !ovf_val || ovf_cap <= 0)) return DCAHIP_EINVAL;
+    if (B == 0) return 0;
+    CompactGatherArgs a{{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
+                         nullptr, 0, X, X ? ldx : 0, sf_out, status},
+                        Yc, ldc, ovf_ptr, ovf_col, ovf_val, ovf_ptr ? ovf_cap : 0, fac_out};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = B < 16384 ? B : 16384;
+    if (!X) hipLaunchKernelGGL(csr_gather_compact_kernel<0>, dim3(grid), dim3(256), 0, s, a);
+    else if (al16(X) && (ldx & 3) == 0) hipLaunchKernelGGL(csr_gather_compact_kernel<4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(csr_gather_compact_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    if (ovf_ptr) {
+        hipLaunchKernelGGL(ovf_scan_kernel, dim3(1), dim3(1024), 0, s, ovf_ptr, B, a.cap, status);
+        hipLaunchKernelGGL(csr_gather_ovf_kernel, dim3((B + 3) / 4), dim3(256), 0, s, a);
+    }
     return (int)hipGetLastError();
 }
 

@@ -378,6 +378,8 @@ class Engine:
         # compact counts (dca_amd/compact.py): K-HEADS reads its targets from the byte store (cc); with the input
         # normalisation known (cc_in) both first-layer products are built from it on the matrix pipe (K-SPARSE)
         self.cc = self.cc_in = None
+        self.cc_csr = None          # counts-resident mode gathering a byte tile per step (attach_counts)
+        self._tile_lut = False
         self.ws_enc0 = self.ws_enc0l = None
         self.ws_stack = None
         # K-STACK at throughput batches: 'steps' = one launch per batch-wide dependency (9 launches instead of 22 for
@@ -629,13 +631,19 @@ class Engine:
         self._data_scales()
         self.attach_compact(compact, norm)
 
-    def attach_counts(self, csr, sf, norm):
+    def attach_counts(self, csr, sf, norm, compact=None):
         """Counts-resident mode: the raw counts stay on the device as CSR (prep.CsrCounts, [n, G_out]) and every step gathers
         its minibatch from them -- Y, the input X = (f(y / fac) - mean) / std described by norm (dict(fac, do_log, mean, std),
         dca/io.py:99-109) and sf [n] -- into [Bmax, .] tiles (dcahip_csr_gather) before the kernels of the dense form run on
-        the tiles.  The byte store stays off (K-HEADS reads the fp32 tile, the first layer takes the dense products).  The
-        once-per-dataset values (tile order, K-HEADS' d_exp, the wide networks' scales) come from the CSR and equal the
-        dense form's."""
+        the tiles.  The once-per-dataset values (tile order, K-HEADS' d_exp, the wide networks' scales) come from the CSR
+        and equal the dense form's.
+        compact (None: EngineConfig.counts_compact; default off): a training step gathers its minibatch as a byte tile
+        instead (dcahip_csr_gather_compact: compact.tile, storage row = tile row) and runs the kernel sequence of the dense
+        engine with its byte store on it; which kernels read the tile is the dense engine's decision (attach_compact),
+        taken from the CSR.  Off, or where the dense engine would not use its byte store, or with ops that lack the entry:
+        K-HEADS reads the fp32 tile and the first layer takes the dense products.  Validation and inference gather the
+        fp32 tiles, and the byte tile beside them for the chunks whose first product the dense engine looks up from its
+        byte store (_lut_fwd: throughput chunks once training has made the tables)."""
         lay = self.lay
         if self.comm.world > 1:
             raise ValueError('dca_amd: counts-resident mode does not apply to data-parallel runs')
@@ -647,9 +655,20 @@ class Engine:
         self.n, self.ldx, self.ldy = csr.n, _r4(lay.G_in), lay.Gp
         self.gather_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.X = self.Y = self.sf = None
-        self._alloc_tiles()
         self.cc = self.cc_in = None
         self.cc_verdict = None
+        self.cc_csr = None                  # compact.CsrVerdict when the steps gather a byte tile
+        self._tile_lut = False              # a training step has made the tile's table (the dense form's "lutp is not None")
+        if compact is None:
+            compact = self.cfg.counts_compact
+        if compact and hasattr(self.ops, 'csr_gather_compact') and hasattr(self.ops, 'counts_compact'):
+            from . import compact as _compact
+            v = _compact.csr_verdict(csr)
+            # the dense engine's thresholds (attach_compact): not counts -> no byte store; more than one escape in 1e3
+            # counts -> fp32 targets
+            if not v.bad and v.n_esc <= 1e-3 * float(csr.n) * lay.G_out:
+                self.cc_csr = v
+        self._alloc_tiles()
         self._set_tile_order()
         self._data_scales()
 
@@ -663,6 +682,38 @@ class Engine:
             self.sf = torch.zeros(B, **f32)
             self.perm_id = torch.arange(B, dtype=torch.int32, device=self.dev)
             self.cursor0 = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        if self.cc_csr is not None and (self.cc is None or self.cc.Yc.shape[0] < B):
+            # the byte tile: B x r16(G) bytes, the overflow list of the B rows with the most escapes, and -- when the first
+            # layer reads it (one escape in 1e5 counts at most, a width its kernels take) -- 1 KB of table per tile cell
+            from . import compact as _compact
+            lay, ops, v, nm = self.lay, self.ops, self.cc_csr, self.norm_c
+            self.cc = _compact.tile(ops, B, lay.G_out, v.capacity(B), self.dev)
+            self.cc_in = None
+            if lay.hidden and v.n_esc <= 1e-5 * float(self.csr.n) * lay.G_out and ops.enc0_sparse_supported(lay.hidden[0]):
+                self.cc_in = _compact.tile_with_input(ops, self.cc, nm.get('fac') is not None, nm.get('do_log', False),
+                                                      nm.get('mean'), nm.get('std'))
+            self._sparse_workspaces()
+
+    def _gather_step(self, B):
+        """Counts-resident mode, the training step's rows: the byte tile (with the fp32 X tile only while a first-layer
+        product of this batch size still reads it), or the fp32 tiles."""
+        if self.cc is None:
+            return self._gather(B)
+        lut, sdw = self._lut_fwd(B, True), self._sparse_dw(B)
+        need_x = not self.lay.hidden or not (lut and sdw)
+        if self.ws_heads is None:           # the separate heads kernels read the fp32 counts
+            self._gather(B)
+            if not (lut or sdw):
+                return
+            need_x = False
+        nm, c = self.norm_c, self.cc
+        ci = self.cc_in if self.cc_in is not None else c
+        self.ops.csr_gather_compact(self.csr, self.perm, self.cursor, 0, B, self.sf_all, nm.get('fac'), nm.get('do_log', False),
+                                    nm.get('mean'), nm.get('std'), c.Yc, c.ldc, c.ovf_ptr, c.ovf_col, c.ovf_val,
+                                    self.X if need_x else None, self.ldx, self.sf, ci.fac, self.gather_status)
+        if lut or sdw:                      # the table of the tile's cells, from the factors the gather just wrote
+            self.ops.enc0_lut(ci.fac, ci.do_log, B, ci.lutp)
+            self._tile_lut = True
 
     def _gather(self, B, row0=None):
         """Counts-resident mode: the tile of B rows -- perm[cursor + r] (row0 None: the training step's rows, read on the
@@ -679,6 +730,12 @@ class Engine:
         if self.csr is None:
             return s
         self._gather(b, row0=s)
+        if self._lut_fwd(b, False):         # the inference forward the dense form looks up from its byte store
+            nm, c = self.norm_c, self.cc_in
+            self.ops.csr_gather_compact(self.csr, None, None, s, b, None, nm.get('fac'), nm.get('do_log', False),
+                                        nm.get('mean'), nm.get('std'), c.Yc, c.ldc, c.ovf_ptr, c.ovf_col, c.ovf_val,
+                                        None, 0, None, c.fac, self.gather_status)
+            self.ops.enc0_lut(c.fac, c.do_log, b, c.lutp)
         return 0
 
     def _csr_rows(self, r0, r1):
@@ -851,8 +908,9 @@ class Engine:
     def _lut_fwd(self, B, training):
         # inference takes this form only once the per-cell tables exist (training made them): a predict-only run keeps the
         # dense product instead of building 512 B of tables per cell for no gain at its chunk size
+        made = self.cc_in is not None and (self.cc_in.lutp is not None if self.csr is None else self._tile_lut)
         return (self.cc_in is not None and self.ws_enc0l is not None and B >= self.cfg.lut_fwd_min
-                and not (training and self.in_drop > 0.0) and (training or self.cc_in.lutp is not None))
+                and not (training and self.in_drop > 0.0) and (training or made))
 
     def _sparse_dw(self, B):
         return (self.cc_in is not None and self.ws_enc0 is not None and B >= self.sparse_dw_min and self.in_drop == 0.0)
@@ -1415,7 +1473,7 @@ class Engine:
         if B > 0:
             if self.csr is not None:
                 with self._t('csr_gather'):
-                    self._gather(B)
+                    self._gather_step(B)
             self._forward_backward(B, Bg, inv_n)
         else:
             self._empty_step()

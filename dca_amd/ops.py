@@ -498,6 +498,20 @@ class HipOps:
                                            p(Y), ldy, p(X), ldx if X is not None else 0, p(sf_out), p(status),
                                            hip.stream()), 'csr_gather')
 
+    def csr_gather_compact(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Yc, ldc, ovf_ptr, ovf_col, ovf_val,
+                           X, ldx, sf_out, fac_out, status):
+        """The minibatch tile of a resident CSR in the byte-store format (compact.CompactCounts of the tile's B rows): every
+        byte of Yc[:B, :ldc], the tile's overflow list (ovf_ptr [B + 1], ovf_col / ovf_val with the list's capacity as their
+        length; all None when the dataset holds no count >= 255), sf_out[:B], fac_out[:B] and, when X is given, csr_gather's
+        X[:B, :ldx].  status (int32 device word) += what had to be ignored or did not fit the list (include/dcahip.h)."""
+        p = hip.ptr
+        cap = int(ovf_col.numel()) if ovf_col is not None else 0
+        hip.check(self.L.dcahip_csr_gather_compact(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G,
+                                                   p(perm), p(cursor), int(row0), B, p(sf), p(fac), int(bool(do_log)), p(mean),
+                                                   p(std), p(Yc), ldc, p(ovf_ptr), p(ovf_col), p(ovf_val), cap, p(X),
+                                                   ldx if X is not None else 0, p(sf_out), p(fac_out), p(status),
+                                                   hip.stream()), 'csr_gather_compact')
+
     def csr_col_pass(self, csr, fac, do_log, col_part, status):
         """prep_col_pass's per-gene partials [R][2][Gp] (R = prep_chunks(n)) from a resident CSR, bit for bit."""
         p = hip.ptr

@@ -231,6 +231,7 @@ class CsrCounts:
         self.n, self.G = int(n), int(G)
         self.nnz = int(values.numel())
         self.device = indptr.device
+        self.compact_verdict = None         # compact.csr_verdict: whether / how these counts take a per-batch byte tile
 
     @property
     def nbytes(self):

@@ -552,6 +552,22 @@ int dcahip_csr_expand(const int* indptr, const int* indices, const float* values
  *                         f(0 / fac[row]) unscaled, as prep_col_pass leaves them.  sf_out[r] = sf[row] (sf_out may be
  *                         NULL).  Reads nothing from the host: capturable in a step's graph, valid on every replay.
  *                         One plain store per element, no atomics on the tiles.  B = 0 launches nothing.
+ *   dcahip_csr_gather_compact
+ *                         the same minibatch tile in the byte-store format of K-SPARSE (below), for the kernels that read
+ *                         the compact counts (dcahip_heads_fused_compact, dcahip_enc0_fwd_lut, dcahip_enc0_dw_sparse) with
+ *                         storage row = tile row.  Writes EVERY byte of Yc[r, 0 .. ldc), ldc = dcahip_counts_compact_ld(G):
+ *                         bit for bit what dcahip_counts_compact writes from dcahip_csr_gather's Y tile (counts 0 .. 254 as
+ *                         is, 255 = escape, pad columns 0; a value that is not a count is stored as 0 and counted into
+ *                         *status as dcahip_counts_compact counts it into status[0]).  The tile's overflow list: ovf_ptr
+ *                         [B + 1] (every word written; a prefix sum over the tile's rows, made on the stream), ovf_col /
+ *                         ovf_val [ovf_cap] = (column, count) of the counts >= 255 of row r at ovf_ptr[r] .. ovf_ptr[r + 1]
+ *                         - 1 in column order.  Entries beyond ovf_cap are not written, ovf_ptr never points beyond it, and
+ *                         their number is added to *status.  All three NULL (ovf_cap ignored): the caller knows that no
+ *                         count reaches 255; one met all the same is counted into *status.  sf_out[r] = sf[row],
+ *                         fac_out[r] = fac[row] (each may be NULL; fac_out needs fac; a row outside [0, n) gives 0 / 1).
+ *                         X (may be NULL): the fp32 input tile, bit for bit dcahip_csr_gather's.  The fp32 Y tile is never
+ *                         written.  Yc 16-byte aligned, ldc a multiple of 16.  Capturable, plain stores only, B = 0
+ *                         launches nothing.
  *   dcahip_csr_col_pass   the per-gene fp64 partials [R][2][Gp] of x = f(y / fac) and x*x that dcahip_prep_col_pass
  *                         produces for the dense rows, bit for bit (same row chunks R = dcahip_prep_chunks(n), same row
  *                         order; the zeros it skips add +0.0): dcahip_prep_col_finish takes them unchanged (gene totals
@@ -562,6 +578,11 @@ int dcahip_csr_gather(const long* indptr, const int* indices, const float* value
                       const int* perm, const long long* cursor, long row0, int B, const float* sf,
                       const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
                       float* X, long ldx, float* sf_out, int* status, void* stream);
+int dcahip_csr_gather_compact(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                              const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                              const float* fac, int do_log, const float* mean, const float* stdv,
+                              unsigned char* Yc, long ldc, int* ovf_ptr, int* ovf_col, float* ovf_val, int ovf_cap,
+                              float* X, long ldx, float* sf_out, float* fac_out, int* status, void* stream);
 int dcahip_csr_col_pass(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
                         const float* fac, int do_log, double* col_part, int* status, void* stream);
 int dcahip_csr_row_sums(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,

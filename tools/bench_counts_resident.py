@@ -1,12 +1,17 @@
 """Counts-resident mode on one MI355X ("Counts-resident mode").
 
   python tools/bench_counts_resident.py --out profiles/counts_resident_bench.json
-      1. ms/step at C3 (68 579 x 20 000, zinb-conddisp 64-32-64, B = 4096) in three forms: the default dense path, dense
-         without the byte store, counts mode -- the full training steps of the epoch replayed from hipGraphs;
-      2. dcahip_csr_gather alone (graph replays, event-timed) against the HBM store bound of its tiles;
+      1. ms/step at C3 (68 579 x 20 000, zinb-conddisp 64-32-64, B = 4096) in four forms: the default dense path, dense
+         without the byte store, counts mode, counts mode gathering a byte tile (EngineConfig.counts_compact) -- the full
+         training steps of the epoch replayed from hipGraphs, the forms INTERLEAVED over --rounds rounds (every round
+         times every form once; the result holds every round, the median and the spread (max - min) / median);
+      2. dcahip_csr_gather and the byte tile's gather (+ its per-step table) alone (graph replays, event-timed) against
+         the HBM store bound of what they write;
       3. 20 steps on a matrix that cannot be dense-resident (default 1 500 000 x 30 000, 2 000 non-zeros per cell,
-         synthesised on the device as CSR): ms/step and the peak device memory.
-  python tools/bench_counts_resident.py --gather-only        (the gather's replays alone: for rocprofv3 --kernel-trace --stats)
+         synthesised on the device as CSR): ms/step and the peak device memory (--big-compact: with the byte tile).
+  python tools/bench_counts_resident.py --gather-only [--compact]   (the gather's replays alone: for rocprofv3
+                                                                     --kernel-trace --stats)
+  --forms a,b: only these forms (a run of an older checkout beside this one: --forms counts).
 """
 import argparse
 import json
@@ -71,8 +76,8 @@ def csr_normalisation(ops, csr):
     return sf, prep.csr_norm(ops, csr, sf, True, True)
 
 
-def time_steps(eng, n_train, B, epochs):
-    """ms per full training step: the full steps of `epochs` epochs replayed from hipGraphs (8 steps per launch)."""
+def prepare_steps(eng, n_train, B):
+    """Reserves, shuffles and captures: the runner whose replays timed_steps times."""
     dev = eng.dev
     steps = n_train // B
     eng.reserve(B)
@@ -84,6 +89,16 @@ def time_steps(eng, n_train, B, epochs):
     eng.cursor.zero_()
     runner.run(B, B, [B], B, steps)                   # eager first step + captures
     torch.cuda.synchronize()
+    return runner, steps
+
+
+def time_steps(eng, n_train, B, epochs):
+    """ms per full training step: the full steps of `epochs` epochs replayed from hipGraphs (8 steps per launch)."""
+    runner, steps = prepare_steps(eng, n_train, B)
+    return timed_steps(eng, runner, B, steps, epochs)
+
+
+def timed_steps(eng, runner, B, steps, epochs):
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     for _ in range(epochs):
@@ -95,18 +110,20 @@ def time_steps(eng, n_train, B, epochs):
     return t0.elapsed_time(t1) / (epochs * steps), loss
 
 
-def gather_replays(ops, eng, B, reps):
-    """csr_gather of B perm rows, replayed from a graph: ms per gather."""
+def gather_replays(ops, eng, B, reps, step=False):
+    """csr_gather of B perm rows (step: what a training step gathers -- the byte tile and its table with counts_compact),
+    replayed from a graph: ms per gather."""
+    gather = eng._gather_step if step else eng._gather
     g = torch.cuda.CUDAGraph()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     eng.cursor.zero_()
-    eng._gather(B)
+    gather(B)
     torch.cuda.synchronize()
     with torch.cuda.stream(s):
         with torch.cuda.graph(g, stream=s):
             for _ in range(10):
-                eng._gather(B)
+                gather(B)
     torch.cuda.current_stream().wait_stream(s)
     g.replay()
     torch.cuda.synchronize()
@@ -131,6 +148,10 @@ def main():
     ap.add_argument('--big-steps', type=int, default=20)
     ap.add_argument('--gather-only', action='store_true')
     ap.add_argument('--skip-big', action='store_true')
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--forms', type=str, default='dense,dense_no_byte_store,counts,counts_compact')
+    ap.add_argument('--compact', action='store_true', help='--gather-only: the byte tile\'s gather')
+    ap.add_argument('--big-compact', action='store_true')
     ap.add_argument('--out', type=str, default='')
     args = ap.parse_args()
     dev = torch.device('cuda')
@@ -150,14 +171,14 @@ def main():
 
     if args.gather_only:
         eng = Engine('zinb-conddisp', G, G, (64, 32, 64), True, 0.0, ops=ops)
-        eng.attach_counts(csr, sf, norm)
+        eng.attach_counts(csr, sf, norm, compact=args.compact)
         eng.reserve(B)
         eng.perm = torch.randperm(n_train, device=dev).to(torch.int32)
-        print('gather %.4f ms' % gather_replays(ops, eng, B, 50))
+        print('gather %.4f ms' % gather_replays(ops, eng, B, 50, step=args.compact))
         return
 
-    forms = {}
-    for form in ('dense', 'dense_no_byte_store', 'counts'):
+    engs, runners = {}, {}
+    for form in args.forms.split(','):
         eng = Engine('zinb-conddisp', G, G, (64, 32, 64), True, 0.0, ops=ops)
         eng.init_params(0)
         if form == 'dense':
@@ -165,21 +186,41 @@ def main():
         elif form == 'dense_no_byte_store':
             eng.attach_device_data(X, Y, sf, norm=norm, compact=False)
         else:
-            eng.attach_counts(csr, sf, norm)
-        ms, loss = time_steps(eng, n_train, B, args.epochs)
-        forms[form] = dict(ms_per_step=round(ms, 4), mean_loss=loss)
-        if form == 'counts':
-            gms = gather_replays(ops, eng, B, 50)
-            tile_bytes = B * (eng.ldx + eng.ldy) * 4 + B * 4
-            res['csr_gather'] = dict(ms=round(gms, 4), tile_mb=tile_bytes / 1e6,
-                                     store_bound_ms=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3, 4),
-                                     fraction_of_store_bound=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3 / gms, 3))
+            eng.attach_counts(csr, sf, norm, compact=(form == 'counts_compact'))
+        engs[form] = eng
+        runners[form] = prepare_steps(eng, n_train, B)
+    rounds = {form: [] for form in engs}
+    loss = {}
+    for _ in range(args.rounds):                      # interleaved: every round times every form once
+        for form, eng in engs.items():
+            ms, loss[form] = timed_steps(eng, runners[form][0], B, runners[form][1], args.epochs)
+            rounds[form].append(round(ms, 4))
+    forms = {}
+    for form, ms in rounds.items():
+        med = sorted(ms)[len(ms) // 2]
+        forms[form] = dict(ms_per_step=med, rounds=ms, spread=round((max(ms) - min(ms)) / med, 4), mean_loss=loss[form])
         print(form, forms[form], flush=True)
-        del eng
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
+    if 'counts' in engs:
+        eng = engs['counts']
+        gms = gather_replays(ops, eng, B, 50)
+        tile_bytes = B * (eng.ldx + eng.ldy) * 4 + B * 4
+        res['csr_gather'] = dict(ms=round(gms, 4), tile_mb=tile_bytes / 1e6,
+                                 store_bound_ms=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3, 4),
+                                 fraction_of_store_bound=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3 / gms, 3))
+    if 'counts_compact' in engs:
+        eng = engs['counts_compact']
+        gms = gather_replays(ops, eng, B, 50, step=True)
+        tile_bytes = B * (eng.cc.ldc + 8) + (B * 1024 if eng.cc_in is not None else 0)
+        res['csr_gather_compact'] = dict(ms=round(gms, 4), tile_mb=tile_bytes / 1e6,
+                                         store_bound_ms=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3, 4),
+                                         fraction_of_store_bound=round(tile_bytes / (STORE_TBPS * 1e12) * 1e3 / gms, 3))
+    del engs, runners, eng
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
     res['c3'] = forms
-    res['counts_over_dense'] = round(forms['counts']['ms_per_step'] / forms['dense']['ms_per_step'], 3)
+    for form in ('counts', 'counts_compact'):
+        if form in forms and 'dense' in forms:
+            res[form + '_over_dense'] = round(forms[form]['ms_per_step'] / forms['dense']['ms_per_step'], 3)
     del X, Y, csr
     torch.cuda.empty_cache()
 
@@ -193,11 +234,11 @@ def main():
         setup = time.perf_counter() - t
         eng = Engine('zinb-conddisp', bG, bG, (64, 32, 64), True, 0.0, ops=ops)
         eng.init_params(0)
-        eng.attach_counts(big, bsf, bnorm)
+        eng.attach_counts(big, bsf, bnorm, compact=args.big_compact)
         steps = args.big_steps
         ms, loss = time_steps(eng, min(int(bn * 0.9), steps * B), B, 1)
         _, total = torch.cuda.mem_get_info()
-        res['beyond_dense'] = dict(cells=bn, genes=bG, nnz=big.nnz, csr_gb=round(big.nbytes / 1e9, 2),
+        res['beyond_dense'] = dict(counts_compact=bool(args.big_compact), cells=bn, genes=bG, nnz=big.nnz, csr_gb=round(big.nbytes / 1e9, 2),
                                    dense_estimate_gb=round(prep.dense_bytes(bn, bG) / 1e9, 1), steps=steps,
                                    ms_per_step=round(ms, 4), mean_loss=loss, setup_s=round(setup, 1),
                                    peak_gb=round(torch.cuda.max_memory_allocated() / 1e9, 2),
