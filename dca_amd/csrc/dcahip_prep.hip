@@ -14,6 +14,8 @@
 //   CSR expand        rows of a CSR chunk -> dense fp32 rows of the resident count matrix (the
 //                     upload of a sparse host matrix: index + value bytes cross PCIe, the zeros
 //                     are written here)
+//   CSR compress /    dense rows -> CSR, and the resident CSR without some rows / columns: the counts-resident form is
+//   subset            built and filtered here, not on the host
 // Arithmetic follows the host restatement operation by operation (fp32 division, fp32 log1p,
 // fp32 square accumulated in fp64) so that host and device inputs agree to the last ulp of
 // log1p.
@@ -591,7 +593,264 @@ __global__ __launch_bounds__(256) void csr_row_sums_kernel(const long* __restric
     if (bad) atomicAdd(status, bad);
 }
 
+// ---- building and filtering the resident CSR on the device (dcahip_csr_compress, dcahip_csr_subset) ----------------------
+// Both are an order-preserving stream compaction in two phases: every output row's number of entries (into ptr[row + 1]),
+// one workgroup that turns the counts into offsets (rowptr_scan_kernel), then one plain store per entry at its offset.
+
+// what scipy.sparse.csr_matrix(dense) stores: x != 0 -- not +0.0, not -0.0; a NaN and a subnormal are kept
+__device__ inline bool stored(float x) { return (__float_as_uint(x) << 1) != 0u; }
+
+// ptr[1 .. rows] hold the rows' entry counts: -> ptr[0] = base, ptr[r + 1] = base + their running sum.  One workgroup, in
+// place; a negative count (never written by the kernels here) counts as 0.
+__global__ __launch_bounds__(1024) void rowptr_scan_kernel(long* ptr, int rows, long base) {
+    __shared__ long part[1024];
+    const int tid = threadIdx.x;
+    const int per = (rows + 1023) / 1024;
+    const int i0 = min(rows, tid * per), i1 = min(rows, i0 + per);
+    long s = 0;
+    for (int i = i0; i < i1; ++i) { const long c = ptr[i + 1]; s += c > 0 ? c : 0; }
+    part[tid] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const long v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    long run = base + part[tid] - s;
+    for (int i = i0; i < i1; ++i) {
+        const long c = ptr[i + 1];
+        run += c > 0 ? c : 0;
+        ptr[i + 1] = run;
+    }
+    if (tid == 0) ptr[0] = base;
+}
+
+// the V columns a lane holds of dense row `row` from column g on: a 16-byte load (V = 4: the row is 16-byte aligned and
+// ld a multiple of 4, so the load stays inside the row's ld floats) whose columns >= G are masked; bit j of the result is
+// set when column g + j is stored
+template <int V>
+__device__ inline unsigned dense_mask(const float* row, int g, int G, float (&v)[4]) {
+    unsigned m = 0;
+    if (g < G) {
+        if (V == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(row + g);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m |= (g + j < G && stored(v[j])) ? (1u << j) : 0u;
+        } else {
+            v[0] = row[g];
+            m = stored(v[0]) ? 1u : 0u;
+        }
+    }
+    return m;
+}
+
+// phase 1 of csr_compress: one wave per dense row, ptr[r + 1] = the row's number of stored entries
+template <int V>
+__global__ __launch_bounds__(256) void compress_count_kernel(const float* __restrict__ X, long ld, int rows, int G, long* ptr) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * 256) >> 6;
+    for (int r = wave; r < rows; r += nwaves) {
+        const float* row = X + (long)r * ld;
+        int c = 0;
+        float v[4];
+        for (int g = lane * V; g < G; g += 64 * V) c += __popc(dense_mask<V>(row, g, G, v));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        if (lane == 0) ptr[r + 1] = c;
+    }
+}
+
+// phase 2 of csr_compress: one workgroup per dense row (grid-stride), tiles of 256 * V columns.  Lane l of wave w holds the
+// V consecutive columns c0 + (64 w + l) V ..; a ballot per component gives the number of stored entries in the lower lanes
+// (the sum of the V mbcnt's), the waves' totals cross in LDS (two alternating slots: one barrier per tile), and the entry
+// of column c lands at the row's offset + its rank: column order, one plain store each.  The offsets come from ptr (written
+// by rowptr_scan_kernel from the SAME data); a store is made only inside the row's own range and the arrays' capacity, and
+// what that refuses is counted into *status.
+template <int V>
+__global__ __launch_bounds__(256) void compress_store_kernel(const float* __restrict__ X, long ld, int rows, int G, long base,
+                                                             const long* __restrict__ ptr, int* __restrict__ indices,
+                                                             float* __restrict__ values, long cap, int* status) {
+    __shared__ int wtot[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int bad = 0;
+    int slot = 0;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+        const float* row = X + (long)r * ld;
+        long pos = ptr[r] - base;
+        long end = ptr[r + 1] - base;
+        if (end > cap) end = cap;
+        if (pos < 0) pos = end;                  // (never with the offsets rowptr_scan_kernel wrote: nothing is stored then)
+        for (int c0 = 0; c0 < G; c0 += 256 * V) {
+            const int g = c0 + tid * V;
+            float v[4];
+            const unsigned m = dense_mask<V>(row, g, G, v);
+            int below = 0, total = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const unsigned long long b = __ballot((m >> j) & 1u);
+                below += lane_rank64(b);
+                total += __popcll(b);
+            }
+            if (lane == 0) wtot[slot][w] = total;
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int t = wtot[slot][k];
+                before += k < w ? t : 0;
+                all += t;
+            }
+            slot ^= 1;
+            long q = pos + before + below;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if ((m >> j) & 1u) {
+                    if (q < end) { indices[q] = g + j; values[q] = v[j]; }
+                    else ++bad;
+                    ++q;
+                }
+            }
+            pos += all;
+        }
+    }
+    if (bad) atomicAdd(status, bad);
+}
+
+// dst[i] = the number of kept elements in front of i when mask[i] is set, else -1 (the renumbering of the kept columns /
+// rows of csr_subset).  One workgroup.  expect >= 0: the number of kept elements the caller sized its output for; another
+// total is counted into *status.
+__global__ __launch_bounds__(1024) void mask_scan_kernel(const unsigned char* __restrict__ mask, int len, int* dst, int expect,
+                                                         int* status) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x;
+    const int per = (len + 1023) / 1024;
+    const int i0 = min(len, tid * per), i1 = min(len, i0 + per);
+    int s = 0;
+    for (int i = i0; i < i1; ++i) s += mask[i] ? 1 : 0;
+    part[tid] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - s;
+    for (int i = i0; i < i1; ++i) {
+        const bool k = mask[i] != 0;
+        dst[i] = k ? run : -1;
+        run += k ? 1 : 0;
+    }
+    if (tid == 1023 && expect >= 0 && part[1023] != expect) atomicAdd(status, 1);
+}
+
+struct SubsetArgs {
+    const long* indptr; const int* indices; const float* values; long nnz; int n, G;
+    const int* rowmap; const int* colmap;      // source row -> output row, source column -> output column (-1: dropped;
+    int n_out;                                 // NULL: identity)
+    long* out_ptr; int* out_indices; float* out_values; long cap; int* status;
+};
+
+// One wave per source row (both phases of csr_subset).  STORE = false: out_ptr[dst + 1] = the number of the row's entries
+// whose column is kept.  STORE = true: those entries, in the order of the source row, at out_ptr[dst] ...: a ballot per 64
+// entries gives the ranks.  Malformed input is clamped and counted as in the other CSR kernels (once: in the count phase).
+template <bool STORE>
+__global__ __launch_bounds__(256) void csr_subset_kernel(SubsetArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * 256) >> 6;
+    int bad = 0;
+    for (int r = wave; r < a.n; r += nwaves) {
+        const int dst = a.rowmap ? a.rowmap[r] : r;
+        if (dst < 0) continue;
+        if (dst >= a.n_out) { if (!STORE && lane == 0) ++bad; continue; }
+        const long s = a.indptr[r], e = a.indptr[r + 1];
+        const long s0 = s < 0 ? 0 : (s > a.nnz ? a.nnz : s);
+        const long e0 = e < s0 ? s0 : (e > a.nnz ? a.nnz : e);
+        if (!STORE && lane == 0 && (s0 != s || e0 != e)) ++bad;
+        long pos = 0, end = 0;
+        if (STORE) {
+            pos = a.out_ptr[dst];
+            end = a.out_ptr[dst + 1];
+            if (end > a.cap) end = a.cap;
+            if (pos < 0) pos = end;
+        }
+        int cnt = 0;
+        for (long j0 = s0; j0 < e0; j0 += 64) {
+            const long j = j0 + lane;
+            int c = -1;
+            if (j < e0) {
+                const int cs = a.indices[j];
+                if (cs < 0 || cs >= a.G) { if (!STORE) ++bad; }
+                else c = a.colmap ? a.colmap[cs] : cs;
+            }
+            const unsigned long long m = __ballot(c >= 0);
+            if (STORE) {
+                if (c >= 0) {
+                    const long q = pos + lane_rank64(m);
+                    if (q < end) { a.out_indices[q] = c; a.out_values[q] = a.values[j]; }
+                    else ++bad;
+                }
+                pos += __popcll(m);
+            } else {
+                cnt += __popcll(m);
+            }
+        }
+        if (!STORE && lane == 0) a.out_ptr[dst + 1] = cnt;
+    }
+    if (bad) atomicAdd(a.status, bad);
+}
+
 }  // namespace
+
+extern "C" int dcahip_csr_compress(const float* X, long ld, int rows, int G, long base, long* indptr, int* indices,
+                                   float* values, long cap, int* status, void* stream) {
+    if (rows < 0 || G <= 0 || ld < G || base < 0 || cap < 0 || !status) return DCAHIP_EINVAL;
+    if ((long)rows * G > 0x7fffffffL) return DCAHIP_EINVAL;
+    if (rows == 0) return 0;
+    if (!X || !indptr || (cap > 0 && (!indices || !values))) return DCAHIP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int cgrid = (rows + 3) / 4;
+    if (cgrid > 4096) cgrid = 4096;
+    const int grid = rows < 16384 ? rows : 16384;
+    if (al16(X) && (ld & 3) == 0) {
+        hipLaunchKernelGGL(compress_count_kernel<4>, dim3(cgrid), dim3(256), 0, s, X, ld, rows, G, indptr);
+        hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, indptr, rows, base);
+        hipLaunchKernelGGL(compress_store_kernel<4>, dim3(grid), dim3(256), 0, s, X, ld, rows, G, base, indptr, indices, values,
+                           cap, status);
+    } else {
+        hipLaunchKernelGGL(compress_count_kernel<1>, dim3(cgrid), dim3(256), 0, s, X, ld, rows, G, indptr);
+        hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, indptr, rows, base);
+        hipLaunchKernelGGL(compress_store_kernel<1>, dim3(grid), dim3(256), 0, s, X, ld, rows, G, base, indptr, indices, values,
+                           cap, status);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_subset(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                 const unsigned char* row_keep, const unsigned char* col_keep, int n_out, long* out_indptr,
+                                 int* out_indices, float* out_values, long cap, int* ws, int* status, void* stream) {
+    if (n < 0 || G <= 0 || nnz < 0 || n_out < 0 || n_out > n || cap < 0 || !status || !indptr || !out_indptr)
+        return DCAHIP_EINVAL;
+    if ((nnz > 0 && (!indices || !values)) || (cap > 0 && (!out_indices || !out_values))) return DCAHIP_EINVAL;
+    if ((row_keep || col_keep) && !ws) return DCAHIP_EINVAL;
+    if (!row_keep && n_out != n) return DCAHIP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int* rowmap = row_keep ? ws : nullptr;
+    int* colmap = col_keep ? ws + n : nullptr;
+    if (row_keep && n > 0) hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(1024), 0, s, row_keep, n, rowmap, n_out, status);
+    if (col_keep) hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(1024), 0, s, col_keep, G, colmap, -1, status);
+    SubsetArgs a{indptr, indices, values, nnz, n, G, rowmap, colmap, n_out, out_indptr, out_indices, out_values, cap, status};
+    int grid = (n + 3) / 4;
+    if (grid > 4096) grid = 4096;
+    if (n_out > 0) hipLaunchKernelGGL(csr_subset_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, out_indptr, n_out, 0L);
+    if (n_out > 0) hipLaunchKernelGGL(csr_subset_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
 
 extern "C" int dcahip_csr_expand(const int* indptr, const int* indices, const float* values, long nnz, int rows, int G,
                                  float* Y, long ldy, int* status, void* stream) {

@@ -162,6 +162,10 @@ _SIGNATURES = {
     'dcahip_prep_col_finish': (_c.c_int, [_f64p, _c.c_int, _c.c_int, _c.c_double, _f32p, _f32p, _f32p, _vp]),
     'dcahip_prep_scale': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _vp]),
     'dcahip_csr_expand': (_c.c_int, [_i32p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _i32p, _vp]),
+    'dcahip_csr_compress': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_long, _i64p, _i32p, _f32p, _c.c_long, _i32p,
+                                       _vp]),
+    'dcahip_csr_subset': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _i64p, _i32p,
+                                     _f32p, _c.c_long, _i32p, _i32p, _vp]),
     'dcahip_csr_gather': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
                                      _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _i32p,
                                      _vp]),

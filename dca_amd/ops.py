@@ -488,6 +488,26 @@ class HipOps:
         hip.check(self.L.dcahip_csr_expand(p(indptr), p(indices), p(values), nnz, rows, G, p(Y), ldy, p(status),
                                            hip.stream()), 'csr_expand')
 
+    def csr_compress(self, X, ld, rows, G, base, indptr, indices, values, status):
+        """Dense fp32 rows X[:rows, :G] (row stride ld) -> their CSR: indptr[:rows + 1] (int64, from `base` on), the entries
+        from position 0 of indices (int32) / values (fp32), whose common length is the capacity; status (int32 device word)
+        += the entries that did not fit (include/dcahip.h)."""
+        p = hip.ptr
+        cap = min(int(indices.numel()), int(values.numel()))
+        hip.check(self.L.dcahip_csr_compress(p(X), ld, rows, G, int(base), p(indptr), p(indices), p(values), cap, p(status),
+                                             hip.stream()), 'csr_compress')
+
+    def csr_subset(self, csr, row_keep, col_keep, n_out, out_indptr, out_indices, out_values, ws, status):
+        """A resident CSR (prep.CsrCounts) without the rows / columns whose byte in row_keep [n] / col_keep [G] (uint8 or
+        bool device tensors, None: keep all) is 0 -> out_indptr[:n_out + 1] (int64, from 0), the kept entries in out_indices /
+        out_values (their common length is the capacity), columns renumbered; ws: n + G int32 of scratch; status (int32
+        device word) += what had to be ignored or did not fit, or that row_keep does not keep n_out rows (include/dcahip.h)."""
+        p = hip.ptr
+        cap = min(int(out_indices.numel()), int(out_values.numel()))
+        hip.check(self.L.dcahip_csr_subset(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G, p(row_keep),
+                                           p(col_keep), int(n_out), p(out_indptr), p(out_indices), p(out_values), cap, p(ws),
+                                           p(status), hip.stream()), 'csr_subset')
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];

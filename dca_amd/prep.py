@@ -291,7 +291,9 @@ def device_budget(dev):
 
 
 def _nnz(X):
-    return int(X.nnz) if sp_sparse.issparse(X) else int(np.count_nonzero(np.asarray(X)))
+    """The stored entries of a sparse host matrix; 0 for a dense one (choose_residency does not use the counts' size, and
+    counting the non-zeros of a dense matrix is a pass over all of it)."""
+    return int(X.nnz) if sp_sparse.issparse(X) else 0
 
 
 def residency(X, dev, ops, mode=None):
@@ -321,11 +323,86 @@ def residency(X, dev, ops, mode=None):
     return choose_residency(mode, need, 0, 0, world=world)
 
 
-def upload_csr(X, dev, ops, nnz_cap=1 << 22, row_cap=1 << 14):
-    """Host matrix [n, G] (scipy.sparse; a dense one is compressed on the host) -> a CsrCounts on `dev`, staged through the
-    page-locked slots of upload_sparse (pack_csr_chunk: canonical rows, fp32 values) without expanding it.  A malformed
-    matrix raises ValueError."""
+def compress_capable(X, dev, ops):
+    """Whether the dense host matrix X becomes a CsrCounts on the device (upload_csr's device route): a GPU, ops with
+    csr_compress, a 2-d numpy array of a dtype for which the device route gives the host route's arrays bit for bit.  The
+    kernel stores what is non-zero AFTER the conversion to fp32, the host route what is non-zero before it: the same for
+    float32, integers and booleans (a non-zero integer never rounds to 0.0f).  A non-zero float64 can round to 0.0f, which
+    the host route keeps as a stored zero: float64 and every other dtype stay on the host route (float16 too: scipy.sparse
+    refuses it, so there are no host arrays to equal and the refusal stays)."""
+    if sp_sparse.issparse(X) or dev.type != 'cuda' or ops is None or not hasattr(ops, 'csr_compress'):
+        return False
+    if not isinstance(X, np.ndarray) or X.ndim != 2 or X.shape[0] == 0 or X.shape[1] == 0:
+        return False
+    return X.dtype == np.float32 or X.dtype.kind in 'biu'
+
+
+def _compress_dense(X, dev, ops, chunk_rows):
+    """upload_csr's device route (see there)."""
     n, G = X.shape
+    ld = _r4(G)
+    rows_cap = max(1, min(int(chunk_rows), n, (2 ** 31 - 1) // G))
+    stage = _stage_buffers(rows_cap, G)
+    dense = torch.empty(rows_cap, ld, dtype=torch.float32, device=dev)
+    sidx = torch.empty(rows_cap * G, dtype=torch.int32, device=dev)
+    sval = torch.empty(rows_cap * G, dtype=torch.float32, device=dev)
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ends = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in range(2)]
+    events = [torch.cuda.Event() for _ in range(2)]
+    idx_parts, val_parts = [], []
+
+    def collect(slot, base):
+        # the chunk compressed last: its end offset (a read-back of one word), its entries out of the scratch
+        events[slot].synchronize()
+        end = int(ends[slot].item())
+        idx_parts.append(sidx[:end - base].clone())
+        val_parts.append(sval[:end - base].clone())
+        return end
+
+    base, prev = 0, None
+    for ci, s in enumerate(range(0, n, rows_cap)):
+        e = min(n, s + rows_cap)
+        slot = ci % 2
+        # (the copy that last read this page-locked slot belongs to chunk ci - 2, whose event collect() has waited for)
+        _pack(stage[slot][:e - s].numpy(), X[s:e])
+        dense[:e - s, :G].copy_(stage[slot][:e - s], non_blocking=True)
+        if prev is not None:
+            base = collect(prev, base)          # the device works on chunk ci - 1 and the copy of chunk ci meanwhile
+        ops.csr_compress(dense, ld, e - s, G, base, indptr[s:e + 1], sidx, sval, status)
+        ends[slot].copy_(indptr[e:e + 1], non_blocking=True)
+        events[slot].record()
+        prev = slot
+    total = collect(prev, base)
+    if int(status.item()):
+        raise RuntimeError('dca_amd: csr_compress left %d entries unwritten' % int(status.item()))
+    del dense, sidx, sval
+    indices = idx_parts[0] if len(idx_parts) == 1 else torch.cat(idx_parts)
+    del idx_parts
+    values = val_parts[0] if len(val_parts) == 1 else torch.cat(val_parts)
+    del val_parts
+    assert indices.numel() == total
+    return CsrCounts(indptr, indices, values, n, G)
+
+
+def upload_csr(X, dev, ops, nnz_cap=1 << 22, row_cap=1 << 14, dense_rows=2048, device_compress=True):
+    """Host matrix [n, G] -> a CsrCounts on `dev`.
+
+    A scipy.sparse matrix is staged through the page-locked slots of upload_sparse (pack_csr_chunk: canonical rows, fp32
+    values) without expanding it.  A malformed matrix raises ValueError.
+
+    A dense matrix is compressed ON THE DEVICE when compress_capable() says so (device_compress=False: never): chunks of
+    dense_rows rows cross PCIe through the page-locked double slots of the dense upload (_stage_buffers; host threads pack
+    chunk i + 1 while chunk i is copied and compressed), dcahip_csr_compress writes the chunk's row pointer into the final
+    indptr and its entries into a chunk-sized scratch, and one word read back per chunk tells how many there were; the
+    pieces are joined on the device at the end.  The arrays equal the host route's bit for bit.  Peak device memory of this
+    route: the larger of (the final CSR + the chunk scratch) and 1.5 x the final CSR, where the chunk scratch is the dense
+    chunk and room for all of its elements as entries, dense_rows x G x 12 bytes (0.49 GB at 2 048 x 20 000); the dense
+    matrix is never allocated.  Any other dense matrix (no GPU, ops without the kernel, float64, float16, ...) is compressed by
+    scipy on the host and takes the sparse route."""
+    n, G = X.shape
+    if device_compress and compress_capable(X, dev, ops):
+        return _compress_dense(X, dev, ops, min(int(dense_rows), int(row_cap)))
     if not sp_sparse.issparse(X):
         X = sp_sparse.csr_matrix(np.asarray(X))
     if X.format != 'csr':
@@ -397,6 +474,32 @@ def csr_cell_counts(ops, csr):
     out = torch.zeros(csr.n, dtype=torch.float32, device=csr.device)
     ops.csr_row_sums(csr, out, torch.zeros(1, dtype=torch.int32, device=csr.device))
     return out
+
+
+def subset_csr(ops, csr, rows=None, cols=None):
+    """The resident CSR without the rows / columns that the boolean host masks `rows` [n] / `cols` [G] drop (None: keep
+    all) -> a new CsrCounts, bit for bit upload_csr of the host matrix subset the same way (X[rows][:, cols]); the entries
+    never leave the device (dcahip_csr_subset).  Device memory: the result is written into arrays of csr's size and cut to
+    its own when entries were dropped."""
+    dev = csr.device
+    n_out = csr.n if rows is None else int(np.count_nonzero(rows))
+    G_out = csr.G if cols is None else int(np.count_nonzero(cols))
+    mask = lambda m, k: None if m is None else torch.from_numpy(                                  # noqa: E731
+        np.ascontiguousarray(np.asarray(m).reshape(k) != 0).view(np.uint8)).to(dev)
+    rk, ck = mask(rows, csr.n), mask(cols, csr.G)
+    indptr = torch.zeros(n_out + 1, dtype=torch.int64, device=dev)
+    indices = torch.empty(csr.nnz, dtype=torch.int32, device=dev)
+    values = torch.empty(csr.nnz, dtype=torch.float32, device=dev)
+    ws = torch.empty(csr.n + csr.G, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ops.csr_subset(csr, rk, ck, n_out, indptr, indices, values, ws, status)
+    total = int(indptr[n_out].item())
+    bad = int(status.item())
+    if bad:
+        raise ValueError('dca_amd: malformed resident CSR: %d entries / rows outside the matrix' % bad)
+    if total < csr.nnz:
+        indices, values = indices[:total].clone(), values[:total].clone()
+    return CsrCounts(indptr, indices, values, n_out, G_out)
 
 
 def csr_norm(ops, csr, fac, logtrans_input, normalize_input):
@@ -632,12 +735,19 @@ def normalize_device(adata, filter_min_counts=True, size_factors=True, normalize
 
 
 def _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, logtrans_input, ops, dev, to_host, csr):
-    """normalize_device in the counts-resident form: the statistics from the CSR kernels, each filter a subset of the host
-    matrix followed by a new upload of it; the host AnnData ends up exactly as the dense form leaves it."""
+    """normalize_device in the counts-resident form: the statistics from the CSR kernels; each filter subsets the host
+    AnnData as the dense form does and the RESIDENT CSR with it (subset_csr) -- or, with ops that lack csr_subset, uploads
+    the subset host matrix again; the host AnnData ends up exactly as the dense form leaves it."""
     from . import io as _io
     n, G = adata.X.shape
     if csr is None:
         csr = upload_csr(adata.X, dev, ops)
+
+    def filtered(csr, rows=None, cols=None):
+        # (the host AnnData has been subset already)
+        if hasattr(ops, 'csr_subset'):
+            return subset_csr(ops, csr, rows=rows, cols=cols)
+        return upload_csr(adata.X, dev, ops)
     if filter_min_counts:                                         # io.py:90-92
         gc = csr_gene_counts(ops, csr).cpu().numpy()
         adata.var['n_counts'] = gc
@@ -645,14 +755,14 @@ def _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, l
         if not keep.all():
             _io._subset(adata, cols=keep)
             G = int(keep.sum())
-            csr = upload_csr(adata.X, dev, ops)
+            csr = filtered(csr, cols=keep)
         cc = csr_cell_counts(ops, csr).cpu().numpy()
         adata.obs['n_counts'] = cc
         keep = cc >= 1
         if not keep.all():
             _io._subset(adata, rows=keep)
             n = int(keep.sum())
-            csr = upload_csr(adata.X, dev, ops)
+            csr = filtered(csr, rows=keep)
 
     if size_factors or normalize_input or logtrans_input:         # io.py:94-97
         adata.raw = adata.copy()
@@ -668,7 +778,7 @@ def _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, l
             _io._subset(adata, rows=keep)
             counts = counts[keep]
             n = int(keep.sum())
-            csr = upload_csr(adata.X, dev, ops)
+            csr = filtered(csr, rows=keep)
         after = np.median(counts)
         c2 = counts + (counts == 0)
         fac = (c2 / after).astype(np.float32)

@@ -537,6 +537,34 @@ int dcahip_csr_expand(const int* indptr, const int* indices, const float* values
                       float* Y, long ldy, int* status, void* stream);
 
 /*
+ * CSR compress: dense fp32 rows (a row chunk of a dense host count matrix, copied to the device as it is) -> their CSR,
+ * in place of the host's scipy.sparse.csr_matrix(dense) on what sc.read hands over (dca/io.py:58-59) when the counts go
+ * counts-resident (below).  An entry is stored when x != 0, as scipy decides it: -0.0 is dropped, a NaN is kept.
+ *   X [rows, ld] fp32 (ld >= G; columns G .. ld are never interpreted).  indptr [rows + 1] int64: every word written,
+ *   indptr[0] = base, indptr[r + 1] = base + the entries of rows 0 .. r (base: the entries of the matrix in front of this
+ *   chunk, so that a matrix beyond 2^31 entries is built chunk by chunk).  indices (int32) / values (fp32) [cap]: the
+ *   chunk's entries from position 0 on (position = indptr - base), rows in order, columns ascending, the value's bits
+ *   unchanged.  cap >= rows * G always suffices; entries beyond cap are not written and counted into *status (one int32,
+ *   zeroed by the caller).  Three launches on the stream (counts per row, their prefix sum, the stores): one plain store
+ *   per entry, no atomics on the arrays, deterministic; nothing outside the buffers is read or written.  rows = 0 launches
+ *   nothing.  ld < G, G <= 0, base < 0 or rows * G > INT32_MAX: DCAHIP_EINVAL.
+ *
+ * CSR subset: a resident CSR (next comment) without the rows / columns whose keep byte is 0, in place of a second upload
+ * after scanpy's filter_genes / filter_cells (dca/io.py:90-92) and normalize_per_cell's drop of empty cells (:99-101).
+ *   row_keep [n], col_keep [G] bytes (either may be NULL: keep all).  out_indptr [n_out + 1] int64 from 0, out_indices /
+ *   out_values [cap]: the kept rows in order, their kept entries in order, columns renumbered by the prefix sum of
+ *   col_keep (computed here).  n_out: the number of kept rows the caller sized out_indptr for (n when row_keep is NULL,
+ *   else DCAHIP_EINVAL); if row_keep keeps another number, *status is raised and the result is not to be used.  cap >= nnz
+ *   always suffices; what does not fit is counted into *status, as is malformed input (clamped as in the entries below).
+ *   ws: n + G int32 of scratch (may be NULL when both masks are).  Plain stores only, deterministic, on the stream.
+ */
+int dcahip_csr_compress(const float* X, long ld, int rows, int G, long base, long* indptr, int* indices, float* values,
+                        long cap, int* status, void* stream);
+int dcahip_csr_subset(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                      const unsigned char* row_keep, const unsigned char* col_keep, int n_out, long* out_indptr,
+                      int* out_indices, float* out_values, long cap, int* ws, int* status, void* stream);
+
+/*
  * Resident CSR (counts-resident mode): the raw counts stay on the device as CSR -- indptr [n + 1] int64 (absolute offsets),
  * indices int32, values fp32, canonical rows -- and every step builds only its own minibatch.  The preprocessing is that
  * of dca/io.py:88-111 (as dcahip_prep_*), the per-batch rows those of the Keras feed, dca/train.py:83-98.  All three
