@@ -79,7 +79,9 @@ __global__ __launch_bounds__(256) void l1l2_seg_kernel(const float* w, float* g,
     double acc = 0.0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float x = w[i];
-        if (g) g[i] += l1 * (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f)) + 2.f * l2 * x;
+        // the three-term sum in fp64, rounded once: within one fp32 ulp of its larger term also where the penalty's
+        // gradient and g are of one size (two fp32 roundings reach 1.2 ulp there)
+        if (g) g[i] = (float)((double)g[i] + ((double)l1 * (x > 0.f ? 1.0 : (x < 0.f ? -1.0 : 0.0)) + 2.0 * (double)l2 * (double)x));
         acc += (double)(l1 * fabsf(x)) + (double)(l2 * x * x);
     }
 #pragma unroll

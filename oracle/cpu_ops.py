@@ -365,7 +365,8 @@ class CpuRefOps:
         counter[0] += v
 
     def reg_desc(self, segs):
-        return [(int(a), int(b), float(l1), float(l2)) for a, b, l1, l2 in segs]
+        # (the coefficients of dcahip_reg_desc are fp32)
+        return [(int(a), int(b), float(np.float32(l1)), float(np.float32(l2))) for a, b, l1, l2 in segs]
 
     def l1l2_workspace_doubles(self):
         return 16
@@ -431,3 +432,8 @@ class CpuRefOps:
         m = rho * mv.astype(np.float64) + (1 - rho) * gv * gv
         mv[:] = m
         wv[:] = wv - float(lr[0].item()) * gv / (np.sqrt(m) + eps)
+
+    def rmsprop_clip_end(self, w, g, ms, n, lr, rho, eps, clip, loss, weight, hist, rows_per_slot, acc, cursor, advance):
+        """Contract of dcahip_rmsprop_clip_end: rmsprop_clip, then step_end on the same words."""
+        self.rmsprop_clip(w, g, ms, n, lr, rho, eps, clip)
+        self.step_end(loss, weight, hist, rows_per_slot, acc, cursor, advance)

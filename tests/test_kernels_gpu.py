@@ -124,13 +124,17 @@ def test_zinb_nll_vs_oracle(ops, flags, B, G, edge):
 
 
 @pytest.mark.parametrize('flags', [1, 3, 0])
-@pytest.mark.parametrize('B,G,dense', [(2500, 1000, False), (2500, 1000, True), (4099, 520, False)])
+@pytest.mark.parametrize('B,G,dense', [(2500, 1000, False), (2500, 1000, True), (4099, 520, False), (700, 2050, False)])
 def test_zinb_nll_row_pairs_and_planes(ops, flags, B, G, dense):
     """The training kernel takes two batch rows per iteration and keeps both in registers until the non-zero elements are
     evaluated (zinb_nll_rows_kernel): batches deep enough that a workgroup walks several row pairs, the second row of the
     last pair missing for some workgroups and present for others; `dense` makes EVERY element non-zero (the queue at its
-    capacity of 2 x 256 entries per wave).  The plane-output entry point must hold the same numbers as three bf16 pieces."""
+    capacity of 2 x 256 entries per wave).  The plane-output entry point must hold the same numbers as three bf16 pieces.
+    (700, 2050): three gene segments, the last with a single active lane, a partial last quad, rows 682..699 the second row
+    of a pair for some workgroups only -- and the counts / size factors gathered through perm / cursor from a storage
+    whose other rows hold NaN."""
     has_pi, cdisp = bool(flags & 1), bool(flags & 2)
+    gather = (B, G) == (700, 2050)
     am, ad, ap, y, sf = _heads(B, G, 3 + B, False)
     if dense:
         y = y + 1.0
@@ -148,11 +152,19 @@ def test_zinb_nll_row_pairs_and_planes(ops, flags, B, G, dense):
     A = np.zeros((B, lda)); A[:, :G] = am; A[:, Gp:Gp + G] = ad; A[:, 2 * Gp:2 * Gp + G] = ap
     dA = dev(A); dD = torch.full((B, lda), 7.0, device='cuda')
     dY, dsf, dtw = dev(pad_cols(y, Gp)), dev(sf), dev(tw)
+    dperm = dcur = None
+    if gather:
+        n_store, cur = B + 7, 3
+        perm = rng.permutation(n_store)[:B + 3].astype(np.int32)
+        Yst = np.full((n_store, Gp), np.nan); Yst[perm[cur:cur + B]] = pad_cols(y, Gp)
+        sfst = np.full(n_store, np.nan); sfst[perm[cur:cur + B]] = sf
+        dY, dsf, dperm = dev(Yst), dev(sfst), torch.as_tensor(perm).cuda()
+        dcur = torch.tensor([cur], dtype=torch.int64, device='cuda')
     part = torch.zeros(ops.max_partials, dtype=torch.float64, device='cuda')
     a_mean, a_disp, a_pi = dA[:, 0:], dA[:, Gp:], dA[:, 2 * Gp:]
     d_mean, d_disp, d_pi = dD[:, 0:], dD[:, Gp:], dD[:, 2 * Gp:]
     n = ops.zinb_nll(a_mean, None if cdisp else a_disp, a_pi if has_pi else None, lda, dtw if cdisp else None, dY, Gp, dsf,
-                     None, None, B, G, ridge, inv_n, flags, d_mean, d_disp, d_pi if has_pi else None, lda, part)
+                     dperm, dcur, B, G, ridge, inv_n, flags, d_mean, d_disp, d_pi if has_pi else None, lda, part)
     loss = torch.zeros(1, device='cuda')
     ops.loss_finalize(part, n, inv_n, loss)
     torch.cuda.synchronize()
@@ -175,7 +187,7 @@ def test_zinb_nll_row_pairs_and_planes(ops, flags, B, G, dense):
     Dth = torch.full((B, Gp), 7.0, device='cuda')
     part.zero_()
     n2 = ops.zinb_nll_planes(a_mean, None if cdisp else a_disp, a_pi if has_pi else None, lda, dtw if cdisp else None, dY, Gp, dsf,
-                             None, None, B, G, ridge, inv_n, flags, P, 0, 0 if cdisp else Gp, 2 * Gp if has_pi else 0,
+                             dperm, dcur, B, G, ridge, inv_n, flags, P, 0, 0 if cdisp else Gp, 2 * Gp if has_pi else 0,
                              Dth if cdisp else None, Gp, part)
     ops.loss_finalize(part, n2, inv_n, loss)
     torch.cuda.synchronize()
@@ -185,6 +197,10 @@ def test_zinb_nll_row_pairs_and_planes(ops, flags, B, G, dense):
     for c0, name in heads:
         ref = D[:, c0:c0 + G]
         assert np.abs(S[:, c0:c0 + G] - ref).max() <= 2.0 ** -22 * np.abs(ref).max() + 1e-38, name
+        # ... and of EACH element, not of the plane's largest: 2^-22 |D| plus the smallest bf16-denormal step (2^-133)
+        err = np.abs(S[:, c0:c0 + G] - ref)
+        bad = ~(err <= 2.0 ** -22 * np.abs(ref) + 2.0 ** -133)
+        assert not bad.any(), (name, int(bad.sum()), np.argwhere(bad)[:5], S[:, c0:c0 + G][bad][:5], ref[bad][:5])
     if cdisp:
         assert torch.equal(Dth[:, :G], dD[:, Gp:Gp + G])
 
