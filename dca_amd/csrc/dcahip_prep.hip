@@ -328,6 +328,114 @@ __global__ __launch_bounds__(256) void csr_gather_kernel(GatherArgs a) {
     if (bad) atomicAdd(a.status, bad);
 }
 
+// CSR gather for a network that reads all G input genes and fits G_out of them (train(output_subset=...)): the X tile of
+// csr_gather_kernel over the input columns, the Y tile over the OUTPUT columns, Y[r, col_out[g]] = the count of gene g.
+struct GatherColsArgs {
+    GatherArgs g;                       // g.ldy >= G_out: the Y tile's leading dimension
+    const int* col_out; int G_out;      // [G]: output column of input gene g, -1 = not fitted
+};
+
+// One workgroup per destination row, as csr_gather_kernel.  X pass: its segments of kCsrSeg input columns, entries in column
+// order with the early break.  Y pass: segments of kCsrSeg output columns; output order is not input order, so every
+// segment walks all of the row's entries and keeps those whose output column falls into it (a gene list is far below
+// kCsrSeg genes: one segment, one walk).  Every element of both tiles is written by one plain store.  What is counted
+// into *status is counted once per entry: a column outside [0, G) in the X pass (without X: in the first Y segment), a
+// col_out value outside [-1, G_out) in the first Y segment.
+template <int V>
+__global__ __launch_bounds__(256) void csr_gather_cols_kernel(GatherColsArgs ca) {
+    __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
+    __shared__ int found;
+    const GatherArgs& a = ca.g;
+    const int tid = threadIdx.x;
+    int bad = 0;
+    const long base = a.perm ? (long)*a.cursor : a.row0;
+    for (int r = blockIdx.x; r < a.B; r += gridDim.x) {
+        const long row = a.perm ? (long)a.perm[base + r] : base + r;
+        const bool ok = row >= 0 && row < a.n;
+        long s = 0, e = 0;
+        if (ok) { s = a.indptr[row]; e = a.indptr[row + 1]; }
+        const long s0 = s < 0 ? 0 : (s > a.nnz ? a.nnz : s);
+        const long e0 = e < s0 ? s0 : (e > a.nnz ? a.nnz : e);
+        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
+        const float f = (a.fac && ok) ? a.fac[row] : 1.f;
+        float t0 = 0.f;
+        if (a.fac) t0 = __fdiv_rn(t0, f);
+        if (a.do_log) t0 = log1pf(t0);
+        if (tid == 0 && a.sf_out) a.sf_out[r] = (ok && a.sf) ? a.sf[row] : 0.f;
+        if (a.X) {
+            long p = s0;
+            float* xrow = a.X + (long)r * a.ldx;
+            for (long c0 = 0; c0 < a.ldx; c0 += kCsrSeg) {
+                const int len = (int)(a.ldx - c0 < kCsrSeg ? a.ldx - c0 : kCsrSeg);
+                const long c1 = c0 + kCsrSeg < a.ldx ? c0 + kCsrSeg : (1L << 40);
+                if (V == 4) {
+                    for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {
+                    for (int i = tid; i < len; i += 256) seg[i] = 0.f;
+                }
+                if (tid == 0) found = 0;
+                __syncthreads();
+                int mine = 0;
+                for (long j = p + tid; j < e0; j += 256) {
+                    const long c = a.indices[j];
+                    if (c >= c1) break;
+                    ++mine;
+                    if (c < 0 || c >= a.G) { ++bad; continue; }
+                    const long k = c - c0;
+                    if (k >= 0 && k < len) seg[k] = a.values[j];
+                }
+                if (mine) atomicAdd(&found, mine);
+                __syncthreads();
+                p += found;
+                if (p > e0) p = e0;
+                if (V == 4) {
+                    for (int i = tid; i < (len >> 2); i += 256) {
+                        const float4 y = reinterpret_cast<const float4*>(seg)[i];
+                        const long col = c0 + 4 * i;
+                        float4 x;
+                        x.x = gather_x(y.x, t0, f, a, col);
+                        x.y = gather_x(y.y, t0, f, a, col + 1);
+                        x.z = gather_x(y.z, t0, f, a, col + 2);
+                        x.w = gather_x(y.w, t0, f, a, col + 3);
+                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
+                    }
+                } else {
+                    for (int i = tid; i < len; i += 256) xrow[c0 + i] = gather_x(seg[i], t0, f, a, c0 + i);
+                }
+                __syncthreads();
+            }
+        }
+        float* yrow = a.Y + (long)r * a.ldy;
+        for (long c0 = 0; c0 < a.ldy; c0 += kCsrSeg) {
+            const int len = (int)(a.ldy - c0 < kCsrSeg ? a.ldy - c0 : kCsrSeg);
+            const bool count = c0 == 0;
+            if (V == 4) {
+                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
+            }
+            __syncthreads();
+            for (long j = s0 + tid; j < e0; j += 256) {
+                const long c = a.indices[j];
+                if (c < 0 || c >= a.G) { if (count && !a.X) ++bad; continue; }
+                const long o = ca.col_out[c];
+                if (o < -1 || o >= ca.G_out) { if (count) ++bad; continue; }
+                const long k = o - c0;
+                if (o >= 0 && k >= 0 && k < len) seg[k] = a.values[j];
+            }
+            __syncthreads();
+            if (V == 4) {
+                for (int i = tid; i < (len >> 2); i += 256)
+                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
+            } else {
+                for (int i = tid; i < len; i += 256) yrow[c0 + i] = seg[i];
+            }
+            __syncthreads();
+        }
+    }
+    if (bad) atomicAdd(a.status, bad);
+}
+
 // CSR gather into the byte-store format (the tile the byte-store kernels of K-HEADS and K-SPARSE read): Yc [B, ldc] bytes
 // as counts_compact_kernel makes them from csr_gather_kernel's fp32 tile, the tile's overflow list, sf / fac per tile row
 // and, optionally, the fp32 X tile of csr_gather_kernel.  Three launches: the gather (which leaves every row's number of
@@ -932,6 +1040,26 @@ extern "C" int dcahip_csr_gather(const long* indptr, const int* indices, const f
     const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
     if (vec) hipLaunchKernelGGL(csr_gather_kernel<4>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(csr_gather_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcahip_csr_gather_cols(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                                      const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                                      const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
+                                      float* X, long ldx, float* sf_out, int* status, const int* col_out, int G_out,
+                                      void* stream) {
+    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || !col_out || G_out <= 0 || ldy < G_out || !status || !Y || !indptr)
+        return DCAHIP_EINVAL;
+    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
+    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf)) return DCAHIP_EINVAL;
+    if (B == 0) return 0;
+    GatherColsArgs a{{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
+                      Y, ldy, X, X ? ldx : 0, sf_out, status}, col_out, G_out};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = B < 16384 ? B : 16384;
+    const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
+    if (vec) hipLaunchKernelGGL(csr_gather_cols_kernel<4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(csr_gather_cols_kernel<1>, dim3(grid), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 

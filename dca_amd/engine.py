@@ -337,6 +337,7 @@ class Engine:
         # and every inference chunk gathers first (dcahip_csr_gather), and the kernels read the tiles through an identity
         # row vector and a zero cursor word (_kperm / _kcur) -- the real perm / cursor select the rows of the gather only
         self.csr = None
+        self.out_cols = self.col_out = None     # counts-resident mode fitting a gene subset: the map of attach_counts
         self.perm_id = self.cursor0 = None
         self.tile_order = None
         self.hist = None
@@ -631,7 +632,7 @@ class Engine:
         self._data_scales()
         self.attach_compact(compact, norm)
 
-    def attach_counts(self, csr, sf, norm, compact=None):
+    def attach_counts(self, csr, sf, norm, compact=None, out_cols=None):
         """Counts-resident mode: the raw counts stay on the device as CSR (prep.CsrCounts, [n, G_out]) and every step gathers
         its minibatch from them -- Y, the input X = (f(y / fac) - mean) / std described by norm (dict(fac, do_log, mean, std),
         dca/io.py:99-109) and sf [n] -- into [Bmax, .] tiles (dcahip_csr_gather) before the kernels of the dense form run on
@@ -643,14 +644,37 @@ class Engine:
         taken from the CSR.  Off, or where the dense engine would not use its byte store, or with ops that lack the entry:
         K-HEADS reads the fp32 tile and the first layer takes the dense products.  Validation and inference gather the
         fp32 tiles, and the byte tile beside them for the chunks whose first product the dense engine looks up from its
-        byte store (_lut_fwd: throughput chunks once training has made the tables)."""
+        byte store (_lut_fwd: throughput chunks once training has made the tables).
+        out_cols (train(output_subset=...), dca/train.py:85-87): G_out distinct input gene indices in output-column order
+        (any order) -- the network reads all csr.G input genes and fits these.  Every gather then goes through
+        dcahip_csr_gather_cols: the X tile over all input genes, the Y tile [Bmax, Gp] over the fitted ones, and the
+        once-per-dataset values are those of the dense engine on Y = counts[:, out_cols].  Such an engine gathers fp32 tiles
+        only: the byte tile does not apply, whatever `compact` says."""
         lay = self.lay
         if self.comm.world > 1:
             raise ValueError('dca_amd: counts-resident mode does not apply to data-parallel runs')
-        if norm is None or lay.G_in != lay.G_out or csr.G != lay.G_out:
-            raise ValueError('dca_amd: counts-resident mode needs input genes = output genes and a known input normalisation')
-        if not hasattr(self.ops, 'csr_gather'):
-            raise ValueError('dca_amd: counts-resident mode needs the CSR kernels (ops %s has no csr_gather)' % self.ops.name)
+        if out_cols is None:
+            if norm is None or lay.G_in != lay.G_out or csr.G != lay.G_out:
+                raise ValueError('dca_amd: counts-resident mode needs input genes = output genes and a known input '
+                                 'normalisation')
+            if not hasattr(self.ops, 'csr_gather'):
+                raise ValueError('dca_amd: counts-resident mode needs the CSR kernels (ops %s has no csr_gather)'
+                                 % self.ops.name)
+            col_out = None
+        else:
+            out_cols = np.asarray(out_cols, dtype=np.int64).reshape(-1)
+            if norm is None or csr.G != lay.G_in or len(out_cols) != lay.G_out:
+                raise ValueError('dca_amd: counts-resident mode with an output subset needs the counts of all %d input genes, '
+                                 '%d output genes and a known input normalisation' % (lay.G_in, lay.G_out))
+            if len(out_cols) == 0 or out_cols.min() < 0 or out_cols.max() >= csr.G or len(np.unique(out_cols)) != len(out_cols):
+                raise ValueError('dca_amd: out_cols must be distinct gene indices in [0, %d)' % csr.G)
+            if not hasattr(self.ops, 'csr_gather_cols'):
+                raise ValueError('dca_amd: an output subset in counts-resident mode needs ops with csr_gather_cols (ops %s)'
+                                 % self.ops.name)
+            inv = np.full(csr.G, -1, np.int32)
+            inv[out_cols] = np.arange(len(out_cols), dtype=np.int32)
+            col_out = torch.from_numpy(inv).to(self.dev)
+        self.out_cols, self.col_out = out_cols, col_out
         self.csr, self.sf_all, self.norm_c = csr, sf, dict(norm)
         self.n, self.ldx, self.ldy = csr.n, _r4(lay.G_in), lay.Gp
         self.gather_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -661,6 +685,8 @@ class Engine:
         self._tile_lut = False              # a training step has made the tile's table (the dense form's "lutp is not None")
         if compact is None:
             compact = self.cfg.counts_compact
+        if col_out is not None:
+            compact = False                 # (a byte tile of the subset: not built)
         if compact and hasattr(self.ops, 'csr_gather_compact') and hasattr(self.ops, 'counts_compact'):
             from . import compact as _compact
             v = _compact.csr_verdict(csr)
@@ -720,9 +746,18 @@ class Engine:
         device) or the storage rows row0 + r."""
         nm = self.norm_c
         perm, cur = (self.perm, self.cursor) if row0 is None else (None, None)
-        self.ops.csr_gather(self.csr, perm, cur, 0 if row0 is None else row0, B, self.sf_all, nm.get('fac'),
-                            nm.get('do_log', False), nm.get('mean'), nm.get('std'), self.Y, self.ldy, self.X, self.ldx,
-                            self.sf, self.gather_status)
+        self._csr_gather(perm, cur, 0 if row0 is None else row0, B, self.sf_all, self.Y, self.X, self.sf)
+
+    def _csr_gather(self, perm, cur, row0, B, sf, Y, X, sf_out):
+        """The fp32 tiles of B rows of the resident CSR: csr_gather, or csr_gather_cols when a gene subset is fitted."""
+        nm = self.norm_c
+        if self.col_out is not None:
+            self.ops.csr_gather_cols(self.csr, self.col_out, self.lay.G_out, perm, cur, row0, B, sf, nm.get('fac'),
+                                     nm.get('do_log', False), nm.get('mean'), nm.get('std'), Y, self.ldy, X, self.ldx,
+                                     sf_out, self.gather_status)
+        else:
+            self.ops.csr_gather(self.csr, perm, cur, row0, B, sf, nm.get('fac'), nm.get('do_log', False), nm.get('mean'),
+                                nm.get('std'), Y, self.ldy, X, self.ldx, sf_out, self.gather_status)
 
     def _range_rows(self, s, b):
         """Storage rows [s, s + b) of an inference pass: their first row in X / Y / sf -- s itself, or 0 once the
@@ -737,6 +772,11 @@ class Engine:
                                         None, 0, None, c.fac, self.gather_status)
             self.ops.enc0_lut(c.fac, c.do_log, b, c.lutp)
         return 0
+
+    def _fitted(self, indices):
+        """Counts-resident mode with a gene subset: which of these stored entries (their column indices) belong to a
+        fitted gene."""
+        return self.col_out.index_select(0, indices) >= 0
 
     def _csr_rows(self, r0, r1):
         """Counts-resident mode: (column index, value) of the stored entries of storage rows r0 .. r1 - 1."""
@@ -773,8 +813,18 @@ class Engine:
         """_data_scales of the dense form from the CSR: y_max over [n, Gp] (the zeros included whenever the matrix has one),
         and the block exponent of X over all rows, gathered a range at a time."""
         c, lay = self.csr, self.lay
-        ymax = float(c.values.max().item()) if c.nnz else 0.0
-        if c.nnz and c.nnz < c.n * lay.Gp:
+        if self.col_out is None:
+            nnz = c.nnz
+            ymax = float(c.values.max().item()) if nnz else 0.0
+        else:                                          # the entries of the fitted genes only, a slice of the CSR at a time
+            nnz, tops = 0, []
+            for a in range(0, c.nnz, 1 << 26):
+                v = c.values[a:a + (1 << 26)][self._fitted(c.indices[a:a + (1 << 26)])]
+                if v.numel():
+                    tops.append(v.max())
+                    nnz += int(v.numel())
+            ymax = float(torch.stack(tops).max().item()) if tops else 0.0
+        if nnz and nnz < c.n * lay.Gp:
             ymax = max(ymax, 0.0)                      # (a NaN stays NaN, as in the dense max)
         bound = max(1e4, 2.0 * ymax + 50.0) + 0.5 * float(self.ridge)
         self.d_exp = int(np.floor(np.log2(65000.0 / bound)))
@@ -783,11 +833,9 @@ class Engine:
             b = min(4096, c.n)
             Yt = torch.empty(b, self.ldy, dtype=torch.float32, device=self.dev)
             Xt = torch.empty(b, self.ldx, dtype=torch.float32, device=self.dev)
-            nm = self.norm_c
             for s in range(0, c.n, b):
                 e = min(c.n, s + b)
-                self.ops.csr_gather(c, None, None, s, e - s, None, nm.get('fac'), nm.get('do_log', False), nm.get('mean'),
-                                    nm.get('std'), Yt, self.ldy, Xt, self.ldx, None, self.gather_status)
+                self._csr_gather(None, None, s, e - s, None, Yt, Xt, None)
                 amax = torch.maximum(amax, Xt[:e - s, :lay.G_in].abs().max())
             one = torch.zeros(1, 4, dtype=torch.float32, device=self.dev)
             one[0, 0] = amax
@@ -813,6 +861,8 @@ class Engine:
             starts = torch.repeat_interleave(c.indptr[sel] - torch.cumsum(lens, 0) + lens, lens)
             idx = starts + torch.arange(int(lens.sum().item()), device=self.dev)
             v = c.values[idx]
+            if self.col_out is not None:                      # the sampled rows' entries of the fitted genes
+                v = v[self._fitted(c.indices[idx])]
             cnt = torch.bincount(torch.nan_to_num(v, nan=0.0).clamp(0, 65535.0).to(torch.int64), minlength=2)
             numel = int(sel.numel()) * self.lay.G_out
             cnt[0] += numel - int(v.numel())                  # the zeros the CSR does not store
@@ -929,6 +979,10 @@ class Engine:
         if self.csr is not None:                                 # the same counts of the same rows, from the CSR
             rows = min(self.csr.n, 65536)
             col, val = self._csr_rows(0, rows)
+            if self.col_out is not None:                         # binned by OUTPUT column
+                col = self.col_out.index_select(0, col).to(torch.int64)
+                val = torch.where(col >= 0, val, torch.zeros_like(val))
+                col = col.clamp_(min=0)
             nz += torch.bincount(col[val != 0], minlength=ntg * 32).to(torch.float32)
         else:
             rows = min(self.Y.shape[0], 65536)                   # a sample is enough to rank the tiles

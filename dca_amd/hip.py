@@ -169,6 +169,9 @@ _SIGNATURES = {
     'dcahip_csr_gather': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
                                      _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _i32p,
                                      _vp]),
+    'dcahip_csr_gather_cols': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
+                                          _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
+                                          _i32p, _i32p, _c.c_int, _vp]),
     'dcahip_csr_gather_compact': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long,
                                              _c.c_int, _f32p, _f32p, _c.c_int, _f32p, _f32p, _vp, _c.c_long, _i32p, _i32p,
                                              _f32p, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _i32p, _vp]),

@@ -303,6 +303,17 @@ class Autoencoder():
                    and not (lay.shared or lay.fork or lay.elempi) and mode in ('denoise', 'full')
                    and len(genes) == lay.G_out and getattr(eng, 'cfg', None) is not None and eng.cfg.fused_write
                    and bool(lay.hidden))
+        if not fusable and lay.G_out != adata.n_vars and mode in ('denoise', 'full') and len(genes) == lay.G_out:
+            # a network that fits a gene subset (train(output_subset=...)): its [n, G_out] results cannot replace adata.X
+            # [n, G] -- they go to the files through an AnnData of the fitted genes, adata itself stays as it is
+            import pandas as pd
+            from ._anndata import MiniAnnData
+            outs = self._run_predict(adata, want)
+            res = MiniAnnData(outs['mean'], obs=adata.obs, var=pd.DataFrame(index=pd.Index(genes)))
+            self._store(res, outs, mode, True)
+            self.write(res, file_path, mode=mode, colnames=colnames)
+            self._write_extra(res, file_path, genes)
+            return
         if not fusable:
             self.predict(adata, mode=mode, return_info=True)
             self.write(adata, file_path, mode=mode, colnames=colnames)

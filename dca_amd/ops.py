@@ -518,6 +518,18 @@ class HipOps:
                                            p(Y), ldy, p(X), ldx if X is not None else 0, p(sf_out), p(status),
                                            hip.stream()), 'csr_gather')
 
+    def csr_gather_cols(self, csr, col_out, G_out, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out,
+                        status):
+        """csr_gather for a network that fits G_out of the G input genes: X[:B, :ldx] over all input genes as csr_gather
+        writes it, Y[:B, :ldy] over the output columns, Y[r, col_out[g]] = the count of gene g (col_out: int32 [G] device
+        tensor, -1 = not fitted), zero elsewhere (include/dcahip.h)."""
+        p = hip.ptr
+        assert col_out.dtype == torch.int32 and col_out.numel() >= csr.G
+        hip.check(self.L.dcahip_csr_gather_cols(p(csr.indptr), p(csr.indices), p(csr.values), csr.nnz, csr.n, csr.G, p(perm),
+                                                p(cursor), int(row0), B, p(sf), p(fac), int(bool(do_log)), p(mean), p(std),
+                                                p(Y), ldy, p(X), ldx if X is not None else 0, p(sf_out), p(status),
+                                                p(col_out), int(G_out), hip.stream()), 'csr_gather_cols')
+
     def csr_gather_compact(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Yc, ldc, ovf_ptr, ovf_col, ovf_val,
                            X, ldx, sf_out, fac_out, status):
         """The minibatch tile of a resident CSR in the byte-store format (compact.CompactCounts of the tile's B rows): every

@@ -55,9 +55,19 @@ class DeviceData:
         return self.host_mark is None or fingerprint(host_x) == self.host_mark
 
     def attach(self, eng):
-        """Hands these tensors to the engine (the dense ones, or the CSR of the counts-resident form)."""
+        """Hands these tensors to the engine (the dense ones, or the CSR of the counts-resident form).  An engine that
+        fits a gene subset (train(output_subset=...)) keeps its column map (Engine.out_cols) and gets it back here, so that
+        the tiles of a later inference pass have the shapes of its network; the dense counts of all genes are no target
+        for such a network and stay out (inference reads X only)."""
+        subset = eng.lay.G_out != self.G
         if self.csr is not None:
-            eng.attach_counts(self.csr, self.sf, self.norm)
+            out_cols = getattr(eng, 'out_cols', None)
+            if out_cols is not None and len(out_cols) == eng.lay.G_out:
+                eng.attach_counts(self.csr, self.sf, self.norm, out_cols=out_cols)
+            else:
+                eng.attach_counts(self.csr, self.sf, self.norm)
+        elif subset:
+            eng.attach_device_data(self.X, None, self.sf, norm=self.norm, compact=False)
         else:
             eng.attach_device_data(self.X, self.Y, self.sf, norm=self.norm, compact=self.compact)
 
@@ -253,12 +263,13 @@ RESIDENT_MODES = ('auto', 'counts', 'dense')
 
 
 def choose_residency(mode, dense_need, counts_need, free, world=1, output_subset=False, use_raw_as_output=True,
-                     has_norm=True):
+                     has_norm=True, subset_gather=False):
     """'dense' or 'counts': where the counts of a dataset live on the device (EngineConfig.resident).  'dense' keeps
     today's [n, G] matrices; 'counts' keeps the CSR and gathers each minibatch.  'auto' stays dense whenever its estimate
     fits into `free` device bytes, and whenever counts mode cannot apply: data parallel (world > 1), an output_subset,
     use_raw_as_output=False, an input that is not a known function of the counts (has_norm=False).  Forcing 'counts' in
-    one of those cases raises ValueError saying why."""
+    one of those cases raises ValueError saying why.  subset_gather=True: the ops gather a gene subset from the CSR
+    (csr_gather_cols, Engine.attach_counts(out_cols=...)), so an output_subset no longer stops counts mode."""
     if mode not in RESIDENT_MODES:
         raise ValueError('resident must be one of %s (got %r)' % (', '.join(RESIDENT_MODES), mode))
     if mode == 'dense':
@@ -266,7 +277,7 @@ def choose_residency(mode, dense_need, counts_need, free, world=1, output_subset
     why = None
     if world > 1:
         why = 'data-parallel runs (%d ranks) keep dense residency' % world
-    elif output_subset:
+    elif output_subset and not subset_gather:
         why = 'an output_subset needs the dense count matrix'
     elif not use_raw_as_output:
         why = 'use_raw_as_output=False trains on the normalised input, which is not kept'

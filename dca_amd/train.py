@@ -270,6 +270,21 @@ class _StepRunner:
         self.run(b, b_global, world_counts, rows_per_slot, 1)
 
 
+def _subset_gather_refusal(adata, dd, gene_idx, ops):
+    """Why the genes `gene_idx` of adata.raw cannot be gathered as a subset of the counts resident in dd.csr -- None when
+    they can: the ops have the kernel, adata.raw is the resident matrix (its shape and gene names) and no gene is named
+    twice (two output columns of one gene need the dense matrix)."""
+    if not hasattr(ops, 'csr_gather_cols'):
+        return 'an output_subset needs the dense count matrix'
+    raw = adata.raw
+    if tuple(raw.X.shape) != (dd.n, dd.G) or len(raw.var_names) != len(adata.var_names) or \
+            not (np.asarray(raw.var_names) == np.asarray(adata.var_names)).all():
+        return 'adata.raw is not the resident count matrix'
+    if len(set(int(g) for g in gene_idx)) != len(gene_idx):
+        return 'the output_subset names a gene twice'
+    return None
+
+
 def train(adata, network, output_dir=None, optimizer='RMSprop', learning_rate=None,
           epochs=300, reduce_lr=10, output_subset=None, use_raw_as_output=True,
           early_stop=15, batch_size=32, clip_grad=5., save_weights=False,
@@ -309,12 +324,25 @@ def train(adata, network, output_dir=None, optimizer='RMSprop', learning_rate=No
     v0, nv = ddist.shard(n_val, comm.world, comm.rank)
     rows = np.r_[np.arange(t0, t0 + nt), split_at + np.arange(v0, v0 + nv)]
     dd = getattr(adata, '_dca_device', None)
+    out_cols = None
+    if dd is not None and dd.csr is not None and output_subset:
+        # the resident CSR holds the counts of all genes: the subset is gathered from it (Engine.attach_counts(out_cols=...))
+        # when the ops can and the targets are the raw counts of distinct genes of that very matrix
+        why = _subset_gather_refusal(adata, dd, gene_idx, eng.ops)
+        if why is None and use_raw_as_output and comm.world == 1 and dd.norm is not None:
+            out_cols = np.asarray(gene_idx, dtype=np.int64)
+        elif eng.cfg.resident == 'counts' and why is not None and hasattr(eng.ops, 'csr_gather_cols'):
+            raise ValueError('dca_amd: counts-resident mode does not apply: ' + why)
     if dd is not None and dd.csr is not None and eng.cfg.resident == 'counts':
         # forced counts-resident mode: say why it cannot apply instead of falling back to a dense upload
         from .prep import choose_residency
         choose_residency('counts', 0, 0, 0, world=comm.world, output_subset=bool(output_subset),
-                         use_raw_as_output=use_raw_as_output, has_norm=dd.norm is not None)
-    if comm.world == 1 and dd is not None and not output_subset and use_raw_as_output and \
+                         use_raw_as_output=use_raw_as_output, has_norm=dd.norm is not None,
+                         subset_gather=hasattr(eng.ops, 'csr_gather_cols'))
+    if out_cols is not None and dd.n == n and dd.G == X.shape[1] == eng.lay.G_in and len(out_cols) == eng.lay.G_out and \
+            dd.device == eng.dev and dd.matches(X):
+        eng.attach_counts(dd.csr, dd.sf, dd.norm, out_cols=out_cols)
+    elif comm.world == 1 and dd is not None and not output_subset and use_raw_as_output and \
             dd.n == n and dd.G == X.shape[1] == eng.lay.G_in == eng.lay.G_out and \
             dd.device == eng.dev and dd.matches(X):
         dd.attach(eng)                                                                  # K-PREP left the tensors in HBM

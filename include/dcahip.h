@@ -567,7 +567,7 @@ int dcahip_csr_subset(const long* indptr, const int* indices, const float* value
 /*
  * Resident CSR (counts-resident mode): the raw counts stay on the device as CSR -- indptr [n + 1] int64 (absolute offsets),
  * indices int32, values fp32, canonical rows -- and every step builds only its own minibatch.  The preprocessing is that
- * of dca/io.py:88-111 (as dcahip_prep_*), the per-batch rows those of the Keras feed, dca/train.py:83-98.  All three
+ * of dca/io.py:88-111 (as dcahip_prep_*), the per-batch rows those of the Keras feed, dca/train.py:83-98.  All these
  * entries share csr_expand's guarantees: a storage row outside [0, n), an indptr entry outside [0, nnz] or decreasing, a
  * column outside [0, G) is clamped / skipped and counted into *status (one int32, zeroed by the caller); nothing outside
  * the buffers is read or written.
@@ -580,6 +580,17 @@ int dcahip_csr_subset(const long* indptr, const int* indices, const float* value
  *                         f(0 / fac[row]) unscaled, as prep_col_pass leaves them.  sf_out[r] = sf[row] (sf_out may be
  *                         NULL).  Reads nothing from the host: capturable in a step's graph, valid on every replay.
  *                         One plain store per element, no atomics on the tiles.  B = 0 launches nothing.
+ *   dcahip_csr_gather_cols
+ *                         the minibatch tile of a network that reads all G input genes and fits G_out of them
+ *                         (train(output_subset=...), dca/train.py:85-87): dcahip_csr_gather's arguments, then col_out [G]
+ *                         int32 -- the output column of input gene g, -1 when the gene is not fitted -- and G_out.
+ *                         X[r, 0 .. ldx) is over ALL G input genes, bit for bit dcahip_csr_gather's X tile (pad columns and
+ *                         the fac / do_log / mean / std options included).  Y[r, 0 .. ldy), ldy >= G_out: Y[r, col_out[g]]
+ *                         = the count of gene g, every other element +0.0, the pad columns G_out .. ldy included.  sf_out,
+ *                         the choice of the storage row, the capture guarantee, "one plain store per element" and B = 0 as
+ *                         dcahip_csr_gather.  Besides the shared guarantees, an entry whose col_out value lies outside
+ *                         [-1, G_out) is skipped and counted into *status (once per entry).  Two genes with the same
+ *                         output column are the caller's error: one of the two counts lands there.
  *   dcahip_csr_gather_compact
  *                         the same minibatch tile in the byte-store format of K-SPARSE (below), for the kernels that read
  *                         the compact counts (dcahip_heads_fused_compact, dcahip_enc0_fwd_lut, dcahip_enc0_dw_sparse) with
@@ -606,6 +617,10 @@ int dcahip_csr_gather(const long* indptr, const int* indices, const float* value
                       const int* perm, const long long* cursor, long row0, int B, const float* sf,
                       const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
                       float* X, long ldx, float* sf_out, int* status, void* stream);
+int dcahip_csr_gather_cols(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                           const int* perm, const long long* cursor, long row0, int B, const float* sf,
+                           const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
+                           float* X, long ldx, float* sf_out, int* status, const int* col_out, int G_out, void* stream);
 int dcahip_csr_gather_compact(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
                               const int* perm, const long long* cursor, long row0, int B, const float* sf,
                               const float* fac, int do_log, const float* mean, const float* stdv,

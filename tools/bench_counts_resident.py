@@ -11,6 +11,9 @@
          synthesised on the device as CSR): ms/step and the peak device memory (--big-compact: with the byte tile).
   python tools/bench_counts_resident.py --gather-only [--compact]   (the gather's replays alone: for rocprofv3
                                                                      --kernel-trace --stats)
+  python tools/bench_counts_resident.py --subset K --out profiles/counts_subset_bench.json
+      dcahip_csr_gather_cols for K shuffled output genes beside dcahip_csr_gather at the same shape, in one process, the two
+      interleaved over --rounds rounds (graph replays, event-timed): ms per call, the spread, their ratio.
   --forms a,b: only these forms (a run of an older checkout beside this one: --forms counts).
 """
 import argparse
@@ -152,6 +155,8 @@ def main():
     ap.add_argument('--forms', type=str, default='dense,dense_no_byte_store,counts,counts_compact')
     ap.add_argument('--compact', action='store_true', help='--gather-only: the byte tile\'s gather')
     ap.add_argument('--big-compact', action='store_true')
+    ap.add_argument('--subset', type=int, default=0,
+                    help='time csr_gather_cols for this many shuffled output genes beside csr_gather, interleaved; nothing else')
     ap.add_argument('--out', type=str, default='')
     args = ap.parse_args()
     dev = torch.device('cuda')
@@ -168,6 +173,35 @@ def main():
     res['nnz'] = csr.nnz
     res['csr_gb'] = csr.nbytes / 1e9
     res['dense_estimate_gb'] = prep.dense_bytes(n, G) / 1e9
+
+    if args.subset:
+        import numpy as np
+        K = args.subset
+        cols = np.random.default_rng(0).permutation(G)[:K]
+        engs = {}
+        for form, k, oc in (('csr_gather', G, None), ('csr_gather_cols', K, cols)):
+            eng = Engine('zinb-conddisp', G, k, (64, 32, 64), True, 0.0, ops=ops)
+            eng.attach_counts(csr, sf, norm, compact=False, out_cols=oc)
+            eng.reserve(B)
+            eng.perm = torch.randperm(n_train, device=dev).to(torch.int32)
+            engs[form] = eng
+        rounds = {form: [] for form in engs}
+        for _ in range(args.rounds):                  # interleaved: every round times both entries once
+            for form, eng in engs.items():
+                rounds[form].append(round(gather_replays(ops, eng, B, 50), 4))
+        for form, ms in rounds.items():
+            med = sorted(ms)[len(ms) // 2]
+            eng = engs[form]
+            res[form] = dict(ms=med, rounds=ms, spread=round((max(ms) - min(ms)) / med, 4),
+                             tile_mb=(B * (eng.ldx + eng.ldy) * 4 + B * 4) / 1e6)
+        res['subset'] = K
+        res['cols_over_gather'] = round(res['csr_gather_cols']['ms'] / res['csr_gather']['ms'], 3)
+        res['gather_status'] = [int(e.gather_status.item()) for e in engs.values()]
+        print(json.dumps(res), flush=True)
+        if args.out:
+            with open(args.out, 'w') as f:
+                json.dump(res, f, indent=1)
+        return
 
     if args.gather_only:
         eng = Engine('zinb-conddisp', G, G, (64, 32, 64), True, 0.0, ops=ops)
