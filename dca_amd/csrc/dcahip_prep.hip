@@ -161,72 +161,18 @@ __global__ __launch_bounds__(256) void scale_kernel(float* X, long ldx, int n, i
     }
 }
 
-// CSR expand: one workgroup per row (grid-stride).  The row is built in LDS column segments of
-// kCsrSeg floats: zero the segment, scatter the row's entries that fall into it, write it out with
-// V-float stores.  Columns are sorted (canonical rows), so the entries of a segment are the
-// contiguous run [p, q) that starts where the previous segment's run ended; q - p is the number of
-// entries the threads found below the segment's end (each thread walks its strided share and stops
-// at the first column beyond it).  Every LDS and global write is bounds-checked against the segment
-// and the row, so unsorted or malformed input can give wrong values but never touches memory outside
-// Y; entries with a column outside [0, G) and rows whose indptr leaves [0, nnz] or decreases are
-// counted into *status.  Each element is written by exactly one plain store: no atomics on Y.
+// ---- the row core of the CSR expand and gather kernels -------------------------------------------------------------------
+// One workgroup builds one destination row in LDS column segments: zero the segment (seg_clear), scatter the row's entries
+// that fall into it (seg_scatter), write it out (seg_store, seg_store_x).  Every kernel below is this loop with its own
+// row header, segment type and stores; a further tile format is one more such loop: its own `put` for seg_scatter and its
+// own store of the finished segment.
+// The contract of all of them: malformed input (unsorted columns, a column outside [0, G), a storage row outside [0, n),
+// an indptr that leaves [0, nnz] or decreases) is clamped and counted into *status -- wrong values at worst, never an
+// access outside the buffers -- and each element of a tile is written by exactly one plain store: no atomics on a tile.
 constexpr int kCsrSeg = 8064;                 // floats per LDS segment (31.5 KiB + the counter: 5 workgroups per CU)
-
-template <int V>
-__global__ __launch_bounds__(256) void csr_expand_kernel(const int* __restrict__ indptr, const int* __restrict__ indices,
-                                                         const float* __restrict__ values, long nnz, int rows, int G,
-                                                         float* __restrict__ Y, long ldy, int* status) {
-    __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
-    __shared__ int found;
-    const int tid = threadIdx.x;
-    int bad = 0;
-    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-        long s = indptr[r], e = indptr[r + 1];
-        const long s0 = s < 0 ? 0 : (s > nnz ? nnz : s);
-        const long e0 = e < s0 ? s0 : (e > nnz ? nnz : e);
-        if (tid == 0 && (s0 != s || e0 != e)) ++bad;
-        long p = s0;
-        float* yrow = Y + (long)r * ldy;
-        for (long c0 = 0; c0 < ldy; c0 += kCsrSeg) {
-            const int len = (int)(ldy - c0 < kCsrSeg ? ldy - c0 : kCsrSeg);
-            // the last segment takes every remaining entry (columns >= ldy are counted, not written)
-            const long c1 = c0 + kCsrSeg < ldy ? c0 + kCsrSeg : (1L << 40);
-            if (V == 4) {
-                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
-            }
-            if (tid == 0) found = 0;
-            __syncthreads();
-            int mine = 0;
-            for (long j = p + tid; j < e0; j += 256) {
-                const long c = indices[j];
-                if (c >= c1) break;
-                ++mine;
-                if (c < 0 || c >= G) { ++bad; continue; }
-                const long k = c - c0;
-                if (k >= 0 && k < len) seg[k] = values[j];
-            }
-            if (mine) atomicAdd(&found, mine);
-            __syncthreads();
-            p += found;
-            if (p > e0) p = e0;
-            if (V == 4) {
-                for (int i = tid; i < (len >> 2); i += 256)
-                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
-            } else {
-                for (int i = tid; i < len; i += 256) yrow[c0 + i] = seg[i];
-            }
-            __syncthreads();
-        }
-    }
-    if (bad) atomicAdd(status, bad);
-}
 
 // Resident CSR (counts-resident mode: the counts stay in HBM as CSR, each step builds only its own minibatch).
 // indptr is int64 (absolute offsets into indices / values, whose length nnz may exceed 2^31); rows are canonical.
-// The entries of a storage row that malformed input names outside [0, n) or whose indptr leaves [0, nnz] / decreases are
-// clamped and counted, exactly as in csr_expand_kernel: wrong values at worst, never an access outside the buffers.
 struct GatherArgs {
     const long* indptr; const int* indices; const float* values; long nnz; int n, G;
     const int* perm; const long long* cursor; long row0; int B;
@@ -234,9 +180,45 @@ struct GatherArgs {
     float* Y; long ldy; float* X; long ldx; float* sf_out; int* status;
 };
 
-// x of one element as prep_col_pass + prep_scale write it.  t0: the row's transform of a +0 count (a function of the row
-// only, computed once per row); the scale applies to the G real columns only (prep_scale leaves the pad columns as
-// prep_col_pass wrote them).
+// [s, e) clamped into [0, nnz] and made non-decreasing; true when that changed it
+__device__ __forceinline__ bool clamp_span(long s, long e, long nnz, long& s0, long& e0) {
+    s0 = s < 0 ? 0 : (s > nnz ? nnz : s);
+    e0 = e < s0 ? s0 : (e > nnz ? nnz : e);
+    return s0 != s || e0 != e;
+}
+
+struct RowSpan { long row; bool ok; long s0, e0; };   // the storage row, whether the CSR has it, its clamped entries
+
+__device__ __forceinline__ long gather_base(const GatherArgs& g) { return g.perm ? (long)*g.cursor : g.row0; }
+
+// Destination row r: storage row perm[*cursor + r] or row0 + r.  A storage row outside [0, n) has no entries; it and a
+// clamped span are counted once (thread 0).
+__device__ __forceinline__ RowSpan row_span(const GatherArgs& g, long base, int r, int tid, int& bad) {
+    RowSpan w;
+    w.row = g.perm ? (long)g.perm[base + r] : base + r;
+    w.ok = w.row >= 0 && w.row < g.n;
+    long s = 0, e = 0;
+    if (w.ok) { s = g.indptr[w.row]; e = g.indptr[w.row + 1]; }
+    const bool moved = clamp_span(s, e, g.nnz, w.s0, w.e0);
+    if (tid == 0 && (!w.ok || moved)) ++bad;
+    return w;
+}
+
+// The row's normalisation factor f, sf_out[r] and -- where an X tile is written (x) -- t0, the row's transform of a +0
+// count: a function of the row only, computed once per row.
+__device__ __forceinline__ float row_factor(const GatherArgs& g, const RowSpan& w, int r, int tid, bool x, float& t0) {
+    const float f = (g.fac && w.ok) ? g.fac[w.row] : 1.f;
+    t0 = 0.f;
+    if (x) {
+        if (g.fac) t0 = __fdiv_rn(t0, f);
+        if (g.do_log) t0 = log1pf(t0);
+    }
+    if (tid == 0 && g.sf_out) g.sf_out[r] = (w.ok && g.sf) ? g.sf[w.row] : 0.f;
+    return f;
+}
+
+// x of one element as prep_col_pass + prep_scale write it; the scale applies to the G real columns only (prep_scale leaves
+// the pad columns as prep_col_pass wrote them).
 __device__ inline float gather_x(float y, float t0, float f, const GatherArgs& a, long col) {
     float t = t0;
     if (__float_as_uint(y) != 0u) {
@@ -248,80 +230,131 @@ __device__ inline float gather_x(float y, float t0, float f, const GatherArgs& a
     return t;
 }
 
-// CSR gather: one workgroup per destination row r < B (grid-stride), storage row perm[*cursor + r] or row0 + r.  The row is
-// built in LDS segments as in csr_expand_kernel; every element of Y[r, 0 .. ldy) and X[r, 0 .. ldx) is written by one
-// plain store (V-float stores when aligned).
+// The segment at column c0 of a row of L columns in segments of S: its length, and the first column behind it -- the last
+// segment takes every remaining entry (columns >= L are counted, not written); seg_part: what of it lies in a tile of
+// leading dimension ld <= L.
+__device__ __forceinline__ int seg_len(long L, long c0, int S) { return (int)(L - c0 < S ? L - c0 : S); }
+__device__ __forceinline__ long seg_end(long L, long c0, int S) { return c0 + S < L ? c0 + S : (1L << 40); }
+__device__ __forceinline__ int seg_part(long ld, long c0, int len) {
+    return (int)(ld - c0 < len ? (ld - c0 > 0 ? ld - c0 : 0) : len);
+}
+
+// V = 4: 16-byte accesses (len * sizeof(T) is a multiple of 16), V = 1: one element at a time
+template <typename T, int V>
+__device__ __forceinline__ void seg_clear(T* seg, int len, int tid) {
+    if (V == 1) {
+        for (int i = tid; i < len; i += 256) seg[i] = T(0);
+    } else {
+        const int nq = (int)((len * sizeof(T)) >> 4);
+        for (int i = tid; i < nq; i += 256) reinterpret_cast<uint4*>(seg)[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// The entries of the segment [c0, c0 + len): every thread walks its strided share of the sorted run that starts at p and
+// stops at the first column >= c1; put(k, j) places entry j at segment element k, 0 <= k < len.  A column outside [0, G)
+// is counted and skipped.  Returns where the next segment's run starts: p + the number of entries the threads found,
+// at most e0.  Two barriers: behind the clear, and behind the scatter (the segment is complete when this returns).
+template <class Put>
+__device__ __forceinline__ long seg_scatter(const int* indices, long p, long e0, long c0, long c1, int len, int G, int tid,
+                                            int& bad, int& found, Put put) {
+    if (tid == 0) found = 0;
+    __syncthreads();
+    int mine = 0;
+    for (long j = p + tid; j < e0; j += 256) {
+        const long c = indices[j];
+        if (c >= c1) break;
+        ++mine;
+        if (c < 0 || c >= G) { ++bad; continue; }
+        const long k = c - c0;
+        if (k >= 0 && k < len) put(k, j);
+    }
+    if (mine) atomicAdd(&found, mine);
+    __syncthreads();
+    p += found;
+    return p > e0 ? e0 : p;
+}
+
+// dst[0 .. n) = seg[0 .. n)
+template <typename T, int V>
+__device__ __forceinline__ void seg_store(T* dst, const T* seg, int n, int tid) {
+    if (V == 1) {
+        for (int i = tid; i < n; i += 256) dst[i] = seg[i];
+    } else {
+        const int nq = (int)((n * sizeof(T)) >> 4);
+        for (int i = tid; i < nq; i += 256) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(seg)[i];
+    }
+}
+
+// dst[0 .. n) = gather_x of the segment's counts; dst[0] is column c0
+template <int V>
+__device__ __forceinline__ void seg_store_x(float* dst, const float* seg, int n, long c0, float t0, float f,
+                                            const GatherArgs& g, int tid) {
+    if (V == 4) {
+        for (int i = tid; i < (n >> 2); i += 256) {
+            const float4 y = reinterpret_cast<const float4*>(seg)[i];
+            const long col = c0 + 4 * i;
+            float4 x;
+            x.x = gather_x(y.x, t0, f, g, col);
+            x.y = gather_x(y.y, t0, f, g, col + 1);
+            x.z = gather_x(y.z, t0, f, g, col + 2);
+            x.w = gather_x(y.w, t0, f, g, col + 3);
+            reinterpret_cast<float4*>(dst)[i] = x;
+        }
+    } else {
+        for (int i = tid; i < n; i += 256) dst[i] = gather_x(seg[i], t0, f, g, c0 + i);
+    }
+}
+
+// CSR expand: rows of an int32 CSR chunk (grid-stride), every element of Y[r, 0 .. ldy) written with V-float stores.
+template <int V>
+__global__ __launch_bounds__(256) void csr_expand_kernel(const int* __restrict__ indptr, const int* __restrict__ indices,
+                                                         const float* __restrict__ values, long nnz, int rows, int G,
+                                                         float* __restrict__ Y, long ldy, int* status) {
+    __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
+    __shared__ int found;
+    const int tid = threadIdx.x;
+    int bad = 0;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+        long s0, e0;
+        if (clamp_span(indptr[r], indptr[r + 1], nnz, s0, e0) && tid == 0) ++bad;
+        long p = s0;
+        float* yrow = Y + (long)r * ldy;
+        for (long c0 = 0; c0 < ldy; c0 += kCsrSeg) {
+            const int len = seg_len(ldy, c0, kCsrSeg);
+            seg_clear<float, V>(seg, len, tid);
+            p = seg_scatter(indices, p, e0, c0, seg_end(ldy, c0, kCsrSeg), len, G, tid, bad, found,
+                            [&](long k, long j) { seg[k] = values[j]; });
+            seg_store<float, V>(yrow + c0, seg, len, tid);
+            __syncthreads();
+        }
+    }
+    if (bad) atomicAdd(status, bad);
+}
+
+// CSR gather: one workgroup per destination row r < B (grid-stride); every element of Y[r, 0 .. ldy) and X[r, 0 .. ldx)
+// is written (V-float stores when aligned).
 template <int V>
 __global__ __launch_bounds__(256) void csr_gather_kernel(GatherArgs a) {
     __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
     __shared__ int found;
     const int tid = threadIdx.x;
     int bad = 0;
-    const long base = a.perm ? (long)*a.cursor : a.row0;
+    const long base = gather_base(a);
     const long L = (a.X && a.ldx > a.ldy) ? a.ldx : a.ldy;
     for (int r = blockIdx.x; r < a.B; r += gridDim.x) {
-        const long row = a.perm ? (long)a.perm[base + r] : base + r;
-        const bool ok = row >= 0 && row < a.n;
-        long s = 0, e = 0;
-        if (ok) { s = a.indptr[row]; e = a.indptr[row + 1]; }
-        const long s0 = s < 0 ? 0 : (s > a.nnz ? a.nnz : s);
-        const long e0 = e < s0 ? s0 : (e > a.nnz ? a.nnz : e);
-        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
-        const float f = (a.fac && ok) ? a.fac[row] : 1.f;
-        float t0 = 0.f;
-        if (a.fac) t0 = __fdiv_rn(t0, f);
-        if (a.do_log) t0 = log1pf(t0);
-        if (tid == 0 && a.sf_out) a.sf_out[r] = (ok && a.sf) ? a.sf[row] : 0.f;
-        long p = s0;
+        const RowSpan w = row_span(a, base, r, tid, bad);
+        float t0;
+        const float f = row_factor(a, w, r, tid, true, t0);
+        long p = w.s0;
         float* yrow = a.Y + (long)r * a.ldy;
         float* xrow = a.X ? a.X + (long)r * a.ldx : nullptr;
         for (long c0 = 0; c0 < L; c0 += kCsrSeg) {
-            const int len = (int)(L - c0 < kCsrSeg ? L - c0 : kCsrSeg);
-            const long c1 = c0 + kCsrSeg < L ? c0 + kCsrSeg : (1L << 40);
-            if (V == 4) {
-                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
-            }
-            if (tid == 0) found = 0;
-            __syncthreads();
-            int mine = 0;
-            for (long j = p + tid; j < e0; j += 256) {
-                const long c = a.indices[j];
-                if (c >= c1) break;
-                ++mine;
-                if (c < 0 || c >= a.G) { ++bad; continue; }
-                const long k = c - c0;
-                if (k >= 0 && k < len) seg[k] = a.values[j];
-            }
-            if (mine) atomicAdd(&found, mine);
-            __syncthreads();
-            p += found;
-            if (p > e0) p = e0;
-            const int ly = (int)(a.ldy - c0 < len ? (a.ldy - c0 > 0 ? a.ldy - c0 : 0) : len);
-            if (V == 4) {
-                for (int i = tid; i < (ly >> 2); i += 256)
-                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
-            } else {
-                for (int i = tid; i < ly; i += 256) yrow[c0 + i] = seg[i];
-            }
-            if (xrow) {
-                const int lx = (int)(a.ldx - c0 < len ? (a.ldx - c0 > 0 ? a.ldx - c0 : 0) : len);
-                if (V == 4) {
-                    for (int i = tid; i < (lx >> 2); i += 256) {
-                        const float4 y = reinterpret_cast<const float4*>(seg)[i];
-                        const long col = c0 + 4 * i;
-                        float4 x;
-                        x.x = gather_x(y.x, t0, f, a, col);
-                        x.y = gather_x(y.y, t0, f, a, col + 1);
-                        x.z = gather_x(y.z, t0, f, a, col + 2);
-                        x.w = gather_x(y.w, t0, f, a, col + 3);
-                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
-                    }
-                } else {
-                    for (int i = tid; i < lx; i += 256) xrow[c0 + i] = gather_x(seg[i], t0, f, a, c0 + i);
-                }
-            }
+            const int len = seg_len(L, c0, kCsrSeg);
+            seg_clear<float, V>(seg, len, tid);
+            p = seg_scatter(a.indices, p, w.e0, c0, seg_end(L, c0, kCsrSeg), len, a.G, tid, bad, found,
+                            [&](long k, long j) { seg[k] = a.values[j]; });
+            seg_store<float, V>(yrow + c0, seg, seg_part(a.ldy, c0, len), tid);
+            if (xrow) seg_store_x<V>(xrow + c0, seg, seg_part(a.ldx, c0, len), c0, t0, f, a, tid);
             __syncthreads();
         }
     }
@@ -335,12 +368,11 @@ struct GatherColsArgs {
     const int* col_out; int G_out;      // [G]: output column of input gene g, -1 = not fitted
 };
 
-// One workgroup per destination row, as csr_gather_kernel.  X pass: its segments of kCsrSeg input columns, entries in column
-// order with the early break.  Y pass: segments of kCsrSeg output columns; output order is not input order, so every
-// segment walks all of the row's entries and keeps those whose output column falls into it (a gene list is far below
-// kCsrSeg genes: one segment, one walk).  Every element of both tiles is written by one plain store.  What is counted
-// into *status is counted once per entry: a column outside [0, G) in the X pass (without X: in the first Y segment), a
-// col_out value outside [-1, G_out) in the first Y segment.
+// X pass: the segments of csr_gather_kernel over the input columns.  Y pass: segments of kCsrSeg output columns; output
+// order is not input order, so every segment walks all of the row's entries and keeps those whose output column falls
+// into it (a gene list is far below kCsrSeg genes: one segment, one walk).  What is counted into *status is counted once
+// per entry: a column outside [0, G) in the X pass (without X: in the first Y segment), a col_out value outside
+// [-1, G_out) in the first Y segment.
 template <int V>
 __global__ __launch_bounds__(256) void csr_gather_cols_kernel(GatherColsArgs ca) {
     __shared__ __attribute__((aligned(16))) float seg[kCsrSeg];
@@ -348,74 +380,30 @@ __global__ __launch_bounds__(256) void csr_gather_cols_kernel(GatherColsArgs ca)
     const GatherArgs& a = ca.g;
     const int tid = threadIdx.x;
     int bad = 0;
-    const long base = a.perm ? (long)*a.cursor : a.row0;
+    const long base = gather_base(a);
     for (int r = blockIdx.x; r < a.B; r += gridDim.x) {
-        const long row = a.perm ? (long)a.perm[base + r] : base + r;
-        const bool ok = row >= 0 && row < a.n;
-        long s = 0, e = 0;
-        if (ok) { s = a.indptr[row]; e = a.indptr[row + 1]; }
-        const long s0 = s < 0 ? 0 : (s > a.nnz ? a.nnz : s);
-        const long e0 = e < s0 ? s0 : (e > a.nnz ? a.nnz : e);
-        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
-        const float f = (a.fac && ok) ? a.fac[row] : 1.f;
-        float t0 = 0.f;
-        if (a.fac) t0 = __fdiv_rn(t0, f);
-        if (a.do_log) t0 = log1pf(t0);
-        if (tid == 0 && a.sf_out) a.sf_out[r] = (ok && a.sf) ? a.sf[row] : 0.f;
+        const RowSpan w = row_span(a, base, r, tid, bad);
+        float t0;
+        const float f = row_factor(a, w, r, tid, true, t0);
         if (a.X) {
-            long p = s0;
+            long p = w.s0;
             float* xrow = a.X + (long)r * a.ldx;
             for (long c0 = 0; c0 < a.ldx; c0 += kCsrSeg) {
-                const int len = (int)(a.ldx - c0 < kCsrSeg ? a.ldx - c0 : kCsrSeg);
-                const long c1 = c0 + kCsrSeg < a.ldx ? c0 + kCsrSeg : (1L << 40);
-                if (V == 4) {
-                    for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                } else {
-                    for (int i = tid; i < len; i += 256) seg[i] = 0.f;
-                }
-                if (tid == 0) found = 0;
-                __syncthreads();
-                int mine = 0;
-                for (long j = p + tid; j < e0; j += 256) {
-                    const long c = a.indices[j];
-                    if (c >= c1) break;
-                    ++mine;
-                    if (c < 0 || c >= a.G) { ++bad; continue; }
-                    const long k = c - c0;
-                    if (k >= 0 && k < len) seg[k] = a.values[j];
-                }
-                if (mine) atomicAdd(&found, mine);
-                __syncthreads();
-                p += found;
-                if (p > e0) p = e0;
-                if (V == 4) {
-                    for (int i = tid; i < (len >> 2); i += 256) {
-                        const float4 y = reinterpret_cast<const float4*>(seg)[i];
-                        const long col = c0 + 4 * i;
-                        float4 x;
-                        x.x = gather_x(y.x, t0, f, a, col);
-                        x.y = gather_x(y.y, t0, f, a, col + 1);
-                        x.z = gather_x(y.z, t0, f, a, col + 2);
-                        x.w = gather_x(y.w, t0, f, a, col + 3);
-                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
-                    }
-                } else {
-                    for (int i = tid; i < len; i += 256) xrow[c0 + i] = gather_x(seg[i], t0, f, a, c0 + i);
-                }
+                const int len = seg_len(a.ldx, c0, kCsrSeg);
+                seg_clear<float, V>(seg, len, tid);
+                p = seg_scatter(a.indices, p, w.e0, c0, seg_end(a.ldx, c0, kCsrSeg), len, a.G, tid, bad, found,
+                                [&](long k, long j) { seg[k] = a.values[j]; });
+                seg_store_x<V>(xrow + c0, seg, len, c0, t0, f, a, tid);
                 __syncthreads();
             }
         }
         float* yrow = a.Y + (long)r * a.ldy;
         for (long c0 = 0; c0 < a.ldy; c0 += kCsrSeg) {
-            const int len = (int)(a.ldy - c0 < kCsrSeg ? a.ldy - c0 : kCsrSeg);
+            const int len = seg_len(a.ldy, c0, kCsrSeg);
             const bool count = c0 == 0;
-            if (V == 4) {
-                for (int i = tid; i < (len >> 2); i += 256) reinterpret_cast<float4*>(seg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                for (int i = tid; i < len; i += 256) seg[i] = 0.f;
-            }
+            seg_clear<float, V>(seg, len, tid);
             __syncthreads();
-            for (long j = s0 + tid; j < e0; j += 256) {
+            for (long j = w.s0 + tid; j < w.e0; j += 256) {
                 const long c = a.indices[j];
                 if (c < 0 || c >= a.G) { if (count && !a.X) ++bad; continue; }
                 const long o = ca.col_out[c];
@@ -424,12 +412,7 @@ __global__ __launch_bounds__(256) void csr_gather_cols_kernel(GatherColsArgs ca)
                 if (o >= 0 && k >= 0 && k < len) seg[k] = a.values[j];
             }
             __syncthreads();
-            if (V == 4) {
-                for (int i = tid; i < (len >> 2); i += 256)
-                    reinterpret_cast<float4*>(yrow + c0)[i] = reinterpret_cast<const float4*>(seg)[i];
-            } else {
-                for (int i = tid; i < len; i += 256) yrow[c0 + i] = seg[i];
-            }
+            seg_store<float, V>(yrow + c0, seg, len, tid);
             __syncthreads();
         }
     }
@@ -460,107 +443,61 @@ __device__ inline int lane_rank64(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// One workgroup per destination row, LDS column segments as in csr_gather_kernel.  XV = 0: no X tile, the segment holds
-// the bytes themselves (four times the columns per segment); XV = 4 / 1: the segment holds the fp32 counts, X is written
-// from them as csr_gather_kernel writes it (V-float stores) and the bytes are coded on the way out.  16-byte stores of Yc.
+// XV = 0: no X tile, the segment holds the bytes themselves (four times the columns per segment); XV = 4 / 1: the segment
+// holds the fp32 counts, X is written from them as csr_gather_kernel writes it and the bytes are coded on the way out.
+// 16-byte stores of Yc (ldc % 16 == 0; ldx % 4 == 0 where XV = 4).
 template <int XV>
 __global__ __launch_bounds__(256) void csr_gather_compact_kernel(CompactGatherArgs a) {
     using T = typename std::conditional<XV != 0, float, unsigned char>::type;
     constexpr int kSeg = XV ? kCsrSeg : kCsrSegB;
+    constexpr int CV = XV == 1 ? 1 : 4;
     __shared__ __attribute__((aligned(16))) T seg[kSeg];
     __shared__ int found, nesc;
     const GatherArgs& g = a.g;
     const int tid = threadIdx.x;
     int bad = 0;
-    const long base = g.perm ? (long)*g.cursor : g.row0;
+    const long base = gather_base(g);
     const long L = (XV && g.ldx > a.ldc) ? g.ldx : a.ldc;
     for (int r = blockIdx.x; r < g.B; r += gridDim.x) {
-        const long row = g.perm ? (long)g.perm[base + r] : base + r;
-        const bool ok = row >= 0 && row < g.n;
-        long s = 0, e = 0;
-        if (ok) { s = g.indptr[row]; e = g.indptr[row + 1]; }
-        const long s0 = s < 0 ? 0 : (s > g.nnz ? g.nnz : s);
-        const long e0 = e < s0 ? s0 : (e > g.nnz ? g.nnz : e);
-        if (tid == 0 && (!ok || s0 != s || e0 != e)) ++bad;
-        const float f = (g.fac && ok) ? g.fac[row] : 1.f;
-        float t0 = 0.f;
-        if (XV) {
-            if (g.fac) t0 = __fdiv_rn(t0, f);
-            if (g.do_log) t0 = log1pf(t0);
-        }
+        const RowSpan w = row_span(g, base, r, tid, bad);
+        float t0;
+        const float f = row_factor(g, w, r, tid, XV != 0, t0);
         if (tid == 0) {
-            if (g.sf_out) g.sf_out[r] = (ok && g.sf) ? g.sf[row] : 0.f;
             if (a.fac_out) a.fac_out[r] = f;
             nesc = 0;                   // (the first segment's barrier orders it before the row's additions)
         }
-        long p = s0;
+        long p = w.s0;
         unsigned char* crow = a.Yc + (long)r * a.ldc;
         float* xrow = (XV && g.X) ? g.X + (long)r * g.ldx : nullptr;
         for (long c0 = 0; c0 < L; c0 += kSeg) {
-            const int len = (int)(L - c0 < kSeg ? L - c0 : kSeg);
-            const long c1 = c0 + kSeg < L ? c0 + kSeg : (1L << 40);
-            if (XV == 1) {
-                for (int i = tid; i < len; i += 256) seg[i] = T(0);
-            } else {                    // len * sizeof(T) is a multiple of 16 (ldc % 16 == 0, ldx % 4 == 0)
-                const int nq = (int)((len * sizeof(T)) >> 4);
-                for (int i = tid; i < nq; i += 256) reinterpret_cast<uint4*>(seg)[i] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            if (tid == 0) found = 0;
-            __syncthreads();
-            int mine = 0, esc = 0;
-            for (long j = p + tid; j < e0; j += 256) {
-                const long c = g.indices[j];
-                if (c >= c1) break;
-                ++mine;
-                if (c < 0 || c >= g.G) { ++bad; continue; }
-                const long k = c - c0;
-                if (k >= 0 && k < len) {
-                    const float v = g.values[j];
-                    const unsigned code = count_code(v, bad);
-                    esc += code == 255u;
-                    if (XV) seg[k] = (T)v; else seg[k] = (T)code;
-                }
-            }
-            if (mine) atomicAdd(&found, mine);
-            if (esc) atomicAdd(&nesc, esc);
-            __syncthreads();
-            p += found;
-            if (p > e0) p = e0;
-            const int lb = (int)(a.ldc - c0 < len ? (a.ldc - c0 > 0 ? a.ldc - c0 : 0) : len);
+            const int len = seg_len(L, c0, kSeg);
+            seg_clear<T, CV>(seg, len, tid);
+            int esc = 0;
+            p = seg_scatter(g.indices, p, w.e0, c0, seg_end(L, c0, kSeg), len, g.G, tid, bad, found, [&](long k, long j) {
+                const float v = g.values[j];
+                const unsigned code = count_code(v, bad);
+                esc += code == 255u;
+                if (XV) seg[k] = (T)v; else seg[k] = (T)code;
+            });
+            if (esc) atomicAdd(&nesc, esc);     // (before the segment's last barrier, which the row's end reads it behind)
+            const int lb = seg_part(a.ldc, c0, len);
             if (XV == 0) {
-                for (int i = tid; i < (lb >> 4); i += 256)
-                    reinterpret_cast<uint4*>(crow + c0)[i] = reinterpret_cast<const uint4*>(seg)[i];
+                seg_store<unsigned char, 4>(crow + c0, reinterpret_cast<const unsigned char*>(seg), lb, tid);
             } else {
                 for (int i = tid; i < (lb >> 4); i += 256) {
-                    unsigned w[4];
+                    unsigned q4[4];
                     int skip = 0;       // (what is not a count was counted when it was scattered)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float4 y = reinterpret_cast<const float4*>(seg)[4 * i + q];
-                        w[q] = count_code(y.x, skip) | count_code(y.y, skip) << 8 | count_code(y.z, skip) << 16 |
-                               count_code(y.w, skip) << 24;
+                        q4[q] = count_code(y.x, skip) | count_code(y.y, skip) << 8 | count_code(y.z, skip) << 16 |
+                                count_code(y.w, skip) << 24;
                     }
-                    reinterpret_cast<uint4*>(crow + c0)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+                    reinterpret_cast<uint4*>(crow + c0)[i] = make_uint4(q4[0], q4[1], q4[2], q4[3]);
                 }
             }
-            if (XV && xrow) {
-                const float* fs = reinterpret_cast<const float*>(seg);
-                const int lx = (int)(g.ldx - c0 < len ? (g.ldx - c0 > 0 ? g.ldx - c0 : 0) : len);
-                if (XV == 4) {
-                    for (int i = tid; i < (lx >> 2); i += 256) {
-                        const float4 y = reinterpret_cast<const float4*>(fs)[i];
-                        const long col = c0 + 4 * i;
-                        float4 x;
-                        x.x = gather_x(y.x, t0, f, g, col);
-                        x.y = gather_x(y.y, t0, f, g, col + 1);
-                        x.z = gather_x(y.z, t0, f, g, col + 2);
-                        x.w = gather_x(y.w, t0, f, g, col + 3);
-                        reinterpret_cast<float4*>(xrow + c0)[i] = x;
-                    }
-                } else {
-                    for (int i = tid; i < lx; i += 256) xrow[c0 + i] = gather_x(fs[i], t0, f, g, c0 + i);
-                }
-            }
+            if (XV && xrow)
+                seg_store_x<CV>(xrow + c0, reinterpret_cast<const float*>(seg), seg_part(g.ldx, c0, len), c0, t0, f, g, tid);
             __syncthreads();
         }
         if (tid == 0) {
@@ -610,12 +547,10 @@ __global__ __launch_bounds__(256) void csr_gather_ovf_kernel(CompactGatherArgs a
     if (r >= g.B) return;
     const int lo = a.ovf_ptr[r], hi = min(a.ovf_ptr[r + 1], a.cap);
     if (lo < 0 || hi <= lo) return;
-    const long base = g.perm ? (long)*g.cursor : g.row0;
-    const long row = g.perm ? (long)g.perm[base + r] : base + r;
-    if (row < 0 || row >= g.n) return;
-    const long s = g.indptr[row], e = g.indptr[row + 1];
-    const long s0 = s < 0 ? 0 : (s > g.nnz ? g.nnz : s);
-    const long e0 = e < s0 ? s0 : (e > g.nnz ? g.nnz : e);
+    int skip = 0;                       // (the gather counted what is wrong with the row and its entries)
+    const RowSpan w = row_span(g, gather_base(g), r, lane, skip);
+    if (!w.ok) return;
+    const long s0 = w.s0, e0 = w.e0;
     int pos = lo;
     for (long j0 = s0; j0 < e0 && pos < hi; j0 += 64) {
         const long j = j0 + lane;
@@ -626,7 +561,6 @@ __global__ __launch_bounds__(256) void csr_gather_ovf_kernel(CompactGatherArgs a
             c = g.indices[j];
             if (c >= 0 && c < g.G) {
                 v = g.values[j];
-                int skip = 0;
                 is = count_code(v, skip) == 255u;
             }
         }
@@ -912,6 +846,25 @@ __global__ __launch_bounds__(256) void csr_subset_kernel(SubsetArgs a) {
     if (bad) atomicAdd(a.status, bad);
 }
 
+// What the three dcahip_csr_gather* entries require alike of their arguments, and the GatherArgs made of them (Y / ldy: the
+// fp32 count tile, which each entry checks itself).  False: DCAHIP_EINVAL.
+bool gather_args(const long* indptr, const int* indices, const float* values, long nnz, int n, int G, const int* perm,
+                 const long long* cursor, long row0, int B, const float* sf, const float* fac, int do_log, const float* mean,
+                 const float* stdv, float* Y, long ldy, float* X, long ldx, float* sf_out, int* status, GatherArgs* a) {
+    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || !status || !indptr || (nnz > 0 && (!indices || !values))) return false;
+    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf)) return false;
+    *a = GatherArgs{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
+                    Y, ldy, X, X ? ldx : 0, sf_out, status};
+    return true;
+}
+
+inline int gather_grid(int B) { return B < 16384 ? B : 16384; }     // one workgroup per destination row, grid-stride beyond
+
+// V-float stores of both fp32 tiles
+inline bool gather_vec(const GatherArgs& a) {
+    return al16(a.Y) && (a.ldy & 3) == 0 && (!a.X || (al16(a.X) && (a.ldx & 3) == 0));
+}
+
 }  // namespace
 
 extern "C" int dcahip_csr_compress(const float* X, long ld, int rows, int G, long base, long* indptr, int* indices,
@@ -1029,17 +982,14 @@ extern "C" int dcahip_csr_gather(const long* indptr, const int* indices, const f
                                  const int* perm, const long long* cursor, long row0, int B, const float* sf,
                                  const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
                                  float* X, long ldx, float* sf_out, int* status, void* stream) {
-    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || ldy < G || !status || !Y || !indptr) return DCAHIP_EINVAL;
-    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
-    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf)) return DCAHIP_EINVAL;
+    GatherArgs a;
+    if (ldy < G || !Y || !gather_args(indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
+                                      Y, ldy, X, ldx, sf_out, status, &a))
+        return DCAHIP_EINVAL;
     if (B == 0) return 0;
-    GatherArgs a{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
-                 Y, ldy, X, X ? ldx : 0, sf_out, status};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = B < 16384 ? B : 16384;
-    const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
-    if (vec) hipLaunchKernelGGL(csr_gather_kernel<4>, dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(csr_gather_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    if (gather_vec(a)) hipLaunchKernelGGL(csr_gather_kernel<4>, dim3(gather_grid(B)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(csr_gather_kernel<1>, dim3(gather_grid(B)), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 
@@ -1048,18 +998,15 @@ extern "C" int dcahip_csr_gather_cols(const long* indptr, const int* indices, co
                                       const float* fac, int do_log, const float* mean, const float* stdv, float* Y, long ldy,
                                       float* X, long ldx, float* sf_out, int* status, const int* col_out, int G_out,
                                       void* stream) {
-    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || !col_out || G_out <= 0 || ldy < G_out || !status || !Y || !indptr)
+    GatherColsArgs a{{}, col_out, G_out};
+    if (!col_out || G_out <= 0 || ldy < G_out || !Y ||
+        !gather_args(indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv, Y, ldy, X, ldx,
+                     sf_out, status, &a.g))
         return DCAHIP_EINVAL;
-    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
-    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf)) return DCAHIP_EINVAL;
     if (B == 0) return 0;
-    GatherColsArgs a{{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
-                      Y, ldy, X, X ? ldx : 0, sf_out, status}, col_out, G_out};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = B < 16384 ? B : 16384;
-    const bool vec = al16(Y) && (ldy & 3) == 0 && (!X || (al16(X) && (ldx & 3) == 0));
-    if (vec) hipLaunchKernelGGL(csr_gather_cols_kernel<4>, dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(csr_gather_cols_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+    if (gather_vec(a.g)) hipLaunchKernelGGL(csr_gather_cols_kernel<4>, dim3(gather_grid(B)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(csr_gather_cols_kernel<1>, dim3(gather_grid(B)), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 
@@ -1068,18 +1015,14 @@ extern "C" int dcahip_csr_gather_compact(const long* indptr, const int* indices,
                                          const float* fac, int do_log, const float* mean, const float* stdv,
                                          unsigned char* Yc, long ldc, int* ovf_ptr, int* ovf_col, float* ovf_val, int ovf_cap,
                                          float* X, long ldx, float* sf_out, float* fac_out, int* status, void* stream) {
-    if (n < 0 || G <= 0 || B < 0 || nnz < 0 || ldc < G || (ldc & 15) || !status || !Yc || !al16(Yc) || !indptr)
+    CompactGatherArgs a{{}, Yc, ldc, ovf_ptr, ovf_col, ovf_val, ovf_ptr ? ovf_cap : 0, fac_out};
+    if (ldc < G || (ldc & 15) || !Yc || !al16(Yc) || (fac_out && !fac) || (ovf_ptr && (!ovf_col || !ovf_val || ovf_cap <= 0)) ||
+        !gather_args(indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv, nullptr, 0, X, ldx,
+                     sf_out, status, &a.g))
         return DCAHIP_EINVAL;
-    if (nnz > 0 && (!indices || !values)) return DCAHIP_EINVAL;
-    if ((perm && !cursor) || (!perm && row0 < 0) || (X && ldx < G) || (!mean != !stdv) || (sf_out && !sf) || (fac_out && !fac))
-        return DCAHIP_EINVAL;
-    if (ovf_ptr && (!ovf_col || !ovf_val || ovf_cap <= 0)) return DCAHIP_EINVAL;
     if (B == 0) return 0;
-    CompactGatherArgs a{{indptr, indices, values, nnz, n, G, perm, cursor, row0, B, sf, fac, do_log, mean, stdv,
-                         nullptr, 0, X, X ? ldx : 0, sf_out, status},
-                        Yc, ldc, ovf_ptr, ovf_col, ovf_val, ovf_ptr ? ovf_cap : 0, fac_out};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = B < 16384 ? B : 16384;
+    const int grid = gather_grid(B);
     if (!X) hipLaunchKernelGGL(csr_gather_compact_kernel<0>, dim3(grid), dim3(256), 0, s, a);
     else if (al16(X) && (ldx & 3) == 0) hipLaunchKernelGGL(csr_gather_compact_kernel<4>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(csr_gather_compact_kernel<1>, dim3(grid), dim3(256), 0, s, a);

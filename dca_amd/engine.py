@@ -72,6 +72,16 @@ def _r16(x):
     return (x + 15) // 16 * 16
 
 
+def _d_exp_of_histogram(cnt, numel):
+    """Engine._heads_d_exp from the histogram cnt of numel sampled counts: the count c that one element in 20 000 exceeds
+    -> the exponent at which |g| <~ 2 c fits K-HEADS' fp16 gradient pieces."""
+    tail = torch.flip(torch.cumsum(torch.flip(cnt, [0]), 0), [0]).to(torch.float64) / float(numel)     # P(y >= c)
+    over = torch.nonzero(tail > 5e-5)
+    c = float(over.max().item()) if over.numel() else 0.0
+    need = 2.0 * c / 117.0
+    return 0 if need <= 1.0 else -min(24, int(np.ceil(np.log2(need))))
+
+
 class _NullSection:
     def __enter__(self):
         return self
@@ -712,12 +722,12 @@ class Engine:
             # the byte tile: B x r16(G) bytes, the overflow list of the B rows with the most escapes, and -- when the first
             # layer reads it (one escape in 1e5 counts at most, a width its kernels take) -- 1 KB of table per tile cell
             from . import compact as _compact
-            lay, ops, v, nm = self.lay, self.ops, self.cc_csr, self.norm_c
+            lay, ops, v = self.lay, self.ops, self.cc_csr
             self.cc = _compact.tile(ops, B, lay.G_out, v.capacity(B), self.dev)
             self.cc_in = None
             if lay.hidden and v.n_esc <= 1e-5 * float(self.csr.n) * lay.G_out and ops.enc0_sparse_supported(lay.hidden[0]):
-                self.cc_in = _compact.tile_with_input(ops, self.cc, nm.get('fac') is not None, nm.get('do_log', False),
-                                                      nm.get('mean'), nm.get('std'))
+                fac, do_log, mean, std = self._norm_args()
+                self.cc_in = _compact.tile_with_input(ops, self.cc, fac is not None, do_log, mean, std)
             self._sparse_workspaces()
 
     def _gather_step(self, B):
@@ -732,11 +742,8 @@ class Engine:
             if not (lut or sdw):
                 return
             need_x = False
-        nm, c = self.norm_c, self.cc
-        ci = self.cc_in if self.cc_in is not None else c
-        self.ops.csr_gather_compact(self.csr, self.perm, self.cursor, 0, B, self.sf_all, nm.get('fac'), nm.get('do_log', False),
-                                    nm.get('mean'), nm.get('std'), c.Yc, c.ldc, c.ovf_ptr, c.ovf_col, c.ovf_val,
-                                    self.X if need_x else None, self.ldx, self.sf, ci.fac, self.gather_status)
+        ci = self.cc_in if self.cc_in is not None else self.cc
+        self._csr_gather_compact(self.perm, self.cursor, 0, B, self.sf_all, ci, self.X if need_x else None, self.sf)
         if lut or sdw:                      # the table of the tile's cells, from the factors the gather just wrote
             self.ops.enc0_lut(ci.fac, ci.do_log, B, ci.lutp)
             self._tile_lut = True
@@ -744,20 +751,26 @@ class Engine:
     def _gather(self, B, row0=None):
         """Counts-resident mode: the tile of B rows -- perm[cursor + r] (row0 None: the training step's rows, read on the
         device) or the storage rows row0 + r."""
-        nm = self.norm_c
         perm, cur = (self.perm, self.cursor) if row0 is None else (None, None)
         self._csr_gather(perm, cur, 0 if row0 is None else row0, B, self.sf_all, self.Y, self.X, self.sf)
 
     def _csr_gather(self, perm, cur, row0, B, sf, Y, X, sf_out):
         """The fp32 tiles of B rows of the resident CSR: csr_gather, or csr_gather_cols when a gene subset is fitted."""
-        nm = self.norm_c
+        tiles = (Y, self.ldy, X, self.ldx, sf_out, self.gather_status)
         if self.col_out is not None:
-            self.ops.csr_gather_cols(self.csr, self.col_out, self.lay.G_out, perm, cur, row0, B, sf, nm.get('fac'),
-                                     nm.get('do_log', False), nm.get('mean'), nm.get('std'), Y, self.ldy, X, self.ldx,
-                                     sf_out, self.gather_status)
+            self.ops.csr_gather_cols(self.csr, self.col_out, self.lay.G_out, perm, cur, row0, B, sf, *self._norm_args(), *tiles)
         else:
-            self.ops.csr_gather(self.csr, perm, cur, row0, B, sf, nm.get('fac'), nm.get('do_log', False), nm.get('mean'),
-                                nm.get('std'), Y, self.ldy, X, self.ldx, sf_out, self.gather_status)
+            self.ops.csr_gather(self.csr, perm, cur, row0, B, sf, *self._norm_args(), *tiles)
+
+    def _csr_gather_compact(self, perm, cur, row0, B, sf, c, X, sf_out):
+        """The byte tile c (its bytes, its overflow list, its rows' factors) of B rows of the resident CSR, with the fp32 X
+        tile when X is given."""
+        self.ops.csr_gather_compact(self.csr, perm, cur, row0, B, sf, *self._norm_args(), c.Yc, c.ldc, c.ovf_ptr, c.ovf_col,
+                                    c.ovf_val, X, self.ldx, sf_out, c.fac, self.gather_status)
+
+    def _norm_args(self):
+        """(fac, do_log, mean, std) of the resident counts' normalisation, as every gather takes them."""
+        return _prep.norm_args(self.norm_c)
 
     def _range_rows(self, s, b):
         """Storage rows [s, s + b) of an inference pass: their first row in X / Y / sf -- s itself, or 0 once the
@@ -766,10 +779,8 @@ class Engine:
             return s
         self._gather(b, row0=s)
         if self._lut_fwd(b, False):         # the inference forward the dense form looks up from its byte store
-            nm, c = self.norm_c, self.cc_in
-            self.ops.csr_gather_compact(self.csr, None, None, s, b, None, nm.get('fac'), nm.get('do_log', False),
-                                        nm.get('mean'), nm.get('std'), c.Yc, c.ldc, c.ovf_ptr, c.ovf_col, c.ovf_val,
-                                        None, 0, None, c.fac, self.gather_status)
+            c = self.cc_in
+            self._csr_gather_compact(None, None, s, b, None, c, None, None)
             self.ops.enc0_lut(c.fac, c.do_log, b, c.lutp)
         return 0
 
@@ -866,22 +877,14 @@ class Engine:
             cnt = torch.bincount(torch.nan_to_num(v, nan=0.0).clamp(0, 65535.0).to(torch.int64), minlength=2)
             numel = int(sel.numel()) * self.lay.G_out
             cnt[0] += numel - int(v.numel())                  # the zeros the CSR does not store
-            tail = torch.flip(torch.cumsum(torch.flip(cnt, [0]), 0), [0]).to(torch.float64) / float(numel)
-            over = torch.nonzero(tail > 5e-5)
-            cc = float(over.max().item()) if over.numel() else 0.0
-            need = 2.0 * cc / 117.0
-            return 0 if need <= 1.0 else -min(24, int(np.ceil(np.log2(need))))
+            return _d_exp_of_histogram(cnt, numel)
         Y = self.Y
         if Y is None or not getattr(Y, 'is_cuda', False) or Y.numel() == 0:
             return 0
         rows = min(Y.shape[0], max(1, (1 << 24) // max(1, Y.shape[1])))
         samp = Y[:: max(1, Y.shape[0] // rows)][:rows, :self.lay.G_out]
         cnt = torch.bincount(torch.nan_to_num(samp, nan=0.0).clamp(0, 65535.0).to(torch.int64).reshape(-1), minlength=2)
-        tail = torch.flip(torch.cumsum(torch.flip(cnt, [0]), 0), [0]).to(torch.float64) / float(samp.numel())    # P(y >= c)
-        over = torch.nonzero(tail > 5e-5)
-        c = float(over.max().item()) if over.numel() else 0.0
-        need = 2.0 * c / 117.0
-        return 0 if need <= 1.0 else -min(24, int(np.ceil(np.log2(need))))
+        return _d_exp_of_histogram(cnt, samp.numel())
 
     def _h2(self, B):
         """The wide networks' plane products on fp16 x 2 planes (half the matrix instructions of the bf16 x 3 planes) at this
@@ -937,7 +940,7 @@ class Engine:
         # keeps the dense products (_sparse_dw / _lut_fwd test nothing else about the width)
         if norm is not None and lay.hidden and lay.G_in == lay.G_out and n_esc <= 1e-5 * n_el and \
                 ops.enc0_sparse_supported(lay.hidden[0]):
-            self.cc_in = compact.with_input(norm.get('fac'), norm.get('do_log', False), norm.get('mean'), norm.get('std'), ops=ops)
+            self.cc_in = compact.with_input(*_prep.norm_args(norm), ops=ops)
         self._sparse_workspaces()
 
     def _sparse_workspaces(self):

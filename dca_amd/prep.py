@@ -529,6 +529,12 @@ def csr_norm(ops, csr, fac, logtrans_input, normalize_input):
     return dict(fac=fac, do_log=bool(logtrans_input), mean=mean, std=std)
 
 
+def norm_args(norm):
+    """(fac, do_log, mean, std) of a normalisation dict (csr_norm, transform(return_norm=True)): the operands the gather
+    entries and the byte store's description of the network input take, in their order."""
+    return norm.get('fac'), norm.get('do_log', False), norm.get('mean'), norm.get('std')
+
+
 def download_csr(ops, csr, norm, chunk_rows=2048):
     """The normalised input X of counts held as CSR -> new host array [n, G]: row ranges gathered into one device tile and
     copied down (the dense matrix is never resident on the device)."""
@@ -544,8 +550,7 @@ def download_csr(ops, csr, norm, chunk_rows=2048):
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     for s in range(0, n, b):
         e = min(n, s + b)
-        ops.csr_gather(csr, None, None, s, e - s, None, norm.get('fac'), norm.get('do_log', False), norm.get('mean'),
-                       norm.get('std'), Yt, ld, Xt, ld, None, status)
+        ops.csr_gather(csr, None, None, s, e - s, None, *norm_args(norm), Yt, ld, Xt, ld, None, status)
         out[s:e] = Xt[:e - s, :G].cpu().numpy()
     return out
 

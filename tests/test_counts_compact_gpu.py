@@ -28,17 +28,21 @@ def _bits(t):
     return t.detach().contiguous().cpu().numpy().view(np.uint32)
 
 
-def _counts(n, G, density, seed, empty=(), big=()):
+def _counts(n, G, density, seed, empty=(), big=(), last=None):
+    """Random counts; the rows of `empty` (those the matrix has) store nothing, row `last` stores the last column."""
     rng = np.random.default_rng(seed)
     Y = sp.random(n, G, density=density, format='csr', dtype=np.float32, random_state=seed,
                   data_rvs=lambda k: rng.integers(1, 40, k).astype(np.float32))
     Y = Y.tolil()
-    for r in empty:
-        Y[r, :] = 0
+    if last is not None:
+        Y[last, G - 1] = 7
     for k, v in enumerate(big):                               # escapes: several in one row, first / last column included
         Y[(3 * k) % n if k % 2 else 1, (k * 7919) % G if k else G - 1] = v
     if big:
         Y[1, 0] = big[0]
+    for r in empty:
+        if r < n:
+            Y[r, :] = 0
     Y = Y.tocsr()
     Y.eliminate_zeros()
     return Y
@@ -124,12 +128,14 @@ def _equal(t, cc, X, so, fac_rows):
 BIG = (255., 256., 5000., 70000., 254., 300.)
 
 
+# G = 8065: one fp32 LDS segment and a 4-float tail; 32256: exactly one byte segment; 32257: one and a 16-byte tail
 @pytest.mark.parametrize('n, G, big', [(60, 1001, ()), (40, 9001, ()), (60, 1001, BIG), (40, 9001, BIG), (24, 33001, BIG),
-                                       (30, 1024, BIG)])
+                                       (30, 1024, BIG), (5, 8065, BIG), (5, 32256, ()), (5, 32257, BIG)])
 @pytest.mark.parametrize('use_fac, do_log, scale', [(f, l, s) for f in (0, 1) for l in (0, 1) for s in (0, 1)])
 def test_tile_equals_the_dense_stores_rows(ops, n, G, big, use_fac, do_log, scale):
     dev = torch.device('cuda')
-    Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1), big=big)
+    Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1), big=big, last=2)
+    assert Ys[2, G - 1] != 0 and Ys[0].nnz == 0
     csr = prep.upload_csr(Ys, dev, ops)
     ld = prep._r4(G)
     rng = np.random.default_rng(1)
@@ -145,7 +151,8 @@ def test_tile_equals_the_dense_stores_rows(ops, n, G, big, use_fac, do_log, scal
     v = compact.csr_verdict(csr)
     assert not v.bad and v.n_esc == int((Ys.data >= 255).sum())
     perm = rng.permutation(n)
-    for rows, perm_mode in ((perm, True), (perm[:1], True), (np.arange(5, n), False), (np.arange(n - 1, n), False)):
+    for rows, perm_mode in ((perm, True), (perm[:1], True), (np.arange(min(5, n - 2), n), False),
+                            (np.arange(n - 1, n), False)):
         B = len(rows)
         cap = v.capacity(B)
         idx = torch.as_tensor(rows, device=dev)

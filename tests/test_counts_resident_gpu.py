@@ -31,13 +31,17 @@ def _bits(t):
     return t.detach().contiguous().cpu().numpy().view(np.uint32)
 
 
-def _counts(n, G, density, seed, empty=()):
+def _counts(n, G, density, seed, empty=(), last=None):
+    """Random counts; the rows of `empty` (those the matrix has) store nothing, row `last` stores the last column."""
     rng = np.random.default_rng(seed)
     Y = sp.random(n, G, density=density, format='csr', dtype=np.float32, random_state=seed,
                   data_rvs=lambda k: rng.integers(1, 40, k).astype(np.float32))
     Y = Y.tolil()
+    if last is not None:
+        Y[last, G - 1] = 7
     for r in empty:
-        Y[r, :] = 0
+        if r < n:
+            Y[r, :] = 0
     Y = Y.tocsr()
     Y.eliminate_zeros()
     return Y
@@ -79,11 +83,13 @@ def _gather(ops, csr, rows_or_perm, B, sf, fac, do_log, mean, std, ld, perm_mode
     return Yt[1:B + 1], Xt[1:B + 1], so[1:B + 1], int(st.item())
 
 
-@pytest.mark.parametrize('n, G', [(60, 1001), (40, 9001)])
+# G = 8064: exactly one LDS segment of the gather kernels; 8065: one segment and a 4-float tail; 16129: two and a tail
+@pytest.mark.parametrize('n, G', [(60, 1001), (40, 9001), (5, 8064), (5, 8065), (5, 16129)])
 @pytest.mark.parametrize('use_fac, do_log, scale', [(f, l, s) for f in (0, 1) for l in (0, 1) for s in (0, 1)])
 def test_csr_gather_equals_the_dense_preprocessing(ops, n, G, use_fac, do_log, scale):
     dev = torch.device('cuda')
-    Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1))
+    Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1), last=2)
+    assert Ys[2, G - 1] != 0 and Ys[0].nnz == 0
     csr = prep.upload_csr(Ys, dev, ops)
     ld = prep._r4(G)
     rng = np.random.default_rng(1)
@@ -97,7 +103,8 @@ def test_csr_gather_equals_the_dense_preprocessing(ops, n, G, use_fac, do_log, s
         std[:G] = torch.as_tensor(rng.uniform(0.5, 3, G).astype(np.float32))
     sf = torch.as_tensor(rng.uniform(0.1, 9, n).astype(np.float32), device=dev)
     perm = rng.permutation(n)
-    for rows, perm_mode in ((perm, True), (perm[:1], True), (np.arange(5, n), False), (np.arange(n - 1, n), False)):
+    for rows, perm_mode in ((perm, True), (perm[:1], True), (np.arange(min(5, n - 2), n), False),
+                            (np.arange(n - 1, n), False)):
         B = len(rows)
         Yg, Xg, sg, bad = _gather(ops, csr, rows if perm_mode else int(rows[0]), B, sf, fac, do_log, mean, std, ld, perm_mode)
         assert bad == 0

@@ -26,13 +26,17 @@ def _bits(t):
     return t.detach().contiguous().cpu().numpy().view(np.uint32)
 
 
-def _counts(n, G, density, seed, empty=()):
+def _counts(n, G, density, seed, empty=(), last=None):
+    """Random counts; the rows of `empty` (those the matrix has) store nothing, row `last` stores the last column."""
     rng = np.random.default_rng(seed)
     Y = sp.random(n, G, density=density, format='csr', dtype=np.float32, random_state=seed,
                   data_rvs=lambda k: rng.integers(1, 40, k).astype(np.float32))
     Y = Y.tolil()
+    if last is not None:
+        Y[last, G - 1] = 7
     for r in empty:
-        Y[r, :] = 0
+        if r < n:
+            Y[r, :] = 0
     Y = Y.tocsr()
     Y.eliminate_zeros()
     return Y
@@ -76,7 +80,8 @@ def _problem(ops, n, G):
     """The counts, their CSR on the device, the normalisation operands and the gathers' row sets -- made once per shape."""
     if (n, G) not in _PROBLEMS:
         dev = torch.device('cuda')
-        Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1))
+        Ys = _counts(n, G, 0.05, seed=G + n, empty=(0, 7, n - 1), last=2)
+        assert Ys[2, G - 1] != 0 and Ys[0].nnz == 0
         csr = prep.upload_csr(Ys, dev, ops)
         ld = prep._r4(G)
         rng = np.random.default_rng(1)
@@ -101,7 +106,7 @@ def _problem(ops, n, G):
                    'identity': np.arange(G)}
         if G > 8500:
             subsets['k8500'] = shuffled(8500)                       # more output columns than one LDS segment holds
-        row_sets = {'perm': (perm, True), 'one_row': (perm[:1], True), 'range': (np.arange(5, n), False)}
+        row_sets = {'perm': (perm, True), 'one_row': (perm[:1], True), 'range': (np.arange(min(5, n - 2), n), False)}
         _PROBLEMS[(n, G)] = dict(Ys=Ys, csr=csr, ld=ld, fac=fac, mean=mean, std=std, sf=sf, subsets=subsets,
                                  row_sets=row_sets, plain={})
     return _PROBLEMS[(n, G)]
@@ -147,7 +152,8 @@ def _check_against_plain(ops, pr, G, subset, opt, rs, offset=0):
 ALL_OPTIONS = [(f, l, s) for f in (0, 1) for l in (0, 1) for s in (0, 1)]
 
 
-@pytest.mark.parametrize('n, G', [(60, 1001), (40, 9001)])
+# G = 8064: exactly one LDS segment of the gather kernels; 8065: one segment and a 4-float tail; 16129: two and a tail
+@pytest.mark.parametrize('n, G', [(60, 1001), (40, 9001), (5, 8064), (5, 8065), (5, 16129)])
 @pytest.mark.parametrize('opt', ALL_OPTIONS)
 def test_gather_cols_equals_csr_gather_on_37_shuffled_genes(ops, n, G, opt):
     pr = _problem(ops, n, G)
