@@ -243,7 +243,9 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(const float* entri
 __global__ __launch_bounds__(64) void stack_sums_combine_kernel(const float* part, int E, int H, float* out, float* dbeta) {
     const int c = threadIdx.x;
     if (c >= H) return;
-    float v1 = 0.f, v2 = 0.f;
+    // the order of stack_bwd_step_kernel's own merge (entry e in row lane e % 4, the lanes added pairwise): ONE rank of a
+    // data-parallel step computes the bits of the single-GPU step
+    float l1[4] = {0.f, 0.f, 0.f, 0.f}, l2[4] = {0.f, 0.f, 0.f, 0.f};
     for (int e0 = 0; e0 < E; e0 += 8) {
         float a1[8], a2[8];
 #pragma unroll
@@ -252,8 +254,9 @@ __global__ __launch_bounds__(64) void stack_sums_combine_kernel(const float* par
             a1[u] = part[(eo + 0) * H + c]; a2[u] = part[(eo + 1) * H + c];
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) if (e0 + u < E) { v1 += a1[u]; v2 += a2[u]; }
+        for (int u = 0; u < 8; ++u) if (e0 + u < E) { l1[u & 3] += a1[u]; l2[u & 3] += a2[u]; }
     }
+    const float v1 = (l1[0] + l1[1]) + (l1[2] + l1[3]), v2 = (l2[0] + l2[1]) + (l2[2] + l2[3]);
     out[c] = v1; out[H + c] = v2;
     if (dbeta) dbeta[c] = v1;
 }
@@ -1557,9 +1560,13 @@ __global__ __launch_bounds__(256) void stack_fwd_step_kernel(StepFwdArgs a) {
     float out_z[kStepRows / 4];
     int Hs = H;                                            // width of the layer whose block statistics this launch writes
     if (!a.stats_only) {
-        const float* const ein = a.ext_in ? a.ext_in : a.part_in;      // whose statistics: every rank's, or this launch grid's
-        const float* const cnt = a.ext_in ? a.ext_counts : nullptr;
-        const int Em = a.ext_in ? a.ext_E : E;
+        // whose statistics: every rank's, or this launch grid's.  ONE entry that counts exactly this rank's rows is this
+        // rank's own stat_out (a world of one): the block statistics it was rounded from are still in the workspace, and
+        // merging those computes the bits of the single-GPU step.  An entry with any other count is taken as handed in.
+        const bool ext = a.ext_in && !(a.ext_E == 1 && a.ext_counts[0] == (float)a.B);      // (uniform)
+        const float* const ein = ext ? a.ext_in : a.part_in;
+        const float* const cnt = ext ? a.ext_counts : nullptr;
+        const int Em = ext ? a.ext_E : E;
         float pm[32], pq[32];
 #pragma unroll
         for (int u = 0; u < 32; ++u) {
@@ -1587,7 +1594,7 @@ __global__ __launch_bounds__(256) void stack_fwd_step_kernel(StepFwdArgs a) {
                 if (e < Em && c < H) {
                     const double ne = entry_count(cnt, e, Em, a.B);
                     const double me = (double)ein[((long)e * 2 + 0) * H + cc], qe = (double)ein[((long)e * 2 + 1) * H + cc];
-                    n += ne; sw += ne * me; sq += qe + ne * me * me;
+                    n += ne; sw += ne * me; sq += ne > 0.0 ? qe + ne * me * me : 0.0;
                 }
             }
         }

@@ -416,12 +416,18 @@ int dcahip_hidden_stack_bwd(const dcahip_stack_bwd_layer* layers, int n, int B, 
  * quantity of the step's input layer handed in from outside and the one the step produces merged over this rank's row
  * blocks for the exchange that follows:
  *   forward, step s = 0..n: s = 0 only measures layer 0; s >= 1 normalises layer s - 1 with ext_entries [ext_E][2][H]
- *     (mean, M2 per rank) and ext_counts [ext_E] (rows per rank), applies the activation, multiplies by the next layer's
+ *     (mean, M2 per rank) and ext_counts [ext_E] (rows per rank; an entry with count 0 -- a rank without rows -- is IGNORED,
+ *     whatever its mean and M2 hold), applies the activation, multiplies by the next layer's
  *     kernel; stat_out [2][H'] <- (mean, M2) of this rank's rows of the layer made (all-gather it; NULL after the last).
  *   backward, step s = 0..n: s = 0 only sums the top layer; s >= 1 handles layer n - s with ext_sums [2][H] (sum dy,
  *     sum dy xhat over ALL ranks, all-reduced); sums_out [2][K] <- this rank's sums of the layer below (all-reduce them),
  *     whose first half is also stored as that layer's LOCAL d beta.  The weight-gradient reduction is step n + 1 of
  *     dcahip_hidden_stack_bwd (rows_per_wg = 32), unchanged.
+ *   ONE rank that holds the whole batch computes the bits of the single-GPU steps at 32 rows per workgroup: ONE entry
+ *   whose count equals B is taken as this rank's own stat_out, and the forward merges the block statistics the previous
+ *   call left in the workspace -- what that entry was rounded from -- instead (so the workspace must be untouched
+ *   between the calls of a pass, as for dcahip_hidden_stack_fwd); one entry with any other count (a batch merged
+ *   elsewhere) is used as handed in.  The backward sums are added in the step kernel's order.
  * dcahip_hidden_stack_step_blocks(B): workgroups (= row blocks) of these launches. */
 int dcahip_hidden_stack_step_blocks(int B);
 int dcahip_hidden_stack_fwd_sync(const dcahip_small_layer* layers, int n, int B, float momentum, float eps, int act,
