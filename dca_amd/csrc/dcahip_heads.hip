@@ -43,9 +43,13 @@
 //   * per (row tile, gene tile):
 //       F   pre-activations  A = H W + b        32 rows x 32 genes x heads, K = 64
 //       Z   NLL + d NLL / d A   element-wise, through a wave-private fp32 LDS staging tile (the y = 0
-//           formulas densely, the non-zero elements compacted into 64-lane batches)
-//       dH  = D W^T   (D read transposed from the staging tile, split on the fly) -> partial per gene tile
-//       dW += H^T D   (a lane's staged D column IS its B operand)
+//           formulas densely, the non-zero elements compacted into 64-lane batches); the gradient D is split ONCE, here,
+//           into its two fp16 pieces, which replace the pre-activations in their cells
+//       dW += H^T D   (a lane's D column, as the cells hold it, IS its B operand)
+//       dH  = D W^T   (the D pieces read transposed from the cells) -> partial per workgroup and row tile
+//     dW and dH both only read the cells, so their order is free: dW comes first, and the workgroup's dH partial of the
+//     row tile (8 KB from beyond L2) is requested right after Z into the registers of the dH accumulators -- a whole
+//     matrix phase ahead of the products that start from it.
 //     No workgroup barrier inside the loop: waves drift apart, one wave's element-wise phase runs beside
 //     its SIMD partner's matrix phases.
 //   * HBM traffic per element: y (1 B from the byte store) + the dH partial instead of 36 B for materialised
@@ -142,9 +146,14 @@ __device__ __forceinline__ int block_exp(float m) {
     const int e = kTop + 1 - __builtin_amdgcn_frexp_expf(m);          // frexp: m = f 2^k, f in [0.5, 1)
     return e < -60 ? -60 : (e > 60 ? 60 : e);
 }
+// (the lane index is made opaque HERE: the six partner indices are then computed where the maximum is taken -- as loop
+// invariants they would each hold a register for the lifetime of the kernel, through every matrix phase)
 __device__ __forceinline__ float wave_max(float v) {
+    int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1)
+        v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_bpermute((l ^ off) << 2, __float_as_int(v))));
     return v;
 }
 
@@ -406,22 +415,29 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         const int ha_lane = l31 * 128 + hi * 64;       // row l31, this lane half's 32 hidden units (4 K steps x 8)
         const int ht_lane = l31 * 64 + hi * 16;        // hidden unit l31 (+ 32 ib), rows of K-step half hi
         // forward A operands [piece] of one K step and dW A operands [piece][ib] of one K step: requested one step
-        // ahead of their use (the first forward step of the NEXT tile during the dW products of this one)
+        // ahead of their use (the first forward step of the NEXT tile during the dH products of this one, the first dW
+        // step ahead of the last non-zero batch of Z).  The lane offset is made opaque where it is used: the constants
+        // then stay immediates of the loads -- hoisted out of the tile loop, every (offset + constant) holds a register
+        // of its own through every phase.
         u32x4 ha0[2];
         auto load_ha = [&](int tt, int ks, u32x4 (&dst)[2]) {
             const int so = tt * (kHTile * 2);
+            int ha_o = ha_lane;
+            asm volatile("" : "+v"(ha_o));
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                dst[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ha_rs, ha_lane + q * 4096 + ks * 16, so, 0));
+                dst[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ha_rs, ha_o + q * 4096 + ks * 16, so, 0));
         };
         auto load_ht = [&](int tt, int ks, u32x4 (&dst)[2][2]) {
             const int so = tt * (kHTile * 2);
+            int ht_o = ht_lane;
+            asm volatile("" : "+v"(ht_o));
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
                 for (int ib = 0; ib < 2; ++ib)
                     dst[q][ib] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        ht_rs, ht_lane + q * 4096 + ib * 2048 + ks * 32, so, 0));
+                        ht_rs, ht_o + q * 4096 + ib * 2048 + ks * 32, so, 0));
         };
         // LDS addresses of the weight image.  Transposing read (F): lane t of a 16-lane group supplies the 8-byte
         // chunk (row kk + t / 4, genes 16 (group & 1) + 4 (t & 3) ..) and receives rows kk .. kk + 3 of gene
@@ -641,6 +657,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                 const int4 r4 = *reinterpret_cast<const int4*>(Rt + (rb ^ half) * 32 + 8 * grp + 4 * hi);
                 yv[0] = count_at(r4.x); yv[1] = count_at(r4.y); yv[2] = count_at(r4.z); yv[3] = count_at(r4.w);
             };
+            u32x4 htb[2][2][2];                          // dW A operands [K step][piece][ib]
             auto z_loop = [&](auto fullv) {             // (ONE call site of the dense pass: its code, and the non-zero pass
 #pragma unroll 1                                        //  inside it, exist once per row-range variant)
                 for (int grp = 0; grp < 16 / kZU; ++grp) {
@@ -650,6 +667,8 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
 #pragma unroll
                     for (int j = 0; j < kZU; ++j) yA[j] = yB[j];
                 }
+                load_ht(t, 0, htb[0]);                   // first K step of the dW operands: in flight during the last non-zero batch
+                __builtin_amdgcn_sched_barrier(0);       // (a tile that repeats F + Z requests them again: the same values)
                 z_flush(true);
             };
             for (;;) {
@@ -720,69 +739,31 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                         for (int e = 0; e < 16; ++e) dW[h][ib][e] = __builtin_amdgcn_ldexpf(dW[h][ib][e], mv);
             }
 
-            // ---- dH[row, i] = sum_genes D[row, gene] W[i, gene]: A = the D pieces read transposed (row position l31, 8 genes
-            // per K-step half), B = the weight image read directly.  MFMA row m = row POSITION m (the order of the transposed
-            // H image): batch row (m & 0x13) | bit 2 <-> bit 3.
-            u32x4 htb[2][2][2];
-            load_ht(t, 0, htb[0]);                   // first K step of the dW operands: in flight during the dH products
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                // the accumulators start from what the workgroup's earlier gene tiles left for this row tile, brought to
-                // this tile's scale 2^(kDe + eW) (exact: a power of two); the partial itself is kept in g units
-                const float fs = pow2i(kDe + eW), fu = pow2i(-(kDe + eW));
-                f32x16 dHa[2];
-                // the 8 KB partial of (this workgroup, row tile t) through a buffer resource: scalar base, ONE per-lane
-                // offset, immediates -- 32 separate 64-bit addresses would not fit the register file
-                const __amdgpu_buffer_rsrc_t dh_rs = __builtin_amdgcn_make_buffer_rsrc(
-                    dh_part + (long)t * dh_tstride, 0, kTR * KT * 4, 0x00020000);
-                if (first_item) {
-#pragma unroll
-                    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) dHa[jb][e] = 0.f;
-                } else {
-#pragma unroll
-                    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                        for (int eq = 0; eq < 4; ++eq) {
-                            const u32x4 u = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(dh_rs, dh_lane + 128 * jb + 32 * eq, 0, 0));
-#pragma unroll
-                            for (int w = 0; w < 4; ++w) { const unsigned uw = u[w]; dHa[jb][4 * eq + w] = __uint_as_float(uw) * fs; }
-                        }
-                }
-                // the products TRANSPOSED -- hidden units x row positions: a lane then holds four consecutive hidden units of its
-                // row per accumulator quad, and the partial moves in 16-byte units (8 loads + 8 stores per tile instead of 32 + 32)
-#pragma unroll
-                for (int h = 0; h < NH; ++h)
-#pragma unroll
-                    for (int gs = 0; gs < 2; ++gs) {
-                        u32x4 af[2];
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const unsigned char* b0 = Pimg + h * HEAD_B + gs * 16 * CELL_LD + 8 * q + dtr;
-                            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
-                            const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + 4 * CELL_LD));
-                            const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi4);
-                            af[q] = u32x4{a[0], a[1], b[0], b[1]};
-                        }
-#pragma unroll
-                        for (int jb = 0; jb < 2; ++jb) {
-                            u32x4 bf[2] = {w_dr(h, 0, jb, gs), w_dr(h, 1, jb, gs)};
-                            MFMA_H3(bf, af, dHa[jb])
-                        }
-                    }
-#pragma unroll
-                for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                    for (int eq = 0; eq < 4; ++eq) {
-                        u32x4 v;
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) v[w] = __float_as_uint(dHa[jb][4 * eq + w] * fu);
-                        __builtin_amdgcn_raw_buffer_store_b128(v, dh_rs, dh_lane + 128 * jb + 32 * eq, 0, 0);
-                    }
-            }
+            // ---- the dH partial, requested a whole matrix phase ahead of its use: what the workgroup's earlier gene tiles left
+            // for this row tile (workgroup-private, written one work item ago, one of ~130 MB of partials: it comes from
+            // beyond L2), as it is stored (g units), into the registers of the dH accumulators -- free during dW, the low
+            // point of register pressure in the loop.  The 8 KB partial of (this workgroup, row tile t) through a buffer
+            // resource: scalar base, ONE per-lane offset, immediates -- 32 separate 64-bit addresses would not fit the
+            // register file.  The first work item has nothing to read: its request goes through a resource of ZERO records,
+            // which returns zeros without touching memory -- the same straight-line code for every item (0 x 2^k = 0).
+            // The second dW step's operands are requested in FRONT of the partial: loads return in order, and the dW
+            // products must not wait for the partial behind their own operands.
+            const __amdgpu_buffer_rsrc_t dh_rs = __builtin_amdgcn_make_buffer_rsrc(
+                dh_part + (long)t * dh_tstride, 0, kTR * KT * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t dh_rq = __builtin_amdgcn_make_buffer_rsrc(
+                dh_part + (long)t * dh_tstride, 0, first_item ? 0 : kTR * KT * 4, 0x00020000);
+            f32x16 dHa[2];
+            int dh_o = dh_lane;                      // (opaque: see load_ha)
+            asm volatile("" : "+v"(dh_o));
             load_ht(t, 1, htb[1]);
-            load_ha(tn, 0, ha0);                     // next tile's first forward step: in flight during the dW products
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                for (int eq = 0; eq < 4; ++eq) {
+                    const u32x4 u = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(dh_rq, dh_o + 128 * jb + 32 * eq, 0, 0));
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) { const unsigned uw = u[w]; dHa[jb][4 * eq + w] = __uint_as_float(uw); }
+                }
             __builtin_amdgcn_sched_barrier(0);
             // ---- dW[i, gene] += sum_rows H[row, i] D[row, gene]: B = the lane's own D column as stored (row positions in
             // the order of the MFMA row map = the order of the transposed H image), A = H^T pieces.  The accumulators carry
@@ -812,6 +793,10 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                         MFMA_H3(af, bf, dW[h][ib])
                     }
                 }
+            // (the column sums are COMPLETE here: left to the compiler, their dot products sink behind the dH phase and keep
+            // the twelve B operands of dW -- 48 registers -- alive through it)
+#pragma unroll
+            for (int h = 0; h < NH; ++h) asm volatile("" : "+v"(tsum[h]));
             {
                 const float gun = pow2i(-kDe);       // the tile's column sums back to g units
 #pragma unroll
@@ -822,6 +807,55 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
                     for (int e = 0; e < 16; ++e) ts += Th[l31 * kLdS + rowmap(e, hi)];
                     thsum = fmaf(ts, gun, thsum);
                 }
+            }
+            load_ha(tn, 0, ha0);                     // next tile's first forward step: in flight during the dH products
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- dH[row, i] = sum_genes D[row, gene] W[i, gene]: A = the D pieces read transposed (row position l31, 8 genes
+            // per K-step half), B = the weight image read directly.  MFMA row m = row POSITION m (the order of the transposed
+            // H image): batch row (m & 0x13) | bit 2 <-> bit 3.
+            {
+                // the accumulators start from the partial requested after Z, brought IN PLACE to this tile's scale
+                // 2^(kDe + eW) (exact: a power of two; the tied operand keeps the compiler from scaling into a second set of
+                // 32 registers); the partial itself is kept in g units
+                const float fs = pow2i(kDe + eW), fu = pow2i(-(kDe + eW));
+#pragma unroll
+                for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        float x = dHa[jb][e];
+                        asm("v_mul_f32 %0, %1, %0" : "+v"(x) : "s"(fs));
+                        dHa[jb][e] = x;
+                    }
+                // the products TRANSPOSED -- hidden units x row positions: a lane then holds four consecutive hidden units of its
+                // row per accumulator quad, and the partial moves in 16-byte units (8 loads + 8 stores per tile instead of 32 + 32)
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+#pragma unroll
+                    for (int gs = 0; gs < 2; ++gs) {
+                        u32x4 af[2];
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            const unsigned char* b0 = Pimg + h * HEAD_B + gs * 16 * CELL_LD + 8 * q + dtr;
+                            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0));
+                            const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b0 + 4 * CELL_LD));
+                            const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi4);
+                            af[q] = u32x4{a[0], a[1], b[0], b[1]};
+                        }
+#pragma unroll
+                        for (int jb = 0; jb < 2; ++jb) {
+                            u32x4 bf[2] = {w_dr(h, 0, jb, gs), w_dr(h, 1, jb, gs)};
+                            MFMA_H3(bf, af, dHa[jb])
+                        }
+                    }
+#pragma unroll
+                for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                    for (int eq = 0; eq < 4; ++eq) {
+                        u32x4 v;
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) v[w] = __float_as_uint(dHa[jb][4 * eq + w] * fu);
+                        __builtin_amdgcn_raw_buffer_store_b128(v, dh_rs, dh_o + 128 * jb + 32 * eq, 0, 0);
+                    }
             }
             srow_l = srow_n;
             sf_l = sf_n;
