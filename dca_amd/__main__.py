@@ -49,11 +49,14 @@ _OPTIONS = [
     (('--checkcounts',), dict(dest='checkcounts', action='store_true')),
     (('--nocheckcounts',), dict(dest='checkcounts', action='store_false')),
     (('--denoisesubset',), dict(dest='denoisesubset', type=str, help='file with gene names (one per line) to denoise')),
+    (('--score',), dict(dest='score', action='store_true',
+                        help='after the result files: the fitted model\'s mean negative log-likelihood per cell (cell_nll.tsv, train and '
+                             'test cells alike) and per gene (gene_nll.tsv), computed on the GPU')),
 ]
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,
                  checkcounts=True, norminput=True, hyper=False, debug=False, tensorboard=False,
-                 loginput=True)
+                 loginput=True, score=False)
 
 
 def build_parser():

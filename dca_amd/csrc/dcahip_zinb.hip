@@ -498,6 +498,114 @@ __global__ __launch_bounds__(256) void heads_infer_kernel(InferArgs a) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- K-SCORE: the two marginals of the element-wise NLL of a fitted model (dcahip_nll_marginals): per-row sums and
+// per-gene sums over consecutive rows, every element value accumulated in double.  The grid of zinb_nll_kernel:
+// blockIdx.x walks the gene segments (256 lanes x V genes), blockIdx.y = slice strides over the rows.
+//   * per gene: every lane keeps the V column sums of its quad over the rows of its slice and stores them to
+//     gene_part[slice][g] -- no reduction in the kernel;
+//   * per row: every wave adds up its 64 x V genes with shuffles and stores to row_part[segment * 4 + wave][row] -- no
+//     barrier in the row loop.
+// nll_finish_kernel adds the slices / the segment partials in index order.  Every workspace word it reads is written by
+// exactly one lane on every call and no sum depends on scheduling (no atomics): two calls give the same bits.
+// One readable kernel, both branches of the likelihood under divergence: scoring is a pass per dataset, not per step.
+constexpr int kScoreSlices = 64;
+
+struct MargArgs {
+    const float *a_mean, *a_disp, *a_pi, *theta_w, *y, *sf;
+    long lda, ldy;
+    double *gene_part, *row_part;
+    int B, G;
+    float ridge;
+};
+
+template <bool HAS_PI, bool CONST_DISP, int V, int LOSS>
+__global__ __launch_bounds__(256) void nll_marginals_kernel(MargArgs a) {
+    const int nvec = (a.G + V - 1) / V;
+    const int seg = blockIdx.x, wave = threadIdx.x >> 6;
+    const int q = seg * 256 + threadIdx.x;
+    const bool qv = q < nvec;
+    const int g = (qv ? q : 0) * V;
+    bool valid[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) valid[j] = qv && (g + j) < a.G;
+    float vd[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) vd[j] = 0.f;
+    if (CONST_DISP && qv) ldv<V>(a.theta_w + g, vd);
+    double col[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) col[j] = 0.0;
+    double* rp = a.row_part + (long)(seg * 4 + wave) * a.B;
+    const bool wave_live = seg * 256 + wave * 64 < nvec;         // a wave past the last quad only zeroes its partials
+    for (int row = blockIdx.y; row < a.B; row += gridDim.y) {
+        if (!wave_live) {
+            if ((threadIdx.x & 63) == 0) rp[row] = 0.0;
+            continue;
+        }
+        const float sf = a.sf[row];
+        float vm[V], vp[V], vy[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) { vm[j] = 0.f; vp[j] = 0.f; vy[j] = 0.f; }
+        if (qv) {
+            const long ao = (long)row * a.lda + g;
+            ldv<V>(a.a_mean + ao, vm);
+            if (!CONST_DISP && LOSS == 0) ldv<V>(a.a_disp + ao, vd);
+            if (HAS_PI) ldv<V>(a.a_pi + ao, vp);
+            ldv<V>(a.y + (long)row * a.ldy + g, vy);
+        }
+        double racc = 0.0;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            // the padding of a ragged last quad (columns G .. roundup4(G) - 1) holds anything: evaluated on zeros, not added
+            const float am = valid[j] ? vm[j] : 0.f, ad = valid[j] ? vd[j] : 0.f, ap = valid[j] ? vp[j] : 0.f;
+            const float y = valid[j] ? vy[j] : 0.f;
+            float nll, d0 = 0.f, d1 = 0.f, d2 = 0.f;
+            if (LOSS == 1) nll = poisson_elem(am, sf, y, d0);
+            else if (LOSS == 2) nll = mse_elem(am, sf, y, d0);
+            else nll = nll_elem<HAS_PI, false>(head_acts<HAS_PI, CONST_DISP>(am, ad, ap, sf), y, a.ridge, d0, d1, d2);
+            const double v = valid[j] ? (double)nll : 0.0;
+            col[j] += v;
+            racc += v;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) racc += __shfl_down(racc, off, 64);
+        if ((threadIdx.x & 63) == 0) rp[row] = racc;
+    }
+    double* gp = a.gene_part + (long)blockIdx.y * a.G + g;
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+        if (valid[j]) gp[j] = col[j];
+}
+
+__global__ __launch_bounds__(256) void nll_finish_kernel(const double* __restrict__ gene_part, int S,
+                                                         const double* __restrict__ row_part, int P, int B, int G,
+                                                         double* __restrict__ cell_out, double* __restrict__ gene_acc) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < G) {
+        double s = 0.0;
+        for (int k = 0; k < S; ++k) s += gene_part[(long)k * G + i];
+        gene_acc[i] += s;
+    } else if (i < (long)G + B) {
+        const long r = i - G;
+        double s = 0.0;
+        for (int k = 0; k < P; ++k) s += row_part[(long)k * B + r];
+        cell_out[r] = s;
+    }
+}
+
+// doubles of the two partial arrays: [slices][G] and, for the scalar path's 256-gene segments (the larger count),
+// [segments * 4][B]
+long marginals_doubles(int B, int G) {
+    const long S = B < kScoreSlices ? B : kScoreSlices;
+    return S * G + (long)((G + 255) / 256) * 4 * B;
+}
+
+template <bool HAS_PI, bool CONST_DISP, int LOSS>
+void launch_marginals(const MargArgs& a, bool vec, dim3 grid, hipStream_t s) {
+    if (vec) hipLaunchKernelGGL((nll_marginals_kernel<HAS_PI, CONST_DISP, 4, LOSS>), grid, dim3(256), 0, s, a);
+    else     hipLaunchKernelGGL((nll_marginals_kernel<HAS_PI, CONST_DISP, 1, LOSS>), grid, dim3(256), 0, s, a);
+}
+
 template <bool HAS_PI, bool CONST_DISP, bool GRAD>
 int launch_nll(const NllArgs& a, bool vec, dim3 grid, hipStream_t s) {
     // the compacted kernel addresses gradient elements with 32 bits
@@ -631,6 +739,44 @@ extern "C" int dcahip_zinb_nll_planes_h2(const float* a_mean, const float* a_dis
     return zinb_nll_planes_impl(1, ldexpf(1.f, d_exp), a_mean, a_disp, a_pi, lda, theta_w, y, ldy, sf, perm, cursor, B, G, ridge, inv_n,
                                 flags, d_planes, ldp, plane_stride, col_mean, col_disp, col_pi, d_theta, ldd_theta, loss_partials,
                                 n_partials_out, stream);
+}
+
+extern "C" int dcahip_nll_marginals_workspace_doubles(int B, int G) {
+    if (B <= 0 || G <= 0) return 0;
+    const long n = marginals_doubles(B, G);
+    return n > 0x7fffffffL ? DCAHIP_EINVAL : (int)n;
+}
+
+extern "C" int dcahip_nll_marginals(const float* a_mean, const float* a_disp, const float* a_pi, long lda,
+                                    const float* theta_w, const float* y, long ldy, const float* sf,
+                                    int B, int G, float ridge, int flags,
+                                    double* cell_out, double* gene_acc, double* workspace, void* stream) {
+    const bool has_pi = flags & DCAHIP_NLL_HAS_PI, cdisp = flags & DCAHIP_NLL_CONST_DISP;
+    const int loss = (flags & DCAHIP_NLL_POISSON) ? 1 : ((flags & DCAHIP_NLL_MSE) ? 2 : 0);
+    if (B <= 0 || G <= 0 || !a_mean || !y || !sf || !cell_out || !gene_acc || !workspace) return DCAHIP_EINVAL;
+    if (loss != 0 && (has_pi || cdisp)) return DCAHIP_EINVAL;
+    if (has_pi && !a_pi) return DCAHIP_EINVAL;
+    if (loss == 0 && (cdisp ? (theta_w == nullptr) : (a_disp == nullptr))) return DCAHIP_EINVAL;
+    if (lda < G || ldy < G || marginals_doubles(B, G) > 0x7fffffffL) return DCAHIP_EINVAL;
+    const bool vec = (lda % 4 == 0) && (ldy % 4 == 0) && al16(a_mean) && al16(y) &&
+                     (loss != 0 || (cdisp ? al16(theta_w) : al16(a_disp))) && (!has_pi || al16(a_pi)) &&
+                     lda >= ((G + 3) & ~3) && ldy >= ((G + 3) & ~3);
+    const int V = vec ? 4 : 1;
+    const int nseg = ((G + V - 1) / V + 255) / 256;
+    const int S = B < kScoreSlices ? B : kScoreSlices;
+    MargArgs a{a_mean, a_disp, a_pi, theta_w, y, sf, lda, ldy, workspace, workspace + (long)S * G, B, G, ridge};
+    const dim3 grid(nseg, S);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (loss == 1) launch_marginals<false, false, 1>(a, vec, grid, s);
+    else if (loss == 2) launch_marginals<false, false, 2>(a, vec, grid, s);
+    else if (has_pi && cdisp) launch_marginals<true, true, 0>(a, vec, grid, s);
+    else if (has_pi) launch_marginals<true, false, 0>(a, vec, grid, s);
+    else if (cdisp) launch_marginals<false, true, 0>(a, vec, grid, s);
+    else launch_marginals<false, false, 0>(a, vec, grid, s);
+    const long items = (long)G + B;
+    hipLaunchKernelGGL(nll_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
+                       a.gene_part, S, a.row_part, nseg * 4, B, G, cell_out, gene_acc);
+    return (int)hipGetLastError();
 }
 
 extern "C" int dcahip_loss_finalize(const double* partials, int n_partials, double scale,

@@ -343,6 +343,7 @@ class Engine:
         self.Bmax = 0
         self._hl = None             # (tensor, leading dimension) the heads read: the last hidden layer's output, or the input batch
         self.X = self.Y = self.sf = self.perm = None
+        self.has_targets = False    # the attached data came with its targets Y (score() needs them; load_data(X, None, sf) keeps an earlier Y buffer)
         # counts-resident mode (attach_counts): the raw counts as CSR; X / Y / sf are then [Bmax, .] tiles that every step
         # and every inference chunk gathers first (dcahip_csr_gather), and the kernels read the tiles through an identity
         # row vector and a zero cursor word (_kperm / _kcur) -- the real perm / cursor select the rows of the gather only
@@ -597,6 +598,7 @@ class Engine:
         assert X.shape[1] == lay.G_in
         self.csr = None
         self.n = n
+        self.has_targets = Y is not None
         self.ldx = _r4(lay.G_in)
         csr_x = _prep.csr_capable(X, self.dev, self.ops)
         csr_y = Y is not None and _prep.csr_capable(Y, self.dev, self.ops)
@@ -638,6 +640,7 @@ class Engine:
         self.csr = None
         self.n, self.ldx, self.ldy = X.shape[0], X.shape[1], lay.Gp
         self.X, self.Y, self.sf = X, Y, sf
+        self.has_targets = Y is not None
         self._set_tile_order()
         self._data_scales()
         self.attach_compact(compact, norm)
@@ -686,6 +689,7 @@ class Engine:
             col_out = torch.from_numpy(inv).to(self.dev)
         self.out_cols, self.col_out = out_cols, col_out
         self.csr, self.sf_all, self.norm_c = csr, sf, dict(norm)
+        self.has_targets = True
         self.n, self.ldx, self.ldy = csr.n, _r4(lay.G_in), lay.Gp
         self.gather_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.X = self.Y = self.sf = None
@@ -1827,6 +1831,43 @@ class Engine:
             n = self._nll(b, None, None, self.Y[o:], self.sf[o:], 1.0, False)
             ops.loss_finalize(self.partials, n, scale, self.val_loss_tmp)
             ops.step_end(self.val_loss_tmp, 1.0, None, 0, self.acc[1:], None, 0)
+
+    def score(self, r0=0, r1=None, chunk=None):
+        """The marginals of the element-wise NLL over storage rows [r0, r1) (all rows by default), inference mode (moving
+        batch-norm statistics, no dropout): {'cell': [r1 - r0], 'gene': [G_out]} float64 device tensors -- SUMS over the
+        genes / over the cells of the values eval_loss_sum adds up, without the l1 / l2 weight penalties.  Per chunk of
+        rows: the forward pass of eval_loss_sum, then one pass over the heads' pre-activation planes
+        (dcahip_nll_marginals), so every network type and both residency modes take the same path.  Training state
+        (parameters, optimizer slots, acc, cursor, moving statistics) is not touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: score() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not hasattr(ops, 'nll_marginals'):
+            raise NotImplementedError('dca_amd: score() needs ops with nll_marginals (ops %s has none)' % ops.name)
+        if self.csr is None and (self.Y is None or not self.has_targets):
+            raise ValueError('dca_amd: score() needs the targets Y: this engine has none (load_data(X, None, sf) attaches '
+                             'inputs only)')
+        r1 = self.n if r1 is None else r1
+        if not 0 <= r0 <= r1 <= self.n:
+            raise ValueError('dca_amd: score() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        cell, gene = torch.zeros(r1 - r0, **f64), torch.zeros(lay.G_out, **f64)
+        if r1 == r0:
+            return {'cell': cell, 'gene': gene}
+        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
+        self.reserve(chunk)
+        ws = torch.zeros(ops.nll_marginals_workspace_doubles(chunk, lay.G_out), **f64)
+        tw = lay.view(self.w, 'theta_w') if lay.const_disp else None
+        A = self.A
+        for s in range(r0, r1, chunk):
+            b = min(chunk, r1 - s)
+            o = self._range_rows(s, b)
+            KL = self._hidden_forward(b, ('range', o), False)
+            self._heads_forward(b, KL)
+            ops.nll_marginals(self._plane(A, 'mean'), self._plane(A, 'disp'), self._plane(A, 'pi'), lay.ldA, tw,
+                              self.Y[o:], self.ldy, self.sf[o:], b, lay.G_out, self.ridge, self.flags,
+                              cell[s - r0:], gene, ws)
+        return {'cell': cell, 'gene': gene}
 
     def predict_chunk(self, r0, b, want):
         """Inference forward over storage rows [r0, r0+b).  Returns device views (valid until

@@ -62,6 +62,9 @@ _SIGNATURES = {
                                           _i32p, _i64p, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int,
                                           _c.c_void_p, _c.c_long, _c.c_long, _c.c_long, _c.c_long, _c.c_long,
                                           _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp]),
+    'dcahip_nll_marginals_workspace_doubles': (_c.c_int, [_c.c_int, _c.c_int]),
+    'dcahip_nll_marginals': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
+                                        _c.c_int, _c.c_int, _c.c_float, _c.c_int, _f64p, _f64p, _f64p, _vp]),
     'dcahip_loss_finalize': (_c.c_int, [_f64p, _c.c_int, _c.c_double, _f32p, _vp]),
     'dcahip_step_end': (_c.c_int, [_f32p, _c.c_double, _f32p, _c.c_int, _f64p, _i64p, _c.c_int, _vp]),
     'dcahip_zinb_heads_infer': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int,

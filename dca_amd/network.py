@@ -270,6 +270,59 @@ class Autoencoder():
         if mode == 'latent':
             adata.X = adata.raw.X.copy()  # recover normalized expression values (network.py:208-209)
 
+    # ------------------------------------------------------------------ scoring
+    def score(self, adata, output_subset=None, use_raw_as_output=True, copy=False):
+        """The fitted model's negative log-likelihood of these cells, computed on the device (Engine.score) -- beyond the
+        reference, which reports the likelihood only as the epoch's ``loss`` / ``val_loss``.  Inputs, targets and size
+        factors are bound as ``train()`` binds them for one process (``adata.X``; ``adata.raw.X`` or ``adata.X``,
+        restricted to ``output_subset``; ``obs['size_factors']``).  Stores MEANS, comparable with ``val_loss``:
+
+            adata.obs['dca_nll']   per cell: its row sum / G_out
+            adata.var['dca_nll']   per gene: its column sum / n (NaN for the genes a gene-subset network does not fit)
+            adata.uns['dca_nll']   total / (n G_out): what Keras' ``evaluate`` reports for these cells, without the
+                                   l1 / l2 weight penalties
+
+        Returns ``adata`` if ``copy`` else None, like ``predict``."""
+        eng = self.engine
+        dd = getattr(adata, '_dca_device', None)
+        adata = adata.copy() if copy else adata
+        X = adata.X
+        sf = np.asarray(adata.obs['size_factors'].values, dtype=np.float32)       # train.py:83
+        gene_idx = None
+        if output_subset:                                                        # train.py:85-87
+            gene_idx = [np.where(adata.raw.var_names == x)[0][0] for x in output_subset]
+            Y = adata.raw.X[:, gene_idx] if use_raw_as_output else adata.X[:, gene_idx]
+        else:
+            Y = adata.raw.X if use_raw_as_output else adata.X
+        n, G_out = X.shape[0], eng.lay.G_out
+        resident = dd is not None and use_raw_as_output and dd.n == n and dd.G == X.shape[1] == lay_G(eng) and \
+            dd.device == eng.dev and dd.matches(X)
+        out_cols = None
+        if resident and output_subset and dd.csr is not None and dd.norm is not None and len(gene_idx) == G_out:
+            from .train import _subset_gather_refusal
+            if _subset_gather_refusal(adata, dd, gene_idx, eng.ops) is None:
+                out_cols = np.asarray(gene_idx, dtype=np.int64)
+        if out_cols is not None:
+            eng.attach_counts(dd.csr, dd.sf, dd.norm, out_cols=out_cols)
+        elif resident and not output_subset and lay_G(eng) == G_out:
+            dd.attach(eng)                                                      # K-PREP left the tensors (or the CSR) in HBM
+            if dd.csr is None:
+                dd.compact = eng.cc if eng.cc is not None else (False if getattr(eng, 'cc_verdict', None) is False else None)
+        else:
+            eng.load_data(X, Y, sf)
+        res = eng.score()
+        cell = res['cell'].cpu().numpy()
+        gene = res['gene'].cpu().numpy()
+        per_gene = gene / float(n)
+        if gene_idx is not None:
+            full = np.full(adata.n_vars, np.nan)
+            full[[int(np.where(adata.var_names == x)[0][0]) for x in output_subset]] = per_gene
+            per_gene = full
+        adata.obs['dca_nll'] = cell / float(G_out)
+        adata.var['dca_nll'] = per_gene
+        adata.uns['dca_nll'] = float(cell.sum() / (float(n) * G_out))
+        return adata if copy else None
+
     # ------------------------------------------------------------------ predict + write in one pass (the CLI's last step)
     def _write_extra(self, adata, file_path, colnames):
         """Result files that do not come from per-cell heads (the per-gene dispersion of the constant-dispersion types)."""

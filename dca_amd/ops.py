@@ -55,6 +55,18 @@ class HipOps:
                                                    p(partials), ctypes.byref(n), hip.stream()), 'zinb_nll_planes_h2')
         return n.value
 
+    def nll_marginals_workspace_doubles(self, B, G):
+        n = int(self.L.dcahip_nll_marginals_workspace_doubles(B, G))
+        hip.check(min(n, 0), 'nll_marginals_workspace_doubles')
+        return n
+
+    def nll_marginals(self, a_mean, a_disp, a_pi, lda, theta_w, Y, ldy, sf, B, G, ridge, flags, cell_out, gene_acc, ws):
+        """Row sums (cell_out [B], overwritten) and column sums (gene_acc [G], added to) of the element-wise NLL of B
+        consecutive rows, in double; Y / sf start at the first row."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_nll_marginals(p(a_mean), p(a_disp), p(a_pi), lda, p(theta_w), p(Y), ldy, p(sf), B, G,
+                                              ridge, flags, p(cell_out), p(gene_acc), p(ws), hip.stream()), 'nll_marginals')
+
     def loss_finalize(self, partials, n, scale, loss_out):
         hip.check(self.L.dcahip_loss_finalize(hip.ptr(partials), n, scale, hip.ptr(loss_out),
                                               hip.stream()), 'loss_finalize')

@@ -445,4 +445,25 @@ def train_with_args(args):
     columns = names[[int(np.where(names == g)[0][0]) for g in subset]] if subset else names
     # predict(mode='full', return_info=True) + write(...) of the reference (train.py:176-190) as one streaming pass: the
     # result files are the only consumer here, so no cells x genes matrix is staged on the host (network.predict_write)
+    x_in = adata.X                                  # the normalised input (predict() replaces adata.X by the denoised mean)
     net.predict_write(adata, args.outputdir, mode='full', colnames=columns)
+    if getattr(args, 'score', False):
+        write_scores(net, adata, x_in, subset, args.outputdir)
+
+
+def write_scores(net, adata, x_in, subset, output_dir):
+    """--score: the fitted model's mean NLL of every cell of the normalised input (train and test cells alike:
+    Autoencoder.score) -> cell_nll.tsv (index = cell name; nll, split), gene_nll.tsv (index = gene name; nll; the genes a
+    --denoisesubset network does not fit: empty), and one printed line with the mean of each split."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.score(adata, output_subset=subset)
+    cells = pd.DataFrame({'nll': np.asarray(adata.obs['dca_nll'], dtype=np.float64),
+                          'split': np.asarray(adata.obs['dca_split']).astype(str)}, index=pd.Index(adata.obs_names))
+    genes = pd.DataFrame({'nll': np.asarray(adata.var['dca_nll'], dtype=np.float64)}, index=pd.Index(adata.var_names))
+    cells.to_csv(os.path.join(output_dir, 'cell_nll.tsv'), sep='\t', float_format='%.6f')
+    genes.to_csv(os.path.join(output_dir, 'gene_nll.tsv'), sep='\t', float_format='%.6f')
+    means = cells.groupby('split', sort=True)['nll'].mean()
+    print('dca: mean NLL per cell and gene -- ' + ', '.join('%s: %.6f (%d cells)' % (k, means[k], int((cells['split'] == k).sum()))
+                                                            for k in means.index))

@@ -112,6 +112,32 @@ int dcahip_zinb_nll_planes_h2(const float* a_mean, const float* a_disp, const fl
                               double* loss_partials, int* n_partials_out, void* stream);
 
 /*
+ * K-SCORE: the two marginals of the element-wise negative log-likelihood of B consecutive rows -- what a fitted model is
+ * scored by (held-out cells, NB against ZINB, badly fitted genes / cells).  The element value is the one dcahip_zinb_nll
+ * sums (dca/loss.py:72-156: NB.loss / ZINB.loss before the reduce_mean, the ridge term ridge * pi^2 included; poisson_loss /
+ * mse_loss with the flags below), evaluated by the same device functions, WITHOUT an inv_n factor.
+ *
+ *   a_mean, a_disp, a_pi, lda, theta_w, ridge, flags : as dcahip_zinb_nll (DCAHIP_NLL_HAS_PI / CONST_DISP / POISSON / MSE)
+ *   y, ldy, sf      : targets and size factors of the B rows, already offset to the first row (row r of the planes
+ *                     belongs to y + r * ldy and sf[r]: no perm / cursor)
+ *   cell_out        : [B]  doubles, OVERWRITTEN with sum over g of nll(row, g)
+ *   gene_acc        : [G]  doubles, ADDED to: += sum over the rows of nll(row, g), so that chunks of cells accumulate
+ *   workspace       : [>= dcahip_nll_marginals_workspace_doubles(B, G)] doubles (0 for B <= 0 or G <= 0, DCAHIP_EINVAL
+ *                     when the count does not fit an int); needs no initialisation
+ *
+ * Every element value is converted to double before it is added.  Fixed summation order, no atomics: two calls on the same
+ * inputs give bit-identical outputs.  Any B >= 1, G >= 1; 16-byte aligned operands with lda, ldy multiples of 4 (and
+ * >= roundup4(G)) take 16-byte loads, anything else the scalar path; columns >= G of the planes never reach an output.
+ * DCAHIP_EINVAL (nothing launched): the argument errors of dcahip_zinb_nll, lda or ldy < G, NULL cell_out / gene_acc /
+ * workspace.
+ */
+int dcahip_nll_marginals_workspace_doubles(int B, int G);
+int dcahip_nll_marginals(const float* a_mean, const float* a_disp, const float* a_pi, long lda,
+                         const float* theta_w, const float* y, long ldy, const float* sf,
+                         int B, int G, float ridge, int flags,
+                         double* cell_out, double* gene_acc, double* workspace, void* stream);
+
+/*
  * Deterministic second stage of the loss reduction: loss = scale * sum(partials) with
  * nan -> inf (dca/loss.py:148), written to *loss_out (fp32, device).
  */
