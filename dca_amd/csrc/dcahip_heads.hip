@@ -1712,52 +1712,14 @@ extern "C" int dcahip_heads_tile_order_len(int G) { return G > 0 ? (((G + kTG - 
 
 extern "C" int dcahip_heads_fused(const float* H, long ldh, const float* Wh, long ldw,
                                   const float* bh, long plane, const float* theta_w,
-                                  const float* y, long ldy, const float* sf, const int* perm,
+                                  const float* y, long ldy,
+                                  const unsigned char* yc, long ldc, const int* ovf_ptr, const int* ovf_col,
+                                  const float* ovf_val, const float* sf, const int* perm,
                                   const long long* cursor, int B, int hL, int G, float ridge,
                                   float inv_n, int flags, float* gW, long ldg, float* g_theta,
                                   float* dH, long lddh, double* loss_partials, int* n_partials_out,
-                                  void* workspace, long workspace_bytes, void* stream) {
-    return dcahip_heads_fused_ordered(H, ldh, Wh, ldw, bh, plane, theta_w, y, ldy, sf, perm, cursor, B, hL, G, ridge,
-                                      inv_n, flags, gW, ldg, g_theta, dH, lddh, loss_partials, n_partials_out,
-                                      workspace, workspace_bytes, nullptr, stream);
-}
-
-extern "C" int dcahip_heads_fused_ordered(const float* H, long ldh, const float* Wh, long ldw,
-                                          const float* bh, long plane, const float* theta_w,
-                                          const float* y, long ldy, const float* sf, const int* perm,
-                                          const long long* cursor, int B, int hL, int G, float ridge,
-                                          float inv_n, int flags, float* gW, long ldg, float* g_theta,
-                                          float* dH, long lddh, double* loss_partials, int* n_partials_out,
-                                          void* workspace, long workspace_bytes, const int* tile_order,
-                                          void* stream) {
-    return dcahip_heads_fused_loss(H, ldh, Wh, ldw, bh, plane, theta_w, y, ldy, sf, perm, cursor, B, hL, G, ridge,
-                                   inv_n, flags, gW, ldg, g_theta, dH, lddh, loss_partials, n_partials_out,
-                                   workspace, workspace_bytes, tile_order, nullptr, stream);
-}
-
-extern "C" int dcahip_heads_fused_loss(const float* H, long ldh, const float* Wh, long ldw,
-                                       const float* bh, long plane, const float* theta_w,
-                                       const float* y, long ldy, const float* sf, const int* perm,
-                                       const long long* cursor, int B, int hL, int G, float ridge,
-                                       float inv_n, int flags, float* gW, long ldg, float* g_theta,
-                                       float* dH, long lddh, double* loss_partials, int* n_partials_out,
-                                       void* workspace, long workspace_bytes, const int* tile_order,
-                                       float* loss_out, void* stream) {
-    return dcahip_heads_fused_compact(H, ldh, Wh, ldw, bh, plane, theta_w, y, ldy, nullptr, 0, nullptr, nullptr, nullptr,
-                                      sf, perm, cursor, B, hL, G, ridge, inv_n, flags, gW, ldg, g_theta, dH, lddh,
-                                      loss_partials, n_partials_out, workspace, workspace_bytes, tile_order, loss_out, 0, stream);
-}
-
-extern "C" int dcahip_heads_fused_compact(const float* H, long ldh, const float* Wh, long ldw,
-                                          const float* bh, long plane, const float* theta_w,
-                                          const float* y, long ldy,
-                                          const unsigned char* yc, long ldc, const int* ovf_ptr, const int* ovf_col,
-                                          const float* ovf_val, const float* sf, const int* perm,
-                                          const long long* cursor, int B, int hL, int G, float ridge,
-                                          float inv_n, int flags, float* gW, long ldg, float* g_theta,
-                                          float* dH, long lddh, double* loss_partials, int* n_partials_out,
-                                          void* workspace, long workspace_bytes, const int* tile_order,
-                                          float* loss_out, int d_exp, void* stream) {
+                                  void* workspace, long workspace_bytes, const int* tile_order,
+                                  float* loss_out, int d_exp, void* stream) {
     const bool has_pi = flags & DCAHIP_NLL_HAS_PI, cdisp = flags & DCAHIP_NLL_CONST_DISP;
     HeadsPlan pl;
     if (!make_heads_plan(B, hL, G, plane, flags, &pl)) return DCAHIP_EINVAL;

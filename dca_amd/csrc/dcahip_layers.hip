@@ -2033,25 +2033,19 @@ extern "C" int dcahip_bn_relu_apply(const float* Z, long ldz, int B, int H, cons
     return (int)hipGetLastError();
 }
 
-extern "C" int dcahip_bn_bwd_sums_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                                      const float* xhat, long ldx, int B, int H, float* part,
-                                      int act, const float* beta, void* stream) {
+extern "C" int dcahip_bn_bwd_sums(const float* dH, long ldd, const float* Hact, long ldh,
+                                  const float* xhat, long ldx, int B, int H, float* part,
+                                  int act, const float* beta, void* stream) {
     if (!dH || !Hact || !xhat || !part || B <= 0 || H <= 0 || (act >= kActPre && !beta)) return DCAHIP_EINVAL;
     hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(n_chunks(B), strip_blocks(H, n_chunks(B))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act, beta);
     return (int)hipGetLastError();
 }
 
-extern "C" int dcahip_bn_bwd_sums(const float* dH, long ldd, const float* Hact, long ldh,
-                                  const float* xhat, long ldx, int B, int H, float* part,
-                                  int act, void* stream) {
-    return dcahip_bn_bwd_sums_pre(dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act, nullptr, stream);
-}
-
-extern "C" int dcahip_bn_bwd_apply_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                                       const float* xhat, long ldx, const float* inv_std,
-                                       const float* sums, int E, float n_total, int B, int H, float* dZ,
-                                       long ldz, float* dbeta, int act, const float* beta, void* stream) {
+extern "C" int dcahip_bn_bwd_apply(const float* dH, long ldd, const float* Hact, long ldh,
+                                   const float* xhat, long ldx, const float* inv_std,
+                                   const float* sums, int E, float n_total, int B, int H, float* dZ,
+                                   long ldz, float* dbeta, int act, const float* beta, void* stream) {
     if (!dH || !Hact || !xhat || !inv_std || !sums || !dZ || E <= 0 || B <= 0 || H <= 0 || (act >= kActPre && !beta))
         return DCAHIP_EINVAL;
     BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz, dbeta, act, beta};
@@ -2059,14 +2053,6 @@ extern "C" int dcahip_bn_bwd_apply_pre(const float* dH, long ldd, const float* H
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid, strip_blocks(H, grid)), dim3(256), 2 * H * sizeof(float),
                        static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_bn_bwd_apply(const float* dH, long ldd, const float* Hact, long ldh,
-                                   const float* xhat, long ldx, const float* inv_std,
-                                   const float* sums, int E, float n_total, int B, int H, float* dZ,
-                                   long ldz, float* dbeta, int act, void* stream) {
-    return dcahip_bn_bwd_apply_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz, dbeta, act,
-                                   nullptr, stream);
 }
 
 extern "C" int dcahip_bn_fused_max_rows() { return kFusedRows; }
@@ -2083,23 +2069,16 @@ extern "C" int dcahip_bn_relu_train_small(const float* Z, long ldz, int B, int H
     return (int)hipGetLastError();
 }
 
-extern "C" int dcahip_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                                       const float* xhat, long ldx, const float* inv_std, float n_total,
-                                       int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta,
-                                       void* stream) {
+extern "C" int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
+                                   const float* xhat, long ldx, const float* inv_std, float n_total,
+                                   int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta,
+                                   void* stream) {
     if (!dH || !Hact || !xhat || !inv_std || !dZ || B <= 0 || B > kFusedRows || H <= 0 || (act >= kActPre && !beta))
         return DCAHIP_EINVAL;
     BnBwdArgs a{dH, ldd, Hact, ldh, xhat, ldx, inv_std, nullptr, 0, n_total, B, H, dZ, ldz, dbeta, act, beta};
     if (B <= 32) hipLaunchKernelGGL(bn_bwd_small_kernel<8>, dim3((H + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(bn_bwd_small_kernel<kFusedRows / 4>, dim3((H + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
-                                   const float* xhat, long ldx, const float* inv_std, float n_total,
-                                   int B, int H, float* dZ, long ldz, float* dbeta, int act, void* stream) {
-    return dcahip_bn_bwd_small_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, n_total, B, H, dZ, ldz, dbeta, act, nullptr,
-                                   stream);
 }
 
 extern "C" int dcahip_dense_small_max_k() { return kSmallK; }
@@ -2118,6 +2097,11 @@ extern "C" int dcahip_dense_bn_small(const float* Hp, long ldp, const float* W, 
     return (int)hipGetLastError();
 }
 
+static SmallLayer small_layer(const dcahip_small_layer& q) {
+    return SmallLayer{q.W, q.ldw, q.bias, q.K, q.H, q.beta, q.moving_mean, q.moving_var, q.Z, q.ldz, q.xhat, q.ldx,
+                      q.Hout, q.ldh, q.inv_std};
+}
+
 extern "C" int dcahip_hidden_small_chain(const dcahip_small_layer* layers, int n, const float* Hin, long ldin, int B,
                                          int batchnorm, float momentum, float eps, int act, void* stream) {
     if (!layers || n < 1 || n > kChainMax || B <= 0 || B > kFusedRows) return DCAHIP_EINVAL;
@@ -2131,8 +2115,7 @@ extern "C" int dcahip_hidden_small_chain(const dcahip_small_layer* layers, int n
             if (i > 0 && q.K != layers[i - 1].H) return DCAHIP_EINVAL;
         } else if (!q.Z) return DCAHIP_EINVAL;
         if (batchnorm && (!q.moving_mean || !q.moving_var)) return DCAHIP_EINVAL;
-        a.l[i] = SmallLayer{q.W, q.ldw, q.bias, q.K, q.H, q.beta, q.moving_mean, q.moving_var, q.Z, q.ldz, q.xhat, q.ldx,
-                            q.Hout, q.ldh, q.inv_std};
+        a.l[i] = small_layer(q);
     }
     a.Hin = Hin; a.ldin = ldin; a.n = n; a.B = B; a.batchnorm = batchnorm; a.act = act; a.momentum = momentum; a.eps = eps;
     if (B <= 32) hipLaunchKernelGGL(hidden_small_chain_kernel<8>, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a);
@@ -2140,12 +2123,12 @@ extern "C" int dcahip_hidden_small_chain(const dcahip_small_layer* layers, int n
     return (int)hipGetLastError();
 }
 
-extern "C" int dcahip_dense_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                                             const float* xhat, long ldx, const float* inv_std,
-                                             const float* Hp, long ldp, const float* W, long ldw,
-                                             int B, int K, int H, int batchnorm, float n_total, int act,
-                                             float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
-                                             void* stream) {
+extern "C" int dcahip_dense_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
+                                         const float* xhat, long ldx, const float* inv_std,
+                                         const float* Hp, long ldp, const float* W, long ldw,
+                                         int B, int K, int H, int batchnorm, float n_total, int act,
+                                         float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
+                                         void* stream) {
     if (!dH || !Hact || !Hp || !W || !gW || B <= 0 || B > kFusedRows || K <= 0 || K > kSmallK || H <= 0 || H > kSmallK)
         return DCAHIP_EINVAL;
     if (batchnorm && (!xhat || !inv_std || (act >= kActPre && !beta))) return DCAHIP_EINVAL;
@@ -2154,15 +2137,6 @@ extern "C" int dcahip_dense_bn_bwd_small_pre(const float* dH, long ldd, const fl
     if (B <= 32) hipLaunchKernelGGL(dense_bn_bwd_small_kernel<8>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(dense_bn_bwd_small_kernel<16>, dim3(kBwdWGs), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_dense_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
-                                         const float* xhat, long ldx, const float* inv_std,
-                                         const float* Hp, long ldp, const float* W, long ldw,
-                                         int B, int K, int H, int batchnorm, float n_total, int act,
-                                         float* gW, long ldg, float* dbeta, float* dHp, long lddp, void* stream) {
-    return dcahip_dense_bn_bwd_small_pre(dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm,
-                                         n_total, act, gW, ldg, dbeta, dHp, lddp, nullptr, stream);
 }
 
 extern "C" int dcahip_relu_bwd(const float* dH, long ldd, const float* Hact, long ldh, int B, int H,
@@ -2366,21 +2340,9 @@ extern "C" int dcahip_colsum_chain(const float* x, long ldx, int B, int N, const
 }
 
 extern "C" int dcahip_rmsprop_clip(float* w, const float* g, float* ms, long n, const float* lr,
-                                   float rho, float eps, float clip, void* stream) {
-    if (!w || !g || !ms || !lr || n <= 0) return DCAHIP_EINVAL;
-    if (!al16(w) || !al16(g) || !al16(ms)) return DCAHIP_EINVAL;
-    long grid = ((n >> 2) + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(rmsprop_clip_kernel, dim3((int)grid), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), w, g, ms, n, lr, rho, eps, clip, StepEnd{nullptr, 0.0, nullptr, 0, nullptr, nullptr, 0, 0});
-    return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_rmsprop_clip_end(float* w, const float* g, float* ms, long n, const float* lr,
-                                       float rho, float eps, float clip, const float* loss, double weight,
-                                       float* hist, int rows_per_slot, double* acc, long long* cursor, int advance,
-                                       void* stream) {
+                                   float rho, float eps, float clip, const float* loss, double weight,
+                                   float* hist, int rows_per_slot, double* acc, long long* cursor, int advance,
+                                   void* stream) {
     if (!w || !g || !ms || !lr || n <= 0) return DCAHIP_EINVAL;
     if (!al16(w) || !al16(g) || !al16(ms)) return DCAHIP_EINVAL;
     long grid = ((n >> 2) + 255) / 256;
@@ -2388,7 +2350,7 @@ extern "C" int dcahip_rmsprop_clip_end(float* w, const float* g, float* ms, long
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(rmsprop_clip_kernel, dim3((int)grid), dim3(256), 0,
                        static_cast<hipStream_t>(stream), w, g, ms, n, lr, rho, eps, clip,
-                       StepEnd{loss, weight, hist, rows_per_slot, acc, cursor, advance, 1});
+                       StepEnd{loss, weight, hist, rows_per_slot, acc, cursor, advance, (loss || hist || acc || cursor) ? 1 : 0});
     return (int)hipGetLastError();
 }
 
@@ -2410,33 +2372,87 @@ static int stack_plan(int n, int B, int rows_per_wg, int first, int last, int ns
     return 0;
 }
 
+// what every K-STACK entry point asks of its batch and layer count
+static bool stack_shape_ok(const void* layers, int n, int B) {
+    return layers && n >= 1 && n <= kStackMaxLayers && B > 0 && B <= kStackMaxWG * kStackRows;
+}
+
+static bool stack_workspace_ok(const void* workspace, long workspace_bytes, int n, int B) {
+    return workspace && workspace_bytes >= dcahip_hidden_stack_workspace_bytes(n, B) && al16(workspace);
+}
+
+// The forward layers of K-STACK, validated and copied to l[n].  need_z: every layer behind the first hands its Z over to the
+// next launch (one step per launch); a whole pass in one launch keeps it in the workgroup and may leave it out.
+static bool stack_fwd_layers(const dcahip_small_layer* layers, int n, bool need_z, SmallLayer* l) {
+    for (int i = 0; i < n; ++i) {
+        const dcahip_small_layer& q = layers[i];
+        if (q.H <= 0 || q.H > 64 || !q.Hout || !q.moving_mean || !q.moving_var) return false;
+        if (i == 0 ? !q.Z : (!q.W || q.K != layers[i - 1].H || (need_z && !q.Z))) return false;
+        l[i] = small_layer(q);
+    }
+    return true;
+}
+
+// The backward layers, validated and copied to l[n].  need_dh: every layer's dH (a launch boundary between the layers: the
+// gradient goes through memory); otherwise only the last layer's, the incoming gradient.
+static bool stack_bwd_layers(const dcahip_stack_bwd_layer* layers, int n, int act, bool need_dh, StackBwdLayer* l) {
+    for (int i = 0; i < n; ++i) {
+        const dcahip_stack_bwd_layer& q = layers[i];
+        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || (act >= kActPre && !q.beta)) return false;
+        if (i > 0 && (!q.W || !q.Hprev || !q.gW || q.K != layers[i - 1].H || q.K > 64)) return false;
+        if (!q.dH && (i == n - 1 || need_dh)) return false;
+        l[i] = StackBwdLayer{q.W, q.ldw, q.K, q.H, q.Hact, q.ldh, q.xhat, q.ldx, q.inv_std, q.Hprev, q.ldp, q.gW, q.ldg,
+                             q.dbeta, q.dH, q.lddh, q.beta};
+    }
+    return true;
+}
+
+// Forward step `step` (0 .. n) at nwg row blocks: step 0 measures layer 0, step s >= 1 finishes layer s - 1 and makes layer s,
+// whose block statistics go to slot `step` of part [n][nwg][2][64] (step 0: slot 0).
+static StepFwdArgs stack_fwd_step(const SmallLayer* l, int n, int B, float momentum, float eps, int act, int step, int nwg,
+                                  float* part) {
+    StepFwdArgs q{};
+    const int i = step == 0 ? 0 : step - 1;
+    q.cur = l[i];
+    if (step > 0 && i + 1 < n) q.nxt = l[i + 1];
+    q.B = B; q.act = act; q.nwg = nwg; q.stats_only = step == 0; q.momentum = momentum; q.eps = eps;
+    q.part_in = part + (long)i * nwg * 2 * 64;
+    q.part_out = part + (long)step * nwg * 2 * 64;
+    return q;
+}
+
+// the layer whose block sums backward step `step` (0 .. n) writes: the top layer first, then the one below the step's; -1: none
+static int stack_bwd_made(int n, int step) { return step == 0 ? n - 1 : n - step - 1; }
+
+// Backward step `step` (0 .. n): step 0 sums the top layer, step s >= 1 handles layer n - s and sums the layer below.
+static StepBwdArgs stack_bwd_step(const StackBwdLayer* l, int n, int B, float n_total, int act, float* dZ0, long ldz0, int step,
+                                  int nwg, float* part) {
+    StepBwdArgs q{};
+    const int i = step == 0 ? n - 1 : n - step;
+    const int made = stack_bwd_made(n, step);
+    q.cur = l[i];
+    if (step > 0 && i > 0) q.low = l[i - 1];
+    q.B = B; q.act = act; q.nwg = nwg; q.sums_only = step == 0; q.n_total = n_total;
+    q.dZ0 = dZ0; q.ldz0 = ldz0;
+    q.part_in = part + (long)i * nwg * 2 * 64;
+    q.part_out = part + (long)(made >= 0 ? made : 0) * nwg * 2 * 64;
+    q.gwp = part + (long)n * nwg * 2 * 64 + (long)i * nwg * 65 * 64;         // [n][nwg][65][64] behind the sums
+    return q;
+}
+
 extern "C" int dcahip_hidden_stack_fwd(const dcahip_small_layer* layers, int n, int B, float momentum, float eps, int act,
                                        int rows_per_wg, int first_step, int last_step,
                                        void* workspace, long workspace_bytes, void* stream) {
-    if (!layers || n < 1 || n > kStackMaxLayers || B <= 0 || B > kStackMaxWG * kStackRows || !workspace) return DCAHIP_EINVAL;
-    if (workspace_bytes < dcahip_hidden_stack_workspace_bytes(n, B) || !al16(workspace)) return DCAHIP_EINVAL;
+    if (!stack_shape_ok(layers, n, B) || !stack_workspace_ok(workspace, workspace_bytes, n, B)) return DCAHIP_EINVAL;
     StackFwdArgs a{};
     if (stack_plan(n, B, rows_per_wg, first_step, last_step, n + 1, &a.nwg)) return DCAHIP_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const dcahip_small_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hout || !q.moving_mean || !q.moving_var) return DCAHIP_EINVAL;
-        if (i == 0 ? !q.Z : (!q.W || q.K != layers[i - 1].H)) return DCAHIP_EINVAL;
-        if (i > 0 && !q.Z && !(first_step == 0 && last_step == n)) return DCAHIP_EINVAL;   // one step per launch: Z hands over
-        a.l[i] = SmallLayer{q.W, q.ldw, q.bias, q.K, q.H, q.beta, q.moving_mean, q.moving_var, q.Z, q.ldz, q.xhat, q.ldx,
-                            q.Hout, q.ldh, q.inv_std};
-    }
+    if (!stack_fwd_layers(layers, n, !(first_step == 0 && last_step == n), a.l)) return DCAHIP_EINVAL;
     a.n = n; a.B = B; a.act = act; a.first = first_step; a.last = last_step; a.momentum = momentum; a.eps = eps;
     a.sync = static_cast<unsigned*>(workspace);
     a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
     if (first_step == last_step && rows_per_wg == kStepRows) {
         // one step per launch at the step kernels' row partition: every read of the step up front
-        StepFwdArgs q{};
-        const int i = first_step == 0 ? 0 : first_step - 1;
-        q.cur = a.l[i];
-        if (first_step > 0 && i + 1 < n) q.nxt = a.l[i + 1];
-        q.B = B; q.act = act; q.nwg = a.nwg; q.stats_only = first_step == 0; q.momentum = momentum; q.eps = eps;
-        q.part_in = a.part + (long)i * a.nwg * 2 * 64;
-        q.part_out = a.part + (long)(first_step == 0 ? 0 : i + 1) * a.nwg * 2 * 64;
+        const StepFwdArgs q = stack_fwd_step(a.l, n, B, momentum, eps, act, first_step, a.nwg, a.part);
         hipLaunchKernelGGL(stack_fwd_step_kernel, dim3(a.nwg), dim3(256), 0, static_cast<hipStream_t>(stream), q);
         return (int)hipGetLastError();
     }
@@ -2452,33 +2468,19 @@ extern "C" int dcahip_hidden_stack_step_blocks(int B) { return B > 0 ? stack_wor
 extern "C" int dcahip_hidden_stack_fwd_sync(const dcahip_small_layer* layers, int n, int B, float momentum, float eps, int act,
                                             int step, const float* ext_entries, const float* ext_counts, int ext_E,
                                             float* stat_out, void* workspace, long workspace_bytes, void* stream) {
-    if (!layers || n < 1 || n > kStackMaxLayers || B <= 0 || B > kStackMaxWG * kStackRows || !workspace) return DCAHIP_EINVAL;
-    if (workspace_bytes < dcahip_hidden_stack_workspace_bytes(n, B) || !al16(workspace) || step < 0 || step > n) return DCAHIP_EINVAL;
-    if (step > 0 && (!ext_entries || !ext_counts || ext_E <= 0)) return DCAHIP_EINVAL;
+    if (!stack_shape_ok(layers, n, B) || !stack_workspace_ok(workspace, workspace_bytes, n, B)) return DCAHIP_EINVAL;
+    if (step < 0 || step > n || (step > 0 && (!ext_entries || !ext_counts || ext_E <= 0))) return DCAHIP_EINVAL;
     const int nwg = stack_workgroups(B, kStepRows);
     if (nwg > kStackMaxPhaseWG) return DCAHIP_EINVAL;
     SmallLayer l[kStackMaxLayers];
-    for (int i = 0; i < n; ++i) {
-        const dcahip_small_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hout || !q.moving_mean || !q.moving_var || !q.Z) return DCAHIP_EINVAL;
-        if (i > 0 && (!q.W || q.K != layers[i - 1].H)) return DCAHIP_EINVAL;
-        l[i] = SmallLayer{q.W, q.ldw, q.bias, q.K, q.H, q.beta, q.moving_mean, q.moving_var, q.Z, q.ldz, q.xhat, q.ldx,
-                          q.Hout, q.ldh, q.inv_std};
-    }
+    if (!stack_fwd_layers(layers, n, true, l)) return DCAHIP_EINVAL;
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-    StepFwdArgs q{};
-    const int i = step == 0 ? 0 : step - 1;
-    q.cur = l[i];
-    if (step > 0 && i + 1 < n) q.nxt = l[i + 1];
-    q.B = B; q.act = act; q.nwg = nwg; q.stats_only = step == 0; q.momentum = momentum; q.eps = eps;
-    q.part_in = part + (long)i * nwg * 2 * 64;
-    const int made = step == 0 ? 0 : i + 1;                       // the layer whose block statistics this launch writes
-    q.part_out = part + (long)made * nwg * 2 * 64;
+    StepFwdArgs q = stack_fwd_step(l, n, B, momentum, eps, act, step, nwg, part);
     if (step > 0) { q.ext_in = ext_entries; q.ext_counts = ext_counts; q.ext_E = ext_E; }
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(stack_fwd_step_kernel, dim3(nwg), dim3(256), 0, st, q);
-    if (made < n && stat_out) {
-        const int Hm = l[made].H;
+    if (step < n && stat_out) {                                   // layer `step` is the one whose block statistics were written
+        const int Hm = l[step].H;
         hipLaunchKernelGGL(moments_combine_kernel, dim3((Hm + 63) / 64), dim3(256), 0, st,
                            (const float*)q.part_out, (const float*)nullptr, nwg, Hm, stat_out, B);
     }
@@ -2488,34 +2490,18 @@ extern "C" int dcahip_hidden_stack_fwd_sync(const dcahip_small_layer* layers, in
 extern "C" int dcahip_hidden_stack_bwd_sync(const dcahip_stack_bwd_layer* layers, int n, int B, float n_total, int act,
                                             float* dZ0, long ldz0, int step, const float* ext_sums, float* sums_out,
                                             void* workspace, long workspace_bytes, void* stream) {
-    if (!layers || n < 1 || n > kStackMaxLayers || B <= 0 || B > kStackMaxWG * kStackRows || !dZ0 || !workspace) return DCAHIP_EINVAL;
-    if (workspace_bytes < dcahip_hidden_stack_workspace_bytes(n, B) || !al16(workspace) || step < 0 || step > n) return DCAHIP_EINVAL;
-    if (step > 0 && !ext_sums) return DCAHIP_EINVAL;
+    if (!stack_shape_ok(layers, n, B) || !dZ0 || !stack_workspace_ok(workspace, workspace_bytes, n, B)) return DCAHIP_EINVAL;
+    if (step < 0 || step > n || (step > 0 && !ext_sums)) return DCAHIP_EINVAL;
     const int nwg = stack_workgroups(B, kStepRows);
     if (nwg > kStackMaxPhaseWG) return DCAHIP_EINVAL;
     StackBwdLayer l[kStackMaxLayers];
-    for (int i = 0; i < n; ++i) {
-        const dcahip_stack_bwd_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || !q.dH || (act >= kActPre && !q.beta)) return DCAHIP_EINVAL;
-        if (i > 0 && (!q.W || !q.Hprev || !q.gW || q.K != layers[i - 1].H || q.K > 64)) return DCAHIP_EINVAL;
-        l[i] = StackBwdLayer{q.W, q.ldw, q.K, q.H, q.Hact, q.ldh, q.xhat, q.ldx, q.inv_std, q.Hprev, q.ldp, q.gW, q.ldg,
-                             q.dbeta, q.dH, q.lddh, q.beta};
-    }
+    if (!stack_bwd_layers(layers, n, act, true, l)) return DCAHIP_EINVAL;
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
-    float* gwp = part + (long)n * nwg * 2 * 64;
-    StepBwdArgs q{};
-    const int i = step == 0 ? n - 1 : n - step;
-    q.cur = l[i];
-    if (step > 0 && i > 0) q.low = l[i - 1];
-    q.B = B; q.act = act; q.nwg = nwg; q.sums_only = step == 0; q.n_total = n_total;
-    q.dZ0 = dZ0; q.ldz0 = ldz0;
-    q.part_in = part + (long)i * nwg * 2 * 64;
-    const int made = step == 0 ? i : i - 1;                       // the layer whose block sums this launch writes (-1: none)
-    q.part_out = part + (long)(made >= 0 ? made : 0) * nwg * 2 * 64;
-    q.gwp = gwp + (long)i * nwg * 65 * 64;
+    StepBwdArgs q = stack_bwd_step(l, n, B, n_total, act, dZ0, ldz0, step, nwg, part);
     if (step > 0) q.ext_in = ext_sums;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(stack_bwd_step_kernel, dim3(nwg), dim3(256), 0, st, q);
+    const int made = stack_bwd_made(n, step);
     if (made >= 0 && sums_out)
         hipLaunchKernelGGL(stack_sums_combine_kernel, dim3(1), dim3(64), 0, st, (const float*)q.part_out, nwg, l[made].H, sums_out,
                            l[made].dbeta);
@@ -2525,21 +2511,13 @@ extern "C" int dcahip_hidden_stack_bwd_sync(const dcahip_stack_bwd_layer* layers
 extern "C" int dcahip_hidden_stack_bwd(const dcahip_stack_bwd_layer* layers, int n, int B, float n_total, int act,
                                        float* dZ0, long ldz0, int rows_per_wg, int first_step, int last_step,
                                        void* workspace, long workspace_bytes, void* stream) {
-    if (!layers || n < 1 || n > kStackMaxLayers || B <= 0 || B > kStackMaxWG * kStackRows || !dZ0) return DCAHIP_EINVAL;
+    if (!stack_shape_ok(layers, n, B) || !dZ0) return DCAHIP_EINVAL;
     const bool one_launch = first_step == 0 && last_step == n + 1;
     const bool chain = one_launch && B <= kStackRows && n <= 4;  // one workgroup holds the batch: no workspace
-    if (!chain && (!workspace || workspace_bytes < dcahip_hidden_stack_workspace_bytes(n, B) || !al16(workspace)))
-        return DCAHIP_EINVAL;
+    if (!chain && !stack_workspace_ok(workspace, workspace_bytes, n, B)) return DCAHIP_EINVAL;
     StackBwdArgs a{};
     if (stack_plan(n, B, rows_per_wg, first_step, last_step, n + 2, &a.nwg)) return DCAHIP_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const dcahip_stack_bwd_layer& q = layers[i];
-        if (q.H <= 0 || q.H > 64 || !q.Hact || !q.xhat || !q.inv_std || (act >= kActPre && !q.beta)) return DCAHIP_EINVAL;
-        if (i > 0 && (!q.W || !q.Hprev || !q.gW || q.K != layers[i - 1].H || q.K > 64)) return DCAHIP_EINVAL;
-        if (!q.dH && (i == n - 1 || !one_launch)) return DCAHIP_EINVAL;
-        a.l[i] = StackBwdLayer{q.W, q.ldw, q.K, q.H, q.Hact, q.ldh, q.xhat, q.ldx, q.inv_std, q.Hprev, q.ldp, q.gW, q.ldg,
-                               q.dbeta, q.dH, q.lddh, q.beta};
-    }
+    if (!stack_bwd_layers(layers, n, act, !one_launch, a.l)) return DCAHIP_EINVAL;
     a.n = n; a.B = B; a.act = act; a.first = first_step; a.last = last_step; a.n_total = n_total;
     a.dZ0 = dZ0; a.ldz0 = ldz0;
     if (chain) {
@@ -2558,15 +2536,7 @@ extern "C" int dcahip_hidden_stack_bwd(const dcahip_stack_bwd_layer* layers, int
     a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
     a.gwp = a.part + (long)n * a.nwg * 2 * 64;
     if (first_step == last_step && first_step <= n && rows_per_wg == kStepRows) {
-        StepBwdArgs q{};
-        const int i = first_step == 0 ? n - 1 : n - first_step;
-        q.cur = a.l[i];
-        if (first_step > 0 && i > 0) q.low = a.l[i - 1];
-        q.B = B; q.act = act; q.nwg = a.nwg; q.sums_only = first_step == 0; q.n_total = n_total;
-        q.dZ0 = dZ0; q.ldz0 = ldz0;
-        q.part_in = a.part + (long)i * a.nwg * 2 * 64;
-        q.part_out = a.part + (long)(first_step == 0 ? i : (i > 0 ? i - 1 : 0)) * a.nwg * 2 * 64;
-        q.gwp = a.gwp + (long)i * a.nwg * 65 * 64;
+        const StepBwdArgs q = stack_bwd_step(a.l, n, B, n_total, act, dZ0, ldz0, first_step, a.nwg, a.part);
         hipLaunchKernelGGL(stack_bwd_step_kernel, dim3(a.nwg), dim3(256), 0, static_cast<hipStream_t>(stream), q);
         return (int)hipGetLastError();
     }

@@ -858,7 +858,7 @@ class Engine:
             self.ops.absmax_exp(one, 4, 1, 1, self.x_exp)
 
     def _heads_d_exp(self):
-        """K-HEADS' starting exponent for its gradient pieces (include/dcahip.h, dcahip_heads_fused_compact: d_exp <= 0), once
+        """K-HEADS' starting exponent for its gradient pieces (include/dcahip.h, dcahip_heads_fused: d_exp <= 0), once
         per dataset.  The kernel carries D = g 2^(8 + d_exp) in fp16: |g| <= 117 fits at d_exp = 0, and a 32 x 32 tile with a larger
         gradient repeats its forward product and likelihood pass with the exponent it needs (exact, ~1.6 x the tile's time).
         Counts in the hundreds THROUGHOUT the matrix (full-length protocols) would make every tile repeat: start lower instead.

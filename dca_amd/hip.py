@@ -6,13 +6,13 @@ here -- owning device buffers and streams; tensors cross the boundary as raw dev
 """
 import ctypes
 import os
+import re
 
 import torch
 
 from . import build as _build
 
 _c = ctypes
-_f32p, _i32p, _i64p, _f64p, _vp = _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p
 
 NLL_HAS_PI = 1
 NLL_CONST_DISP = 2
@@ -51,183 +51,43 @@ ACT_PRE = 12        # codes from here up take their slope from the pre-activatio
 
 OPT_KINDS = {'sgd': 0, 'rmsprop': 1, 'adagrad': 2, 'adadelta': 3, 'adam': 4, 'adamax': 5}
 
-_SIGNATURES = {
-    'dcahip_version': (_c.c_int, []),
-    'dcahip_zinb_max_partials': (_c.c_int, []),
-    'dcahip_zinb_nll': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
-                                   _i32p, _i64p, _c.c_int, _c.c_int, _c.c_float, _c.c_float,
-                                   _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f64p,
-                                   _c.POINTER(_c.c_int), _vp]),
-    'dcahip_zinb_nll_planes': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
-                                          _i32p, _i64p, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int,
-                                          _c.c_void_p, _c.c_long, _c.c_long, _c.c_long, _c.c_long, _c.c_long,
-                                          _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp]),
-    'dcahip_nll_marginals_workspace_doubles': (_c.c_int, [_c.c_int, _c.c_int]),
-    'dcahip_nll_marginals': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
-                                        _c.c_int, _c.c_int, _c.c_float, _c.c_int, _f64p, _f64p, _f64p, _vp]),
-    'dcahip_loss_finalize': (_c.c_int, [_f64p, _c.c_int, _c.c_double, _f32p, _vp]),
-    'dcahip_step_end': (_c.c_int, [_f32p, _c.c_double, _f32p, _c.c_int, _f64p, _i64p, _c.c_int, _vp]),
-    'dcahip_zinb_heads_infer': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int,
-                                           _f32p, _f32p, _f32p, _c.c_long, _c.c_int, _vp]),
-    'dcahip_heads_fused_workspace_bytes': (_c.c_long, [_c.c_int, _c.c_int, _c.c_int, _c.c_long, _c.c_int]),
-    'dcahip_heads_fused': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                      _f32p, _c.c_long, _f32p, _i32p, _i64p, _c.c_int, _c.c_int,
-                                      _c.c_int, _c.c_float, _c.c_float, _c.c_int, _f32p, _c.c_long,
-                                      _f32p, _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp,
-                                      _c.c_long, _vp]),
-    'dcahip_heads_tile_order_len': (_c.c_int, [_c.c_int]),
-    'dcahip_x3_product_32x32': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_int, _vp]),
-    'dcahip_heads_fused_ordered': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                              _f32p, _c.c_long, _f32p, _i32p, _i64p, _c.c_int, _c.c_int,
-                                              _c.c_int, _c.c_float, _c.c_float, _c.c_int, _f32p, _c.c_long,
-                                              _f32p, _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp,
-                                              _c.c_long, _i32p, _vp]),
-    'dcahip_transpose': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_hidden_small_chain': (_c.c_int, [_c.POINTER(SmallLayer), _c.c_int, _f32p, _c.c_long, _c.c_int, _c.c_int,
-                                             _c.c_float, _c.c_float, _c.c_int, _vp]),
-    'dcahip_transpose_rows': (_c.c_int, [_f32p, _c.c_long, _i32p, _i64p, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_heads_fused_loss': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                           _f32p, _c.c_long, _f32p, _i32p, _i64p, _c.c_int, _c.c_int,
-                                           _c.c_int, _c.c_float, _c.c_float, _c.c_int, _f32p, _c.c_long,
-                                           _f32p, _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp,
-                                           _c.c_long, _i32p, _f32p, _vp]),
-    'dcahip_sgemm': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_long,
-                                _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _i32p, _i64p, _c.c_int,
-                                _c.c_int, _vp, _c.c_long, _vp]),
-    'dcahip_sgemm_workspace_bytes': (_c.c_long, [_c.c_int] * 7),
-    'dcahip_split_planes': (_c.c_int, [_f32p, _c.c_long, _c.c_void_p, _c.c_void_p, _c.c_long, _c.c_int, _c.c_void_p,
-                                       _c.c_long, _c.c_long, _c.c_void_p]),
-    'dcahip_gemm_p3': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_long, _c.c_long,
-                                  _c.c_void_p, _c.c_long, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_void_p, _c.c_void_p,
-                                  _c.c_int, _c.c_int, _c.c_void_p, _c.c_long, _c.c_void_p]),
-    'dcahip_gemm_p3_workspace_bytes': (_c.c_long, [_c.c_int] * 5),
-    'dcahip_col_moments_chunks': (_c.c_int, [_c.c_int]),
-    'dcahip_col_moments': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _vp]),
-    'dcahip_moments_combine': (_c.c_int, [_f32p, _f32p, _c.c_int, _c.c_int, _f32p, _vp]),
-    'dcahip_bn_relu_apply': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _c.c_int,
-                                        _f32p, _f32p, _f32p, _c.c_float, _c.c_float, _c.c_int,
-                                        _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _vp]),
-    'dcahip_bn_bwd_sums': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _c.c_int,
-                                      _c.c_int, _f32p, _c.c_int, _vp]),
-    'dcahip_bn_bwd_apply': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                       _f32p, _c.c_int, _c.c_float, _c.c_int, _c.c_int, _f32p,
-                                       _c.c_long, _f32p, _c.c_int, _vp]),
-    'dcahip_bn_bwd_sums_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _c.c_int,
-                                          _c.c_int, _f32p, _c.c_int, _f32p, _vp]),
-    'dcahip_bn_bwd_apply_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                           _f32p, _c.c_int, _c.c_float, _c.c_int, _c.c_int, _f32p,
-                                           _c.c_long, _f32p, _c.c_int, _f32p, _vp]),
-    'dcahip_bn_fused_max_rows': (_c.c_int, []),
-    'dcahip_dense_small_max_k': (_c.c_int, []),
-    'dcahip_dense_bn_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                         _f32p, _f32p, _f32p, _c.c_float, _c.c_float, _c.c_int, _f32p, _c.c_long, _f32p,
-                                         _c.c_long, _f32p, _c.c_long, _f32p, _vp]),
-    'dcahip_dense_bn_bwd_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p, _c.c_long,
-                                             _f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int,
-                                             _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _vp]),
-    'dcahip_dense_bn_bwd_small_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _f32p,
-                                                 _c.c_long, _f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                                 _c.c_float, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
-                                                 _vp]),
-    'dcahip_bn_relu_train_small': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _f32p, _c.c_float,
-                                              _c.c_float, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _vp]),
-    'dcahip_bn_bwd_small': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_float,
-                                       _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_int, _vp]),
-    'dcahip_bn_bwd_small_pre': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_float,
-                                           _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_int, _f32p, _vp]),
-    'dcahip_rmsprop_clip_end': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_float, _c.c_float, _c.c_float,
-                                           _f32p, _c.c_double, _f32p, _c.c_int, _f64p, _i64p, _c.c_int, _vp]),
-    'dcahip_relu_bwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p,
-                                   _c.c_long, _c.c_int, _vp]),
-    'dcahip_relu_fwd': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _c.c_int, _vp]),
-    'dcahip_colsum_chain': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _vp]),
-    'dcahip_optimizer_step': (_c.c_int, [_c.c_int, _f32p, _f32p, _f32p, _f32p, _c.c_long, _f32p, _i64p,
-                                         _c.c_float, _vp]),
-    'dcahip_counter_add': (_c.c_int, [_i64p, _c.c_int, _vp]),
-    'dcahip_prelu_workspace_doubles': (_c.c_int, [_c.c_int]),
-    'dcahip_prelu_fwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_prelu_bwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int, _f32p, _f64p, _vp]),
-    'dcahip_elempi_workspace_doubles': (_c.c_int, [_c.c_int]),
-    'dcahip_elempi_fwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _f32p, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_elempi_bwd': (_c.c_int, [_f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int, _f32p, _f32p,
-                                     _f64p, _vp]),
-    'dcahip_bcast_cols': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_row_sums_strided': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _vp]),
-    'dcahip_nadam_step': (_c.c_int, [_f32p, _f32p, _f32p, _f32p, _c.c_long, _f32p, _i64p, _f32p, _c.c_float, _vp]),
-    'dcahip_dropout_apply': (_c.c_int, [_f32p, _c.c_long, _i32p, _i64p, _c.c_int, _c.c_int, _c.c_float,
-                                        _c.c_ulonglong, _i64p, _c.c_int, _c.c_long, _f32p, _c.c_long, _vp]),
-    'dcahip_l1l2_workspace_doubles': (_c.c_int, []),
-    'dcahip_l1l2_apply': (_c.c_int, [_c.POINTER(RegDesc), _f32p, _f32p, _f32p, _f64p, _vp]),
-    'dcahip_prep_chunks': (_c.c_int, [_c.c_int]),
-    'dcahip_prep_row_sums': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _vp]),
-    'dcahip_prep_col_pass': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_int, _f32p,
-                                        _c.c_long, _f64p, _vp]),
-    'dcahip_prep_col_finish': (_c.c_int, [_f64p, _c.c_int, _c.c_int, _c.c_double, _f32p, _f32p, _f32p, _vp]),
-    'dcahip_prep_scale': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _f32p, _vp]),
-    'dcahip_csr_expand': (_c.c_int, [_i32p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_long, _i32p, _vp]),
-    'dcahip_csr_compress': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_long, _i64p, _i32p, _f32p, _c.c_long, _i32p,
-                                       _vp]),
-    'dcahip_csr_subset': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _vp, _vp, _c.c_int, _i64p, _i32p,
-                                     _f32p, _c.c_long, _i32p, _i32p, _vp]),
-    'dcahip_csr_gather': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
-                                     _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p, _i32p,
-                                     _vp]),
-    'dcahip_csr_gather_cols': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long, _c.c_int,
-                                          _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                          _i32p, _i32p, _c.c_int, _vp]),
-    'dcahip_csr_gather_compact': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _i32p, _i64p, _c.c_long,
-                                             _c.c_int, _f32p, _f32p, _c.c_int, _f32p, _f32p, _vp, _c.c_long, _i32p, _i32p,
-                                             _f32p, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _i32p, _vp]),
-    'dcahip_csr_col_pass': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _c.c_int, _f64p, _i32p,
-                                       _vp]),
-    'dcahip_csr_row_sums': (_c.c_int, [_i64p, _i32p, _f32p, _c.c_long, _c.c_int, _c.c_int, _f32p, _i32p, _vp]),
-    'dcahip_rmsprop_clip': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _c.c_float,
-                                       _c.c_float, _c.c_float, _vp]),
-    'dcahip_hidden_stack_max_rows': (_c.c_int, []),
-    'dcahip_hidden_stack_workspace_bytes': (_c.c_long, [_c.c_int, _c.c_int]),
-    'dcahip_hidden_stack_fwd': (_c.c_int, [_c.POINTER(SmallLayer), _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int,
-                                           _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_long, _vp]),
-    'dcahip_hidden_stack_bwd': (_c.c_int, [_c.POINTER(StackBwdLayer), _c.c_int, _c.c_int, _c.c_float, _c.c_int,
-                                           _f32p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_long, _vp]),
-    'dcahip_hidden_stack_step_blocks': (_c.c_int, [_c.c_int]),
-    'dcahip_hidden_stack_fwd_sync': (_c.c_int, [_c.POINTER(SmallLayer), _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int,
-                                                _c.c_int, _f32p, _f32p, _c.c_int, _f32p, _vp, _c.c_long, _vp]),
-    'dcahip_hidden_stack_bwd_sync': (_c.c_int, [_c.POINTER(StackBwdLayer), _c.c_int, _c.c_int, _c.c_float, _c.c_int,
-                                                _f32p, _c.c_long, _c.c_int, _f32p, _f32p, _vp, _c.c_long, _vp]),
-    'dcahip_counts_compact_ld': (_c.c_long, [_c.c_int]),
-    'dcahip_counts_compact': (_c.c_int, [_f32p, _c.c_long, _c.c_int, _c.c_int, _vp, _c.c_long, _i32p, _vp]),
-    'dcahip_enc0_sparse_supported': (_c.c_int, [_c.c_int]),
-    'dcahip_enc0_dw_sparse_workspace_bytes': (_c.c_long, [_c.c_int, _c.c_int, _c.c_int]),
-    'dcahip_enc0_lut': (_c.c_int, [_f32p, _c.c_int, _c.c_int, _vp, _vp]),
-    'dcahip_enc0_dw_sparse': (_c.c_int, [_vp, _c.c_long, _i32p, _i32p, _f32p, _f32p, _c.c_int, _f32p, _f32p, _f32p, _i32p, _i64p,
-                                         _c.c_long, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _c.c_long,
-                                         _vp, _c.c_long, _c.c_int, _vp]),
-    'dcahip_peer_slot_bytes': (_c.c_long, [_c.c_int, _c.c_int]),
-    'dcahip_peer_flag_bytes': (_c.c_long, [_c.c_int]),
-    'dcahip_peer_exchange': (_c.c_int, [_f32p, _c.c_int, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _vp, _f32p, _c.c_int, _i32p,
-                                        _c.c_long, _vp]),
-    'dcahip_enc0_lut_entries': (_c.c_int, []),
-    'dcahip_enc0_fwd_lut_workspace_bytes': (_c.c_long, [_c.c_int, _c.c_int, _c.c_int]),
-    'dcahip_enc0_fwd_lut': (_c.c_int, [_vp, _c.c_long, _i32p, _i32p, _f32p, _f32p, _c.c_int, _vp, _f32p, _f32p, _i32p, _i64p,
-                                       _c.c_long, _c.c_int, _c.c_int, _c.c_int, _f32p, _c.c_long, _f32p, _f32p, _c.c_long,
-                                       _vp, _c.c_long, _vp]),
-    'dcahip_absmax_exp': (_c.c_int, [_f32p, _c.c_long, _c.c_long, _c.c_int, _i32p, _vp, _vp]),
-    'dcahip_split_planes_h2': (_c.c_int, [_f32p, _c.c_long, _i32p, _i64p, _c.c_long, _c.c_int, _vp, _c.c_long, _c.c_long, _i32p, _vp]),
-    'dcahip_gemm_h2_supported': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
-    'dcahip_gemm_h2_workspace_bytes': (_c.c_long, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
-    'dcahip_gemm_h2': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp, _c.c_long, _c.c_long, _i32p, _c.c_int,
-                                  _vp, _c.c_long, _c.c_long, _i32p, _c.c_int, _c.c_float, _f32p, _c.c_long, _f32p, _c.c_int, _c.c_int,
-                                  _vp, _c.c_long, _vp]),
-    'dcahip_zinb_nll_planes_h2': (_c.c_int, [_f32p, _f32p, _f32p, _c.c_long, _f32p, _f32p, _c.c_long, _f32p,
-                                             _i32p, _i64p, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int, _c.c_int,
-                                             _vp, _c.c_long, _c.c_long, _c.c_long, _c.c_long, _c.c_long, _f32p, _c.c_long, _f64p,
-                                             _c.POINTER(_c.c_int), _vp]),
-    'dcahip_heads_fused_compact': (_c.c_int, [_f32p, _c.c_long, _f32p, _c.c_long, _f32p, _c.c_long, _f32p,
-                                              _f32p, _c.c_long, _vp, _c.c_long, _i32p, _i32p, _f32p, _f32p, _i32p, _i64p,
-                                              _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_int, _f32p,
-                                              _c.c_long, _f32p, _f32p, _c.c_long, _f64p, _c.POINTER(_c.c_int), _vp,
-                                              _c.c_long, _i32p, _f32p, _c.c_int, _vp]),
-}
+_SCALARS = {'int': _c.c_int, 'long': _c.c_long, 'long long': _c.c_long, 'unsigned long long': _c.c_ulonglong,
+            'float': _c.c_float, 'double': _c.c_double}
+_STRUCTS = {'dcahip_small_layer': SmallLayer, 'dcahip_stack_bwd_layer': StackBwdLayer, 'dcahip_reg_desc': RegDesc}
+_POINTEES = set(_SCALARS) | {'void', 'unsigned', 'unsigned char'}
+
+
+def _ctype(param):
+    """ctypes type of one parameter of a declaration ('long ldh', 'const float* beta', 'unsigned* const* flags')."""
+    words = param.replace('*', ' * ').split()
+    if '*' in words:
+        base = ' '.join(w for w in words[:words.index('*')] if w != 'const')
+        if base in _STRUCTS:
+            return _c.POINTER(_STRUCTS[base])
+        if base in _POINTEES:
+            return _c.c_void_p
+    elif ' '.join(words[:-1]) in _SCALARS:               # the last word is the parameter's name
+        return _SCALARS[' '.join(words[:-1])]
+    raise ValueError('dca_amd.hip: include/dcahip.h: cannot bind the parameter %r' % param)
+
+
+def _parse_header(text):
+    """{name: (restype, argtypes)} of every `int|long dcahip_*(...)` declaration of the header text.  A declaration that
+    does not have that form, or a parameter type without a ctypes counterpart, raises: an entry point is never skipped."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    sigs = {}
+    for res, name, params in re.findall(r'\b(int|long)\s+(dcahip_\w+)\s*\(([^()]*)\)\s*;', text):
+        params = [q.strip() for q in params.split(',')]
+        sigs[name] = (_SCALARS[res], [] if params in ([''], ['void']) else [_ctype(q) for q in params])
+    missed = set(re.findall(r'\b(dcahip_\w+)\s*\(', text)) - set(sigs)
+    if missed:
+        raise ValueError('dca_amd.hip: include/dcahip.h: cannot split the declaration of %s' % ', '.join(sorted(missed)))
+    return sigs
+
+
+# the header the library is compiled against (build.py fingerprints it) is the one table of argument types
+with open(os.path.join(_build.ROOT, 'include', 'dcahip.h')) as _f:
+    _SIGNATURES = _parse_header(_f.read())
 
 _lib = None
 
@@ -257,7 +117,7 @@ def lib():
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(L, name)          # AttributeError => header / library mismatch: loud
         fn.restype, fn.argtypes = res, args
-    assert L.dcahip_version() == 1
+    assert L.dcahip_version() == 2
     _lib = L
     return L
 

@@ -105,15 +105,15 @@ class HipOps:
         n = ctypes.c_int(0)
         p = hip.ptr
         c = compact
-        hip.check(self.L.dcahip_heads_fused_compact(p(H), ldh, p(Wh), ldw, p(bh), plane, p(theta_w), p(Y), ldy,
-                                                    p(c.Yc) if c is not None else None, c.ldc if c is not None else 0,
-                                                    p(c.ovf_ptr) if c is not None else None,
-                                                    p(c.ovf_col) if c is not None else None,
-                                                    p(c.ovf_val) if c is not None else None,
-                                                    p(sf), p(perm), p(cursor), B, hL, G, ridge, inv_n, flags,
-                                                    p(gW), ldg, p(g_theta), p(dH), lddh, p(partials),
-                                                    ctypes.byref(n), p(ws), ws.numel() * ws.element_size(),
-                                                    p(tile_order), p(loss_out), int(d_exp), hip.stream()), 'heads_fused')
+        hip.check(self.L.dcahip_heads_fused(p(H), ldh, p(Wh), ldw, p(bh), plane, p(theta_w), p(Y), ldy,
+                                            p(c.Yc) if c is not None else None, c.ldc if c is not None else 0,
+                                            p(c.ovf_ptr) if c is not None else None,
+                                            p(c.ovf_col) if c is not None else None,
+                                            p(c.ovf_val) if c is not None else None,
+                                            p(sf), p(perm), p(cursor), B, hL, G, ridge, inv_n, flags,
+                                            p(gW), ldg, p(g_theta), p(dH), lddh, p(partials),
+                                            ctypes.byref(n), p(ws), ws.numel() * ws.element_size(),
+                                            p(tile_order), p(loss_out), int(d_exp), hip.stream()), 'heads_fused')
         return n.value
 
     # ------------------------------------------------------------------ compact counts, sparse first layer
@@ -243,28 +243,19 @@ class HipOps:
                                               p(mm), p(mv), momentum, eps, int(relu), p(Hout), ldh,
                                               p(xhat), ldx, p(inv_std), hip.stream()), 'bn_relu_apply')
 
-    # beta (the batch-backward entries below): the layer's batch-norm offset, which codes >= hip.ACT_PRE need for their
-    # pre-activation xhat + beta; given, the *_pre entry point is called
+    # beta (the batch-norm backward entries below): the layer's batch-norm offset, which codes >= hip.ACT_PRE need for their
+    # pre-activation xhat + beta; the other codes do not read it (None: NULL)
     def bn_bwd_sums(self, dH, ldd, Hact, ldh, xhat, ldx, B, H, part, act=1, beta=None):
         p = hip.ptr
-        if beta is not None:
-            hip.check(self.L.dcahip_bn_bwd_sums_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, B, H, p(part),
-                                                    act, p(beta), hip.stream()), 'bn_bwd_sums_pre')
-            return
         hip.check(self.L.dcahip_bn_bwd_sums(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, B, H, p(part),
-                                            act, hip.stream()), 'bn_bwd_sums')
+                                            act, p(beta), hip.stream()), 'bn_bwd_sums')
 
     def bn_bwd_apply(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, sums, E, n_total, B, H, dZ, ldz,
                      dbeta, act=1, beta=None):
         p = hip.ptr
-        if beta is not None:
-            hip.check(self.L.dcahip_bn_bwd_apply_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std),
-                                                     p(sums), E, float(n_total), B, H, p(dZ), ldz, p(dbeta),
-                                                     act, p(beta), hip.stream()), 'bn_bwd_apply_pre')
-            return
         hip.check(self.L.dcahip_bn_bwd_apply(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std),
                                              p(sums), E, float(n_total), B, H, p(dZ), ldz, p(dbeta),
-                                             act, hip.stream()), 'bn_bwd_apply')
+                                             act, p(beta), hip.stream()), 'bn_bwd_apply')
 
     @property
     def bn_fused_max_rows(self):
@@ -278,12 +269,8 @@ class HipOps:
 
     def bn_bwd_small(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, n_total, B, H, dZ, ldz, dbeta, act=1, beta=None):
         p = hip.ptr
-        if beta is not None:
-            hip.check(self.L.dcahip_bn_bwd_small_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), float(n_total), B,
-                                                     H, p(dZ), ldz, p(dbeta), act, p(beta), hip.stream()), 'bn_bwd_small_pre')
-            return
         hip.check(self.L.dcahip_bn_bwd_small(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), float(n_total), B, H,
-                                             p(dZ), ldz, p(dbeta), act, hip.stream()), 'bn_bwd_small')
+                                             p(dZ), ldz, p(dbeta), act, p(beta), hip.stream()), 'bn_bwd_small')
 
     @property
     def dense_small_max_k(self):
@@ -298,12 +285,7 @@ class HipOps:
 
     def hidden_small_chain(self, layers, Hin, ldin, B, batchnorm, momentum, eps, act):
         """layers: dicts with the fields of dcahip_small_layer (tensors or None); one launch for the whole list."""
-        arr = (hip.SmallLayer * len(layers))()
-        for q, d in zip(arr, layers):
-            for k in ('W', 'bias', 'beta', 'moving_mean', 'moving_var', 'Z', 'xhat', 'Hout', 'inv_std'):
-                setattr(q, k, hip.ptr(d.get(k)))
-            for k in ('ldw', 'K', 'H', 'ldz', 'ldx', 'ldh'):
-                setattr(q, k, int(d.get(k, 0)))
+        arr = self._small_layers(layers)
         hip.check(self.L.dcahip_hidden_small_chain(arr, len(layers), hip.ptr(Hin), ldin, B, int(batchnorm), momentum, eps,
                                                    int(act), hip.stream()), 'hidden_small_chain')
 
@@ -318,12 +300,7 @@ class HipOps:
     def hidden_stack_fwd(self, layers, B, momentum, eps, act, ws, rows_per_wg=64, steps=None):
         """layers: dicts with the fields of dcahip_small_layer; entry 0 without a kernel (its Z comes from the first GEMM).
         steps = (first, last) of the pass's n + 1 steps in ONE launch (default: all of them, cooperative)."""
-        arr = (hip.SmallLayer * len(layers))()
-        for q, d in zip(arr, layers):
-            for k in ('W', 'bias', 'beta', 'moving_mean', 'moving_var', 'Z', 'xhat', 'Hout', 'inv_std'):
-                setattr(q, k, hip.ptr(d.get(k)))
-            for k in ('ldw', 'K', 'H', 'ldz', 'ldx', 'ldh'):
-                setattr(q, k, int(d.get(k, 0)))
+        arr = self._small_layers(layers)
         first, last = steps if steps is not None else (0, len(layers))
         hip.check(self.L.dcahip_hidden_stack_fwd(arr, len(layers), B, momentum, eps, int(act), int(rows_per_wg), first, last,
                                                  hip.ptr(ws), ws.numel() * ws.element_size(), hip.stream()), 'hidden_stack_fwd')
@@ -331,19 +308,14 @@ class HipOps:
     def hidden_stack_bwd(self, layers, B, n_total, act, dZ0, ldz0, ws, rows_per_wg=64, steps=None):
         """layers: dicts with the fields of dcahip_stack_bwd_layer; steps = (first, last) of the pass's n + 2 steps.
         A whole pass over a batch of at most 64 rows is one workgroup's work and needs no workspace (ws=None)."""
-        arr = (hip.StackBwdLayer * len(layers))()
-        for q, d in zip(arr, layers):
-            for k in ('W', 'Hact', 'xhat', 'inv_std', 'Hprev', 'gW', 'dbeta', 'dH', 'beta'):
-                setattr(q, k, hip.ptr(d.get(k)))
-            for k in ('ldw', 'K', 'H', 'ldh', 'ldx', 'ldp', 'ldg', 'lddh'):
-                setattr(q, k, int(d.get(k, 0)))
+        arr = self._bwd_layers(layers)
         first, last = steps if steps is not None else (0, len(layers) + 1)
         hip.check(self.L.dcahip_hidden_stack_bwd(arr, len(layers), B, float(n_total), int(act), hip.ptr(dZ0), ldz0,
                                                  int(rows_per_wg), first, last, hip.ptr(ws),
                                                  0 if ws is None else ws.numel() * ws.element_size(),
                                                  hip.stream()), 'hidden_stack_bwd')
 
-    # ---- K-STACK between the exchanges of a data-parallel step (SyncBN): one step per call
+    # ---- the two layer structs of include/dcahip.h, filled from dicts with their fields (tensors or None; absent: NULL / 0)
     def _small_layers(self, layers):
         arr = (hip.SmallLayer * len(layers))()
         for q, d in zip(arr, layers):
@@ -362,6 +334,7 @@ class HipOps:
                 setattr(q, k, int(d.get(k, 0)))
         return arr
 
+    # ---- K-STACK between the exchanges of a data-parallel step (SyncBN): one step per call
     def hidden_stack_fwd_sync(self, layers, B, momentum, eps, act, step, ext_entries, ext_counts, ext_E, stat_out, ws):
         """Step `step` of the forward pass with the input layer's statistics from every rank (ext_entries [E, 2, H],
         ext_counts [E]); stat_out [2, H'] <- this rank's (mean, M2) of the layer made."""
@@ -380,15 +353,9 @@ class HipOps:
     def dense_bn_bwd_small(self, dH, ldd, Hact, ldh, xhat, ldx, inv_std, Hp, ldp, W, ldw, B, K, H, batchnorm, n_total, act,
                            gW, ldg, dbeta, dHp, lddp, beta=None):
         p = hip.ptr
-        if beta is not None:
-            hip.check(self.L.dcahip_dense_bn_bwd_small_pre(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), p(Hp), ldp,
-                                                           p(W), ldw, B, K, H, int(batchnorm), float(n_total), int(act),
-                                                           p(gW), ldg, p(dbeta), p(dHp), lddp, p(beta), hip.stream()),
-                      'dense_bn_bwd_small_pre')
-            return
         hip.check(self.L.dcahip_dense_bn_bwd_small(p(dH), ldd, p(Hact), ldh, p(xhat), ldx, p(inv_std), p(Hp), ldp, p(W), ldw,
                                                    B, K, H, int(batchnorm), float(n_total), int(act), p(gW), ldg, p(dbeta),
-                                                   p(dHp), lddp, hip.stream()), 'dense_bn_bwd_small')
+                                                   p(dHp), lddp, p(beta), hip.stream()), 'dense_bn_bwd_small')
 
     def relu_bwd(self, dH, ldd, Hact, ldh, B, H, dZ, ldz, act=1):
         p = hip.ptr
@@ -570,12 +537,10 @@ class HipOps:
 
     # ------------------------------------------------------------------ optimizer
     def rmsprop_clip_end(self, w, g, ms, n, lr, rho, eps, clip, loss, weight, hist, rows_per_slot, acc, cursor, advance):
+        """The update followed by step_end's bookkeeping in the same launch (include/dcahip.h: dcahip_rmsprop_clip)."""
         p = hip.ptr
-        hip.check(self.L.dcahip_rmsprop_clip_end(p(w), p(g), p(ms), n, p(lr), rho, eps, clip, p(loss), weight, p(hist),
-                                                 rows_per_slot, p(acc), p(cursor), advance, hip.stream()),
-                  'rmsprop_clip_end')
+        hip.check(self.L.dcahip_rmsprop_clip(p(w), p(g), p(ms), n, p(lr), rho, eps, clip, p(loss), weight, p(hist),
+                                             rows_per_slot, p(acc), p(cursor), advance, hip.stream()), 'rmsprop_clip')
 
     def rmsprop_clip(self, w, g, ms, n, lr, rho, eps, clip):
-        p = hip.ptr
-        hip.check(self.L.dcahip_rmsprop_clip(p(w), p(g), p(ms), n, p(lr), rho, eps, clip,
-                                             hip.stream()), 'rmsprop_clip')
+        self.rmsprop_clip_end(w, g, ms, n, lr, rho, eps, clip, None, 0.0, None, 0, None, None, 0)

@@ -27,7 +27,7 @@
  *     replayed for every batch of an epoch.
  *   - activation slopes: the backward entries of the hidden layers derive the slope of codes 0-11 from the
  *     layer's OUTPUT h, and of the non-monotonic codes 12 (swish) and 13 (gelu) from its PRE-activation:
- *     xhat + beta with batch norm (the `beta` argument of the *_pre entries, the `beta` field of
+ *     xhat + beta with batch norm (the `beta` argument of the batch-norm backward entries, the `beta` field of
  *     dcahip_stack_bwd_layer; NULL allowed for codes 0-11), Z in the `Hact` slot without (see
  *     dcahip_bn_relu_apply for the code list).
  */
@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define DCAHIP_VERSION 1
+#define DCAHIP_VERSION 2
 #define DCAHIP_EINVAL (-22)
 
 /* flags for dcahip_zinb_nll */
@@ -176,24 +176,51 @@ int dcahip_zinb_heads_infer(const float* a_mean, const float* a_disp, const floa
  *                     heads skipped), `plane` columns apart (plane % 4 == 0, G <= plane <=
  *                     roundup32(G)); bh [nheads*plane] the biases in the same layout
  *   theta_w [G]     : log-dispersion (CONST_DISP only)
- *   y, ldy, sf, perm, cursor, ridge, inv_n, flags : as dcahip_zinb_nll
+ *   y, ldy, sf, perm, cursor, inv_n, flags : as dcahip_zinb_nll; ridge likewise, and it must lie in [0, 1e3]
  *   gW [hL+1, ldg]  : OUT weight gradient in the layout of Wh; row hL = bias gradient
  *   g_theta [G]     : OUT d loss / d theta_w (CONST_DISP only)
  *   dH [B, lddh]    : OUT gradient w.r.t. H (columns < hL)
- *   loss_partials   : as dcahip_zinb_nll (finish with dcahip_loss_finalize)
+ *   loss_partials   : as dcahip_zinb_nll
  *   workspace       : >= dcahip_heads_fused_workspace_bytes(...) bytes, 16-byte aligned
+ * Optional arguments:
+ *   yc, ldc, ovf_ptr, ovf_col, ovf_val : the counts read from the compact store of K-SPARSE (below; 4 x fewer count bytes
+ *                     per launch): yc != NULL selects it, y / ldy are then unused and may be NULL / 0.  yc == NULL: the
+ *                     fp32 counts y (ldc and the overflow list are ignored).
+ *   tile_order      : the order in which workgroups take the 32-gene tiles: a device array of
+ *                     dcahip_heads_tile_order_len(G) ints, a permutation of 0 .. ceil(G/32)-1 (padded with values >=
+ *                     ceil(G/32)); every 2 consecutive entries share a workgroup.  NULL = identity.  Results do not depend
+ *                     on it beyond fp32 re-association (the weight gradients are per gene tile: bitwise the same for every
+ *                     order, except that a launch whose plan ends in a poorly filled round of workgroups hands the LAST
+ *                     tiles of the order to a second launch with more batch splits -- e.g. 25 000 genes x 4 096 rows -- and
+ *                     a tile's gradient is then the sum of 8 or 16 partial sums instead of 2); for a FIXED order every
+ *                     result is bit for bit reproducible.  A workgroup lasts as long as its slower tile, so pairing tiles
+ *                     of similar non-zero load (sort by the non-zero count of the tile's 32 count columns) removes the
+ *                     imbalance: measured 15 % between the two tiles of a workgroup in file order, 8 % of the kernel.
+ *   loss_out        : != NULL: the batch loss (inv_n * sum of the partials, nan -> inf: what dcahip_loss_finalize
+ *                     computes) is written there by the last launch of the call -- one launch less per step.  NULL:
+ *                     finish the loss with dcahip_loss_finalize.
+ *   d_exp           : in [-24, 0], 0 by default: the kernel carries the gradient planes as g 2^(8 + d_exp) (kDExp0 = 8) in
+ *                     two fp16 pieces, g = the UNSCALED d nll / d pre-activation, |g| <= max(theta, ~2 y): |g| <= 117 fits
+ *                     at d_exp = 0.  A 32 x 32 tile with a larger value repeats at the exponent its maximum needs (a slow
+ *                     path, exact, but the whole tile is then carried at that exponent: 2^-(kDe + 25) absolute on every g of
+ *                     it); a caller whose counts reach c throughout passes d_exp = -ceil(log2(2 c / 117))
+ *                     (Engine._heads_d_exp) and keeps the tiles on the fast path.
  * Supported: 1 <= hL <= 64 (workspace_bytes query returns 0 otherwise -> use the separate
  * kernels).  Deterministic (fixed summation order, no atomics).
  */
 long dcahip_heads_fused_workspace_bytes(int B, int hL, int G, long plane, int flags);
+int dcahip_heads_tile_order_len(int G);
 int dcahip_heads_fused(const float* H, long ldh, const float* Wh, long ldw, const float* bh,
                        long plane, const float* theta_w,
-                       const float* y, long ldy, const float* sf,
+                       const float* y, long ldy,
+                       const unsigned char* yc, long ldc, const int* ovf_ptr, const int* ovf_col,
+                       const float* ovf_val, const float* sf,
                        const int* perm, const long long* cursor,
                        int B, int hL, int G, float ridge, float inv_n, int flags,
                        float* gW, long ldg, float* g_theta, float* dH, long lddh,
                        double* loss_partials, int* n_partials_out,
-                       void* workspace, long workspace_bytes, void* stream);
+                       void* workspace, long workspace_bytes, const int* tile_order,
+                       float* loss_out, int d_exp, void* stream);
 /* The arithmetic of K-HEADS' three matrix products, exposed for testing: C [32, 32] = A [32, K] B [K, 32]
  * (row-major fp32, K % 16 == 0) computed as the kernel does -- each operand scaled by the power of two that brings its
  * largest magnitude into [2^13, 2^14) and split into TWO fp16 pieces (round-to-nearest residual: 2^-22 relative, 2^-25
@@ -202,37 +229,6 @@ int dcahip_heads_fused(const float* H, long ldh, const float* Wh, long ldw, cons
  * (tests/test_heads_fused_gpu.py): |C - A B| <= 5e-7 sum|a b| per element, i.e. the accuracy of an fp32 dot product
  * (the fp32 MFMA measures 1.8e-7 .. 2.1e-7 on the same inputs; three bf16 pieces with six products, rounds 2-5: <= 2.5e-7). */
 int dcahip_x3_product_32x32(const float* A, const float* B, float* C, int K, void* stream);
-/* Same, with the order in which workgroups take the 32-gene tiles: tile_order = device array of
- * dcahip_heads_tile_order_len(G) ints, a permutation of 0 .. ceil(G/32)-1 (padded with values >= ceil(G/32));
- * every 2 consecutive entries share a workgroup.  Results do not depend on it beyond fp32 re-association (the weight gradients
- * are per gene tile: bitwise the same for every order, except that a launch whose plan ends in a poorly filled round of
- * workgroups hands the LAST tiles of the order to a second launch with more batch splits -- e.g. 25 000 genes x 4 096 rows --
- * and a tile's gradient is then the sum of 8 or 16 partial sums instead of 2); for a FIXED order every result is bit for
- * bit reproducible.  A workgroup
- * lasts as long as its slower tile, so pairing tiles of similar non-zero load (sort by the non-zero count of the
- * tile's 32 count columns) removes the imbalance: measured 15 % between the two tiles of a workgroup in file order,
- * 8 % of the kernel.  NULL = identity (what dcahip_heads_fused passes). */
-int dcahip_heads_tile_order_len(int G);
-
-int dcahip_heads_fused_ordered(const float* H, long ldh, const float* Wh, long ldw, const float* bh,
-                               long plane, const float* theta_w,
-                               const float* y, long ldy, const float* sf,
-                               const int* perm, const long long* cursor,
-                               int B, int hL, int G, float ridge, float inv_n, int flags,
-                               float* gW, long ldg, float* g_theta, float* dH, long lddh,
-                               double* loss_partials, int* n_partials_out,
-                               void* workspace, long workspace_bytes, const int* tile_order, void* stream);
-/* Same; when loss_out != NULL the batch loss (inv_n * sum of the partials, nan -> inf: what dcahip_loss_finalize
- * computes) is written there by the last launch of the call -- one launch less per step. */
-int dcahip_heads_fused_loss(const float* H, long ldh, const float* Wh, long ldw, const float* bh,
-                            long plane, const float* theta_w,
-                            const float* y, long ldy, const float* sf,
-                            const int* perm, const long long* cursor,
-                            int B, int hL, int G, float ridge, float inv_n, int flags,
-                            float* gW, long ldg, float* g_theta, float* dH, long lddh,
-                            double* loss_partials, int* n_partials_out,
-                            void* workspace, long workspace_bytes, const int* tile_order,
-                            float* loss_out, void* stream);
 
 /*
  * C[M,N] = op(A) * op(B) (+ bias), fp32 in / fp32 out, LDS-tiled, deterministic split-K through `workspace`.
@@ -332,10 +328,10 @@ int dcahip_transpose_rows(const float* src, long ld_src, const int* perm, const 
  *     layer of its own behind code 0).  The backward entry points take the same code as `act`.
  *     Codes 0-11 derive the slope from the forward OUTPUT h.  Codes 12 and 13 are not monotonic,
  *     so h does not determine the slope: they derive it from the PRE-activation x instead --
- *       with batch norm    x = xhat + beta[c]: the entries named *_pre take `beta` as an extra
- *                          argument (and dcahip_stack_bwd_layer its `beta` field); for codes 12, 13
- *                          it must be non-NULL (DCAHIP_EINVAL otherwise, so the entries without
- *                          the suffix refuse them), for the other codes it is not read;
+ *       with batch norm    x = xhat + beta[c]: the `beta` argument of the batch-norm backward entries
+ *                          (and the `beta` field of dcahip_stack_bwd_layer); for codes 12, 13 it must
+ *                          be non-NULL (DCAHIP_EINVAL otherwise), for the other codes it is not read
+ *                          and may be NULL;
  *       without batch norm x = Z, which the caller passes in the `Hact` slot of dcahip_relu_bwd /
  *                          dcahip_dense_bn_bwd_small(batchnorm = 0) (the slope is its only use there).
  *     B == 0 is legal (only the moving statistics are updated): a data-parallel rank with an
@@ -373,13 +369,8 @@ int dcahip_dense_bn_bwd_small(const float* dH, long ldd, const float* Hact, long
                               const float* xhat, long ldx, const float* inv_std,
                               const float* Hp, long ldp, const float* W, long ldw,
                               int B, int K, int H, int batchnorm, float n_total, int act,
-                              float* gW, long ldg, float* dbeta, float* dHp, long lddp, void* stream);
-int dcahip_dense_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                                  const float* xhat, long ldx, const float* inv_std,
-                                  const float* Hp, long ldp, const float* W, long ldw,
-                                  int B, int K, int H, int batchnorm, float n_total, int act,
-                                  float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
-                                  void* stream);
+                              float* gW, long ldg, float* dbeta, float* dHp, long lddp, const float* beta,
+                              void* stream);
 /* The hidden stack behind the first layer's product in ONE launch (every layer <= 64 units, B <= dcahip_bn_fused_max_rows()):
  * entry 0 with W == NULL normalises + activates its own Z (written by dcahip_sgemm), every entry with a kernel is
  * Dense -> BatchNormalization -> activation on the previous entry's Hout (entry 0 with a kernel reads Hin).  Same
@@ -468,10 +459,7 @@ int dcahip_bn_relu_train_small(const float* Z, long ldz, int B, int H, const flo
                                float* inv_std, void* stream);
 int dcahip_bn_bwd_small(const float* dH, long ldd, const float* Hact, long ldh,
                         const float* xhat, long ldx, const float* inv_std, float n_total,
-                        int B, int H, float* dZ, long ldz, float* dbeta, int act, void* stream);
-int dcahip_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                            const float* xhat, long ldx, const float* inv_std, float n_total,
-                            int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
+                        int B, int H, float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
 
 /*
  * Backward of ReLU + batch norm.  mask = the forward output h (h > 0 <=> pre-ReLU > 0).
@@ -480,21 +468,16 @@ int dcahip_bn_bwd_small_pre(const float* dH, long ldd, const float* Hact, long l
  *  3. dcahip_bn_bwd_apply: dz = inv_std * (dy - S1/n - xhat * S2/n), dbeta = S1
  *     (sums: E entries [E][2][H] are added in order; n_total = global batch rows).
  * Without batch norm use dcahip_relu_bwd (dz = dh*[h>0]).
- * The *_pre forms take `beta` as their last argument before `stream` (codes 12, 13: pre-activation = xhat + beta).
+ * The `beta` argument (the last before `stream`, here and in dcahip_bn_bwd_small / dcahip_dense_bn_bwd_small): the layer's
+ * batch-norm offset, read for codes 12, 13 only (pre-activation = xhat + beta); NULL allowed for codes 0-11.
  */
 int dcahip_bn_bwd_sums(const float* dH, long ldd, const float* Hact, long ldh,
-                       const float* xhat, long ldx, int B, int H, float* part, int act, void* stream);
+                       const float* xhat, long ldx, int B, int H, float* part, int act, const float* beta,
+                       void* stream);
 int dcahip_bn_bwd_apply(const float* dH, long ldd, const float* Hact, long ldh,
                         const float* xhat, long ldx, const float* inv_std,
                         const float* sums, int E, float n_total, int B, int H,
-                        float* dZ, long ldz, float* dbeta, int act, void* stream);
-int dcahip_bn_bwd_sums_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                           const float* xhat, long ldx, int B, int H, float* part, int act, const float* beta,
-                           void* stream);
-int dcahip_bn_bwd_apply_pre(const float* dH, long ldd, const float* Hact, long ldh,
-                            const float* xhat, long ldx, const float* inv_std,
-                            const float* sums, int E, float n_total, int B, int H,
-                            float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
+                        float* dZ, long ldz, float* dbeta, int act, const float* beta, void* stream);
 int dcahip_relu_bwd(const float* dH, long ldd, const float* Hact, long ldh, int B, int H,
                     float* dZ, long ldz, int act, void* stream);
 /* h = max(z, 0): Activation('relu') of a stack built with batchnorm=False (network.py:132-135). */
@@ -625,7 +608,7 @@ int dcahip_csr_subset(const long* indptr, const int* indices, const float* value
  *                         output column are the caller's error: one of the two counts lands there.
  *   dcahip_csr_gather_compact
  *                         the same minibatch tile in the byte-store format of K-SPARSE (below), for the kernels that read
- *                         the compact counts (dcahip_heads_fused_compact, dcahip_enc0_fwd_lut, dcahip_enc0_dw_sparse) with
+ *                         the compact counts (dcahip_heads_fused, dcahip_enc0_fwd_lut, dcahip_enc0_dw_sparse) with
  *                         storage row = tile row.  Writes EVERY byte of Yc[r, 0 .. ldc), ldc = dcahip_counts_compact_ld(G):
  *                         bit for bit what dcahip_counts_compact writes from dcahip_csr_gather's Y tile (counts 0 .. 254 as
  *                         is, 255 = escape, pad columns 0; a value that is not a count is stored as 0 and counted into
@@ -671,15 +654,14 @@ int dcahip_csr_row_sums(const long* indptr, const int* indices, const float* val
  * ApplyRMSProp kernel, taken with momentum > 0, puts it inside.)
  * Replaces opt.RMSprop(lr, clipvalue) (dca/train.py:54-57).  *lr is read from device memory
  * so ReduceLROnPlateau does not invalidate a captured graph.  clip <= 0 disables clipping.
+ * When at least one of loss, hist, acc, cursor is given, the same launch goes on with what dcahip_step_end does with
+ * them (loss slot -> history / epoch accumulator, batch cursor += advance): one launch less per step, which is what the
+ * reference-default batch of 32 is made of.  All four NULL: the update alone.
  */
 int dcahip_rmsprop_clip(float* w, const float* g, float* ms, long n, const float* lr,
-                        float rho, float eps, float clip, void* stream);
-/* The same launch followed by what dcahip_step_end does (loss slot -> history / epoch accumulator, batch cursor
- * += advance): one launch less per step, which is what the reference-default batch of 32 is made of. */
-int dcahip_rmsprop_clip_end(float* w, const float* g, float* ms, long n, const float* lr,
-                            float rho, float eps, float clip, const float* loss, double weight,
-                            float* hist, int rows_per_slot, double* acc, long long* cursor, int advance,
-                            void* stream);
+                        float rho, float eps, float clip, const float* loss, double weight,
+                        float* hist, int rows_per_slot, double* acc, long long* cursor, int advance,
+                        void* stream);
 
 /*
  * K-OPT: the other Keras optimizers selectable through dca/train.py:54-57 and the l1 / l2 kernel
@@ -754,30 +736,11 @@ int dcahip_dropout_apply(const float* x, long ldx, const int* perm, const long l
  * reaches 255).  dcahip_counts_compact writes Yc from the fp32 counts and ADDS to status[0] the number of values that
  * are not counts (negative, fractional, not finite: stored as 0 -- the caller must not use the compact store then)
  * and to status[1] the number of escapes (the caller builds the overflow list from Y >= 255).
- * K-HEADS takes the same store through dcahip_heads_fused_compact.
+ * K-HEADS takes the same store through the `yc` arguments of dcahip_heads_fused (its contract is stated there).
  */
 long dcahip_counts_compact_ld(int G);
 int dcahip_counts_compact(const float* Y, long ldy, int n, int G, unsigned char* Yc, long ldc, int* status,
                           void* stream);
-/* K-HEADS (dcahip_heads_fused_loss) reading the counts from the compact store: yc != NULL selects it (y / ldy are then
- * unused and may be NULL / 0), yc == NULL is dcahip_heads_fused_loss.  4 x fewer count bytes per launch.
- * d_exp (in [-24, 0]; 0 is what the other entry points pass): the kernel carries the gradient planes as g 2^(8 + d_exp)
- * (kDExp0 = 8) in two fp16 pieces, g = the UNSCALED d nll / d pre-activation, |g| <= max(theta, ~2 y): |g| <= 117 fits at
- * d_exp = 0.  A 32 x 32 tile with a larger value repeats at the exponent its maximum needs (a slow path, exact, but the whole
- * tile is then carried at that exponent: 2^-(kDe + 25) absolute on every g of it); a caller whose counts reach c throughout
- * passes d_exp = -ceil(log2(2 c / 117)) (Engine._heads_d_exp) and keeps the tiles on the fast path.
- * ridge must lie in [0, 1e3]. */
-int dcahip_heads_fused_compact(const float* H, long ldh, const float* Wh, long ldw, const float* bh,
-                               long plane, const float* theta_w,
-                               const float* y, long ldy,
-                               const unsigned char* yc, long ldc, const int* ovf_ptr, const int* ovf_col,
-                               const float* ovf_val, const float* sf,
-                               const int* perm, const long long* cursor,
-                               int B, int hL, int G, float ridge, float inv_n, int flags,
-                               float* gW, long ldg, float* g_theta, float* dH, long lddh,
-                               double* loss_partials, int* n_partials_out,
-                               void* workspace, long workspace_bytes, const int* tile_order,
-                               float* loss_out, int d_exp, void* stream);
 /* First-layer widths the kernels below take (32, 64, 128). */
 int dcahip_enc0_sparse_supported(int H1);
 /*

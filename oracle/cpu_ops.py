@@ -122,7 +122,7 @@ class CpuRefOps:
 
     def heads_fused(self, H, ldh, Wh, ldw, bh, plane, theta_w, Y, ldy, sf, perm, cursor, B, hL, G,
                     ridge, inv_n, flags, gW, ldg, g_theta, dH, lddh, partials, ws, tile_order=None, loss_out=None):
-        """Contract of dcahip_heads_fused_loss = the composition of the separate entry points (tile_order only
+        """Contract of dcahip_heads_fused = the composition of the separate entry points (tile_order only
         changes which workgroup computes what; loss_out = dcahip_loss_finalize on the partials)."""
         has_pi, cdisp = bool(flags & 1), bool(flags & 2)
         nh = 1 + (0 if cdisp else 1) + (1 if has_pi else 0)
@@ -434,6 +434,6 @@ class CpuRefOps:
         wv[:] = wv - float(lr[0].item()) * gv / (np.sqrt(m) + eps)
 
     def rmsprop_clip_end(self, w, g, ms, n, lr, rho, eps, clip, loss, weight, hist, rows_per_slot, acc, cursor, advance):
-        """Contract of dcahip_rmsprop_clip_end: rmsprop_clip, then step_end on the same words."""
+        """Contract of dcahip_rmsprop_clip with its step-end arguments: rmsprop_clip, then step_end on the same words."""
         self.rmsprop_clip(w, g, ms, n, lr, rho, eps, clip)
         self.step_end(loss, weight, hist, rows_per_slot, acc, cursor, advance)

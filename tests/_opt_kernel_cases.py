@@ -292,7 +292,7 @@ def counter_add_cases(ops):
 
 # ------------------------------------------------------------------ B2
 def rmsprop_stride(ops):
-    """dcahip_rmsprop_clip at stride scale against fp64 with the update-relative bound, and dcahip_rmsprop_clip_end:
+    """dcahip_rmsprop_clip at stride scale against fp64 with the update-relative bound, and the same entry with its step-end arguments:
     w, ms bit-identical to it, the bookkeeping bit-identical to dcahip_step_end on the same words, two calls running."""
     n = N_RMS
     w0, g0, ms0 = rms_inputs(n)

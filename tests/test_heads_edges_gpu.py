@@ -194,6 +194,6 @@ def test_heads_row_scale_spread(ops, B, G, spread):
 
 @pytest.mark.parametrize('d_exp,ridge', [(1, 0.0), (-25, 0.0), (0, -1.0), (0, 2e3), (0, float('nan'))])
 def test_heads_fused_rejects_d_exp_and_ridge_out_of_range(ops, d_exp, ridge):
-    """dcahip_heads_fused_compact: d_exp in [-24, 0], ridge in [0, 1e3] (EINVAL otherwise: nothing is launched)."""
+    """dcahip_heads_fused: d_exp in [-24, 0], ridge in [0, 1e3] (EINVAL otherwise: nothing is launched)."""
     with pytest.raises(RuntimeError, match='heads_fused'):
         run_case(ops, 1, 192, 40, 64, seed=1, ridge=ridge, d_exp=d_exp)

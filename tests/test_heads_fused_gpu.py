@@ -59,7 +59,7 @@ def reference(Hm, W, b, tw, y, sf, flags, ridge, n_total, threads=1):
 
 def run_case(ops, flags, B, G, hL, seed, ridge=0.0, use_perm=True, odd_counts=False, tile_order=None, counts=None,
              threads=1, d_exp=0, hscale=None, compact=False):
-    """d_exp: the kernel's starting gradient exponent (dcahip_heads_fused_compact); hscale: a factor per 32-row tile of H;
+    """d_exp: the kernel's starting gradient exponent (dcahip_heads_fused); hscale: a factor per 32-row tile of H;
     compact: the counts from the byte store (dca_amd.compact, escapes >= 255 through the overflow list).  out['_ref'] keeps
     what the scale-rule checks of tests/test_heads_edges_gpu.py need: H, the gradient planes of the products, the weights."""
     has_pi, cdisp = bool(flags & 1), bool(flags & 2)
@@ -251,7 +251,7 @@ def test_heads_fused_ragged_shapes(ops):
 
 @pytest.mark.parametrize('flags,B,G', [(1, 200, 777), (3, 96, 333), (0, 260, 1000), (1, 2048, 16500)])     # (the last: a tail launch)
 def test_heads_fused_tile_order_changes_nothing(ops, flags, B, G):
-    """dcahip_heads_fused_ordered: any order of the 32-gene tiles gives the results of the identity order -- bitwise
+    """dcahip_heads_fused with a tile_order: any order of the 32-gene tiles gives the results of the identity order -- bitwise
     for the weight / bias / dispersion gradients (each is per gene tile) unless the launch's plan has a tail launch (the
     last case: see below); the input gradient dH and the loss are sums over gene tiles whose association follows the
     order (a workgroup accumulates the tiles it is handed), so they agree to fp32 / fp64 re-association."""

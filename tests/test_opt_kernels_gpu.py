@@ -1,5 +1,5 @@
 """K-OPT (dcahip_optimizer_step, dcahip_nadam_step, dcahip_counter_add, dcahip_l1l2_apply) and the fused step end
-(dcahip_rmsprop_clip, dcahip_rmsprop_clip_end), each kernel on its own against the fp64 oracle at the sizes where the
+(dcahip_rmsprop_clip without and with its step-end arguments), each kernel on its own against the fp64 oracle at the sizes where the
 grid-stride loops run: the cases of tests/_opt_kernel_cases.py on HipOps, and the entry points' argument checks."""
 import ctypes
 
@@ -83,8 +83,8 @@ def test_argument_checks(ops):
 
     def rms(fn, w_=w, g_=g, ms_=s1, n_=n):
         if fn == 'plain':
-            return L.dcahip_rmsprop_clip(p(w_), p(g_), p(ms_), n_, p(lr), 0.9, 1e-7, 5.0, s)
-        return L.dcahip_rmsprop_clip_end(p(w_), p(g_), p(ms_), n_, p(lr), 0.9, 1e-7, 5.0, None, 0.0, None, 0, None, None, 0, s)
+            return L.dcahip_rmsprop_clip(p(w_), p(g_), p(ms_), n_, p(lr), 0.9, 1e-7, 5.0, None, 0.0, None, 0, None, None, 0, s)
+        return L.dcahip_rmsprop_clip(p(w_), p(g_), p(ms_), n_, p(lr), 0.9, 1e-7, 5.0, p(msch), 1.0, None, 0, None, p(it), 0, s)   # a loss word, the cursor + 0
     for fn in ('plain', 'end'):
         assert rms(fn) == 0
         assert rms(fn, w_=w[1:]) == EINVAL and rms(fn, g_=g[2:]) == EINVAL and rms(fn, ms_=s1[3:]) == EINVAL   # 4, 8, 12 bytes off
