@@ -1,6 +1,6 @@
 """Command line of the reference (``dca input outputdir [flags]``, dca/__main__.py:18-154) on the
 MI355X path: same positionals, flag names, defaults and output files.  The option table below
-restates the reference's flag set; ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
+restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
 dca/hyper.py with hyperopt's TPE restated in dca_amd/tpe.py); ``--tensorboard`` is accepted for
 command-line compatibility and ignored.
 """
@@ -44,6 +44,9 @@ _OPTIONS = [
     (('--hyper',), dict(dest='hyper', action='store_true')),
     (('--hypern',), dict(dest='hypern', type=int, default=1000)),
     (('--hyperepoch',), dict(dest='hyperepoch', type=int, default=100)),
+    (('--hypermcv',), dict(dest='hypermcv', type=float, default=None, metavar='FRACTION',
+                           help='with --hyper: rank the trials by molecular cross-validation -- fit on a binomial FRACTION of '
+                                'every count, minimise the likelihood of the held-out molecules -- instead of val_loss')),
     (('--debug',), dict(dest='debug', action='store_true')),
     (('--tensorboard',), dict(dest='tensorboard', action='store_true')),
     (('--checkcounts',), dict(dest='checkcounts', action='store_true')),
@@ -52,6 +55,10 @@ _OPTIONS = [
     (('--score',), dict(dest='score', action='store_true',
                         help='after the result files: the fitted model\'s mean negative log-likelihood per cell (cell_nll.tsv, train and '
                              'test cells alike) and per gene (gene_nll.tsv), computed on the GPU')),
+    (('--mcv',), dict(dest='mcv', type=float, default=None, metavar='FRACTION',
+                      help='molecular cross-validation instead of the denoising run: thin every count binomially, fit on FRACTION '
+                           'of the molecules with the network and training flags given, score the held-out rest of every cell; '
+                           'writes mcv.json, gene_mcv_nll.tsv and cell_mcv_nll.tsv')),
 ]
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,

@@ -3,6 +3,7 @@
 // the single-process run (include/dcahip.h).  One thread per group of 4 columns = one Philox block.
 #include <hip/hip_runtime.h>
 #include "dcahip.h"
+#include "philox.hpp"
 
 namespace {
 
@@ -17,22 +18,6 @@ struct DropArgs {
     long row0;
     float* out; long ldo;
 };
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                               unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const unsigned lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 
 __global__ __launch_bounds__(256) void dropout_kernel(DropArgs p) {
     const long total = (long)p.B * p.hq;

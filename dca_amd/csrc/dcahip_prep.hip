@@ -16,6 +16,8 @@
 //                     are written here)
 //   CSR compress /    dense rows -> CSR, and the resident CSR without some rows / columns: the counts-resident form is
 //   subset            built and filtered here, not on the host
+//   CSR thin          K-SPLIT: every count of the resident CSR thinned binomially into two parts (molecular cross-validation),
+//                     drawn with the counter-based generator of K-DROP: beyond the reference
 // Arithmetic follows the host restatement operation by operation (fp32 division, fp32 log1p,
 // fp32 square accumulated in fp64) so that host and device inputs agree to the last ulp of
 // log1p.
@@ -24,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "dcahip.h"
+#include "philox.hpp"
 
 namespace {
 
@@ -846,6 +849,128 @@ __global__ __launch_bounds__(256) void csr_subset_kernel(SubsetArgs a) {
     if (bad) atomicAdd(a.status, bad);
 }
 
+// ---- K-SPLIT: binomial thinning of the resident CSR into two parts (dcahip_csr_thin) -------------------------------------
+// Molecule t of the count y of (cell i, gene j) goes to part A when word t & 3 of the Philox block with counter
+// (i, j, t >> 2, kPhiloxThinTag) and key = seed is below the threshold (compared in 64 bits: 2^32 keeps every molecule);
+// a = the number of such molecules, part A gets a, part B y - a.  a is a function of (seed, i, j, y, threshold) alone.
+struct ThinArgs {
+    const long* indptr; const int* indices; const float* values; long nnz; int n, G;
+    const long* row_ids;
+    unsigned long long threshold; unsigned k0, k1;
+    long* ptr_a; int* idx_a; float* val_a;
+    long* ptr_b; int* idx_b; float* val_b; long cap;
+    int* drawn;                                 // [nnz]: a of every stored entry, -1 for an entry neither part takes
+    int* status;
+};
+
+constexpr unsigned kThinShare = 64;             // counts above it are drawn by the whole wave
+
+// the molecules t of Philox block `blk` (t = 4 blk .. 4 blk + 3, t < y) that go to part A
+__device__ __forceinline__ int thin_block(unsigned i, unsigned j, unsigned blk, unsigned y, unsigned long long thr,
+                                          unsigned k0, unsigned k1) {
+    unsigned o[4];
+    philox4x32_10(i, j, blk, kPhiloxThinTag, k0, k1, o);
+    const unsigned left = y - 4u * blk;         // >= 1
+    int a = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) a += ((unsigned)w < left && (unsigned long long)o[w] < thr) ? 1 : 0;
+    return a;
+}
+
+// the count of a stored value: true and y in [0, 2^24] for a non-negative integer up to 2^24
+__device__ __forceinline__ bool thin_count(float v, unsigned& y) {
+    const bool ok = v >= 0.f && v == floorf(v) && v <= 16777216.f;
+    y = ok ? (unsigned)v : 0u;
+    return ok;
+}
+
+// One wave per source row (both phases).  STORE = false: the draws -- a of every entry into drawn[], the number of entries
+// with a > 0 into ptr_a[r + 1], with y - a > 0 into ptr_b[r + 1]; malformed input is clamped and counted here, once.
+// STORE = true: the entries of both parts at ptr_x[r] ..., in the order of the source row (a ballot per 64 entries gives the
+// ranks), a read back from drawn[]: nothing is drawn twice.
+template <bool STORE>
+__global__ __launch_bounds__(256) void csr_thin_kernel(ThinArgs p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * 256) >> 6;
+    int bad = 0;
+    for (int r = wave; r < p.n; r += nwaves) {
+        const long s = p.indptr[r], e = p.indptr[r + 1];
+        long s0, e0;
+        const bool moved = clamp_span(s, e, p.nnz, s0, e0);
+        if (!STORE && lane == 0 && moved) ++bad;
+        const unsigned cell = (unsigned)(p.row_ids ? p.row_ids[r] : (long)r);
+        long pa = 0, ea = 0, pb = 0, eb = 0;
+        if (STORE) {
+            pa = p.ptr_a[r]; ea = p.ptr_a[r + 1];
+            if (ea > p.cap) ea = p.cap;
+            if (pa < 0) pa = ea;
+            pb = p.ptr_b[r]; eb = p.ptr_b[r + 1];
+            if (eb > p.cap) eb = p.cap;
+            if (pb < 0) pb = eb;
+        }
+        int cnt_a = 0, cnt_b = 0;
+        for (long j0 = s0; j0 < e0; j0 += 64) {
+            const long j = j0 + lane;
+            int c = 0, a = -1;
+            unsigned y = 0;
+            if (j < e0) {
+                c = p.indices[j];
+                const bool okc = c >= 0 && c < p.G;
+                const bool okv = thin_count(p.values[j], y);
+                if (!STORE) bad += (okc ? 0 : 1) + (okv ? 0 : 1);
+                if (!okc) y = 0;
+                if (STORE) a = p.drawn[j];
+            }
+            if (!STORE) {
+                // small counts: the lane walks its own entry's blocks
+                if (y > 0 && y <= kThinShare) {
+                    a = 0;
+                    for (unsigned blk = 0; 4u * blk < y; ++blk) a += thin_block(cell, (unsigned)c, blk, y, p.threshold, p.k0, p.k1);
+                }
+                // large counts: one entry at a time, its blocks dealt round the wave, the 64 partial counts added up
+                unsigned long long big = __ballot(y > kThinShare);
+                while (big) {
+                    const int src = __ffsll((long long)big) - 1;
+                    big &= big - 1;
+                    const unsigned ys = (unsigned)__shfl((int)y, src, 64);
+                    const unsigned cs = (unsigned)__shfl(c, src, 64);
+                    const unsigned nblk = (ys + 3u) >> 2;
+                    int part = 0;
+                    for (unsigned blk = (unsigned)lane; blk < nblk; blk += 64u)
+                        part += thin_block(cell, cs, blk, ys, p.threshold, p.k0, p.k1);
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+                    if (lane == src) a = part;
+                }
+                if (j < e0) p.drawn[j] = y > 0 ? a : -1;
+            }
+            const bool in_a = y > 0 && a > 0;
+            const bool in_b = y > 0 && a >= 0 && (unsigned)a < y;
+            const unsigned long long ma = __ballot(in_a), mb = __ballot(in_b);
+            if (STORE) {
+                if (in_a) {
+                    const long q = pa + lane_rank64(ma);
+                    if (q < ea) { p.idx_a[q] = c; p.val_a[q] = (float)a; }
+                    else ++bad;
+                }
+                if (in_b) {
+                    const long q = pb + lane_rank64(mb);
+                    if (q < eb) { p.idx_b[q] = c; p.val_b[q] = (float)(y - (unsigned)a); }
+                    else ++bad;
+                }
+                pa += __popcll(ma);
+                pb += __popcll(mb);
+            } else {
+                cnt_a += __popcll(ma);
+                cnt_b += __popcll(mb);
+            }
+        }
+        if (!STORE && lane == 0) { p.ptr_a[r + 1] = cnt_a; p.ptr_b[r + 1] = cnt_b; }
+    }
+    if (bad) atomicAdd(p.status, bad);
+}
+
 // What the three dcahip_csr_gather* entries require alike of their arguments, and the GatherArgs made of them (Y / ldy: the
 // fp32 count tile, which each entry checks itself).  False: DCAHIP_EINVAL.
 bool gather_args(const long* indptr, const int* indices, const float* values, long nnz, int n, int G, const int* perm,
@@ -910,6 +1035,32 @@ extern "C" int dcahip_csr_subset(const long* indptr, const int* indices, const f
     if (n_out > 0) hipLaunchKernelGGL(csr_subset_kernel<false>, dim3(grid), dim3(256), 0, s, a);
     hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, out_indptr, n_out, 0L);
     if (n_out > 0) hipLaunchKernelGGL(csr_subset_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" long dcahip_csr_thin_workspace_bytes(int n, long nnz) {
+    if (n < 0 || nnz < 0) return DCAHIP_EINVAL;
+    return (nnz * (long)sizeof(int) + 15) & ~15L;
+}
+
+extern "C" int dcahip_csr_thin(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                               const long* row_ids, unsigned long long threshold, unsigned long long seed,
+                               long* indptr_a, int* indices_a, float* values_a,
+                               long* indptr_b, int* indices_b, float* values_b, long cap,
+                               void* workspace, int* status, void* stream) {
+    if (n < 0 || G <= 0 || nnz < 0 || cap < 0 || threshold > (1ULL << 32) || !status) return DCAHIP_EINVAL;
+    if (n == 0) return 0;
+    if (!indptr || !indptr_a || !indptr_b || (nnz > 0 && (!indices || !values || !workspace))) return DCAHIP_EINVAL;
+    if (cap > 0 && (!indices_a || !values_a || !indices_b || !values_b)) return DCAHIP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ThinArgs a{indptr, indices, values, nnz, n, G, row_ids, threshold, (unsigned)seed, (unsigned)(seed >> 32),
+               indptr_a, indices_a, values_a, indptr_b, indices_b, values_b, cap, static_cast<int*>(workspace), status};
+    int grid = (n + 3) / 4;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(csr_thin_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, indptr_a, n, 0L);
+    hipLaunchKernelGGL(rowptr_scan_kernel, dim3(1), dim3(1024), 0, s, indptr_b, n, 0L);
+    hipLaunchKernelGGL(csr_thin_kernel<true>, dim3(grid), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }
 

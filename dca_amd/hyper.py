@@ -13,6 +13,10 @@ diverged loss, say) is recorded as failed and skipped, as fmin(catch_eval_except
 reference writes hyperopt's choice indices and carries a TODO about it, hyper.py:109).  As in the
 reference the input is read with transpose=args.transpose (hyper.py:15-17: NOT the `not args.transpose`
 of the training pipeline, train.py:124-127), i.e. `--hyper` expects cell x gene unless -t is given.
+
+Beyond the reference: `--hypermcv FRACTION` ranks the trials by molecular cross-validation (dca_amd/mcv.py) -- every trial
+is fitted on the same binomial part of the counts (seed 42) and its loss is the likelihood of the held-out molecules --
+instead of the validation loss on counts the encoder has seen; best.json then carries "objective": "mcv".
 """
 import json
 import os
@@ -62,9 +66,21 @@ def sample(rng):
     return to_params(t.random())
 
 
-def evaluate(adata, params, epochs, debug=False, seed=0):
-    """Trains one configuration; returns the best held-out loss and the history."""
+def mcv_parts(adata, fraction):
+    """The molecular cross-validation split of `--hypermcv FRACTION` (dca_amd/mcv.py): made with seed 42, the same for every
+    trial."""
+    from . import mcv as _mcv
+    return _mcv.split_counts(adata, fraction, seed=42)
+
+
+def evaluate(adata, params, epochs, debug=False, seed=0, mcv=None, _parts=None):
+    """Trains one configuration; returns the best held-out loss and the history.  mcv=FRACTION: the configuration is fitted
+    on the fit part of the molecular cross-validation split of the counts and its loss is the likelihood of the held-out
+    molecules of every cell (mcv.mcv's ``mcv_loss``) instead of the best ``val_loss``; _parts: that split, made once by the
+    caller (hyper())."""
     d, m = params['data'], params['model']
+    if mcv is not None:
+        return _evaluate_mcv(adata, params, epochs, debug, seed, mcv, _parts)
     # kopt.CompileFN(valid_split=.2) holds out a RANDOM fifth of the cells (hyper.py:85-95); train() takes the
     # validation rows from the tail (Keras validation_split), so the cells are permuted once -- the same permutation
     # for every trial (seed 42): trials are ranked on the same held-out cells
@@ -86,8 +102,36 @@ def evaluate(adata, params, epochs, debug=False, seed=0):
     return float(np.min(val)), hist.history
 
 
+def _evaluate_mcv(adata, params, epochs, debug, seed, fraction, parts):
+    from . import mcv as _mcv
+    d, m = params['data'], params['model']
+    fit, held = parts if parts is not None else mcv_parts(adata, fraction)
+    order = np.random.RandomState(42).permutation(adata.n_obs)          # as evaluate(): early stopping watches the same cells
+    fit, held = fit[order].copy(), held[order].copy()
+    _mcv.drop_empty(fit, held)
+    fit = io.normalize(fit, filter_min_counts=False, size_factors=d['norm_input_sf'], logtrans_input=d['norm_input_log'],
+                       normalize_input=d['norm_input_zeromean'])
+    net = AE_types[m['aetype']](input_size=fit.n_vars, hidden_size=m['hidden_size'], l2_coef=0.0, l1_coef=0.0,
+                                l2_enc_coef=0.0, l1_enc_coef=m['l1_enc_coef'], ridge=m['ridge'],
+                                hidden_dropout=m['dropout'], input_dropout=m['input_dropout'],
+                                batchnorm=m['batchnorm'], activation=m['activation'], init='glorot_uniform',
+                                debug=debug)
+    net.seed = seed
+    net.build()
+    hist = train(fit, net, optimizer='RMSprop', learning_rate=m['lr'], epochs=epochs, reduce_lr=None,
+                 early_stop=KOPT_PATIENCE, batch_size=32, clip_grad=5.0, validation_split=VALID_SPLIT, verbose=False)
+    ev = _mcv.evaluation_set(fit, held, fraction)
+    net.score(ev)
+    loss = float(ev.uns['dca_nll'])
+    if not np.isfinite(loss):
+        raise FloatingPointError('no finite held-out loss')
+    return loss, hist.history
+
+
 def hyper(args):
     adata = io.read_dataset(args.input, transpose=args.transpose, test_split=False)
+    fraction = getattr(args, 'hypermcv', None)
+    parts = mcv_parts(adata, fraction) if fraction is not None else None
     output_dir = os.path.join(args.outputdir, 'hyperopt_results')
     os.makedirs(output_dir, exist_ok=True)
     search = _tpe.TPE(SPACE, seed=42)
@@ -97,7 +141,8 @@ def hyper(args):
         params = to_params(vals)
         rec = {'tid': t, 'params': params, 'vals': vals, 'status': 'ok'}
         try:
-            rec['loss'], rec['history'] = evaluate(adata, params, int(args.hyperepoch), getattr(args, 'debug', False), seed=t)
+            rec['loss'], rec['history'] = evaluate(adata, params, int(args.hyperepoch), getattr(args, 'debug', False), seed=t,
+                                                   mcv=fraction, _parts=parts)
         except Exception as e:          # fmin(catch_eval_exceptions=True)
             rec['status'], rec['error'] = 'fail', '%s: %s' % (type(e).__name__, e)
         trials.append(rec)
@@ -109,6 +154,8 @@ def hyper(args):
     with open(os.path.join(output_dir, 'trials.pickle'), 'wb') as f:
         pickle.dump(trials, f)
     best_out = {} if best is None else dict(loss=best['loss'], tid=best['tid'], **best['params'])
+    if fraction is not None and best is not None:
+        best_out['objective'] = 'mcv'
     with open(os.path.join(output_dir, 'best.json'), 'wt') as f:
         json.dump(best_out, f, sort_keys=True, indent=4)
     print(best_out)

@@ -487,6 +487,42 @@ class HipOps:
                                            p(col_keep), int(n_out), p(out_indptr), p(out_indices), p(out_values), cap, p(ws),
                                            p(status), hip.stream()), 'csr_subset')
 
+    def csr_thin(self, csr, row_ids, threshold, seed):
+        """K-SPLIT (include/dcahip.h, dcahip_csr_thin): the resident CSR (prep.CsrCounts) thinned binomially into two parts,
+        (A, B) as new CsrCounts with A + B = csr: of every count y, a ~ Binomial(y, threshold / 2^32) molecules go to A and
+        y - a to B, drawn from Philox4x32-10 with key `seed` and the counter (cell, gene, molecule block).  row_ids: int64
+        [n] device tensor of the rows' global cell ids (None: row r is cell r).  The outputs are allocated at csr.nnz and cut
+        to their own size.  A value that is not a count (negative, fractional, above 2^24) or a malformed CSR raises
+        ValueError."""
+        from .prep import CsrCounts
+        p = hip.ptr
+        threshold, seed = int(threshold), int(seed) & 0xffffffffffffffff
+        if not 0 <= threshold <= 1 << 32:
+            raise ValueError('dca_amd: csr_thin: threshold must lie in [0, 2^32] (got %d)' % threshold)
+        dev, n, nnz = csr.device, csr.n, csr.nnz
+        if row_ids is not None:
+            assert row_ids.dtype == torch.int64 and row_ids.numel() >= n
+        parts = [(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.empty(nnz, dtype=torch.int32, device=dev),
+                  torch.empty(nnz, dtype=torch.float32, device=dev)) for _ in range(2)]
+        ws = torch.empty(int(self.L.dcahip_csr_thin_workspace_bytes(n, nnz)), dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        (pa, ia, va), (pb, ib, vb) = parts
+        hip.check(self.L.dcahip_csr_thin(p(csr.indptr), p(csr.indices) if nnz else None, p(csr.values) if nnz else None, nnz,
+                                         n, csr.G, p(row_ids), threshold, seed, p(pa), p(ia) if nnz else None,
+                                         p(va) if nnz else None, p(pb), p(ib) if nnz else None, p(vb) if nnz else None, nnz,
+                                         p(ws) if nnz else None, p(status), hip.stream()), 'csr_thin')
+        ends = torch.stack([pa[n], pb[n]]).cpu()
+        bad = int(status.item())
+        if bad:
+            raise ValueError('dca_amd: csr_thin: %d values are not counts (negative, not an integer or above 2^24), or '
+                             'entries / rows lie outside the matrix' % bad)
+        out = []
+        for (ptr, idx, val), total in zip(parts, ends.tolist()):
+            if total < nnz:
+                idx, val = idx[:total].clone(), val[:total].clone()
+            out.append(CsrCounts(ptr, idx, val, n, csr.G))
+        return out[0], out[1]
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];

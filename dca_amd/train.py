@@ -408,6 +408,8 @@ def train_with_args(args):
     if args.hyper:
         from .hyper import hyper
         return hyper(args)
+    if getattr(args, 'mcv', None) is not None:
+        return mcv_with_args(args, seed)
 
     # the CLI reads gene x cell tables unless --transpose says otherwise
     adata = io.read_dataset(args.input, transpose=not args.transpose, check_counts=args.checkcounts,
@@ -449,6 +451,29 @@ def train_with_args(args):
     net.predict_write(adata, args.outputdir, mode='full', colnames=columns)
     if getattr(args, 'score', False):
         write_scores(net, adata, x_in, subset, args.outputdir)
+
+
+def mcv_with_args(args, seed):
+    """--mcv FRACTION: molecular cross-validation (dca_amd/mcv.py) of the configuration the command line describes, on the
+    input read as the training pipeline reads it; writes mcv.json, gene_mcv_nll.tsv, cell_mcv_nll.tsv, prints the loss and
+    returns it -- no denoising run."""
+    from . import io
+    from . import mcv as _mcv
+    adata = io.read_dataset(args.input, transpose=not args.transpose, check_counts=args.checkcounts, test_split=False)
+    rates = [float(r) for r in args.dropoutrate.split(',')]
+    res = _mcv.mcv(adata, fraction=args.mcv, seed=seed, ae_type=args.type, normalize_per_cell=args.sizefactors,
+                   scale=args.norminput, log1p=args.loginput, hidden_size=[int(w) for w in args.hiddensize.split(',')],
+                   hidden_dropout=rates[0] if len(rates) == 1 else rates, batchnorm=args.batchnorm, activation=args.activation,
+                   init=args.init,
+                   network_kwds=dict(input_dropout=args.inputdropout, ridge=args.ridge, l1_coef=args.l1, l2_coef=args.l2,
+                                     l1_enc_coef=args.l1enc, l2_enc_coef=args.l2enc, debug=args.debug),
+                   epochs=args.epochs, reduce_lr=args.reducelr, early_stop=args.earlystop, batch_size=args.batchsize,
+                   optimizer=args.optimizer, learning_rate=args.learningrate, random_state=seed, threads=args.threads,
+                   training_kwds=dict(clip_grad=args.gradclip), check_counts=False)
+    _mcv.write_mcv(res, args.outputdir)
+    print('dca: mcv: held-out NLL per cell and gene %.6f (fraction %g, %d cells x %d genes)'
+          % (res['mcv_loss'], res['fraction'], res['n_cells'], res['n_genes']))
+    return res['mcv_loss']
 
 
 def write_scores(net, adata, x_in, subset, output_dir):

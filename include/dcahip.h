@@ -647,6 +647,47 @@ int dcahip_csr_row_sums(const long* indptr, const int* indices, const float* val
                         float* out, int* status, void* stream);
 
 /*
+ * K-SPLIT: binomial thinning of a resident CSR of counts into two independent parts -- molecular cross-validation (Batson
+ * et al. 2019) / count splitting (Neufeld et al. 2022): fit on part A, evaluate the likelihood of part B's molecules with the
+ * size factors scaled by (1 - f) / f.  Beyond the reference, which scores a model only on counts its encoder has seen
+ * (val_loss, dca/train.py:91-98); no reference call site.
+ *
+ * The draw.  A stored entry of cell i, gene j with the integer count y, 1 <= y <= 2^24:
+ *   a(i, j) = #{ t in [0, y) : word (t & 3) of philox4x32_10(counter = (i, j, t >> 2, 0x7468696E), key = (lo32(seed),
+ *               hi32(seed))) < threshold }
+ * compared in 64 bits: threshold = 2^32 keeps every molecule, 0 keeps none; a fraction f is threshold = int(f 2^32), and a is
+ * Binomial(y, threshold / 2^32) exactly, in integer arithmetic.  Part A receives a, part B y - a.  i = row_ids[r] (row_ids
+ * NULL: r), its low 32 bits; j = the entry's column.  Counter word 3 is a constant no K-DROP counter holds there
+ * (dcahip_dropout_apply puts its layer code, 0 .. 255, in that word), so the two streams of one seed never meet.  a depends
+ * on (seed, i, j, y, threshold) only: not on the launch shape, the order of the rows or how an entry's molecules are shared
+ * between lanes (a count above 64 is drawn by the whole wave, its Philox blocks dealt round the lanes and the partial counts
+ * added; smaller ones by one lane) -- dca_amd/mcv.py thin_counts_host restates it in numpy and gives the same bits.
+ *
+ *   indptr / indices / values, nnz, n, G : the resident CSR (as dcahip_csr_gather)
+ *   row_ids [n] int64     : the global cell id of every row (a subset or a permutation of a dataset draws what the whole
+ *                           dataset draws for those cells); NULL: row r is cell r
+ *   indptr_a, indptr_b [n + 1] int64 from 0 (every word written); indices_x / values_x [cap]: each part's entries, rows in
+ *                           order, every row in the column order of the source row, values fp32 integers.  Explicit stored
+ *                           zeros are dropped from both parts, entries with a = 0 from A, with y - a = 0 from B.
+ *                           cap >= nnz always suffices; what does not fit is counted into *status.
+ *   workspace             : >= dcahip_csr_thin_workspace_bytes(n, nnz) bytes (a per stored entry: the draws are made once,
+ *                           in the count phase, and read back by the store phase); needs no initialisation
+ *   status                : one int32, zeroed by the caller: += malformed row pointers and columns (clamped / skipped as in
+ *                           the entries above) and every value that is negative, not an integer or above 2^24 (such an
+ *                           entry goes to neither part) -- the result is not to be used then
+ * Four launches on the stream (draw + count per row, one prefix sum per part, the stores); one plain store per entry, no
+ * atomics except the status counter: two calls give the same bits.  Nothing outside the buffers is read or written.
+ * DCAHIP_EINVAL (nothing launched): n < 0, G <= 0, nnz < 0, cap < 0, threshold > 2^32, a missing pointer.  n = 0 launches
+ * nothing and returns 0; nnz = 0 writes two zero row pointers.
+ */
+long dcahip_csr_thin_workspace_bytes(int n, long nnz);
+int dcahip_csr_thin(const long* indptr, const int* indices, const float* values, long nnz, int n, int G,
+                    const long* row_ids, unsigned long long threshold, unsigned long long seed,
+                    long* indptr_a, int* indices_a, float* values_a,
+                    long* indptr_b, int* indices_b, float* values_b, long cap,
+                    void* workspace, int* status, void* stream);
+
+/*
  * Keras clipvalue + Keras RMSprop (momentum 0) on one flat parameter buffer:
  *   g = clip(g, -clip, clip); ms = rho*ms + (1-rho)*g*g; w -= lr * g / (sqrt(ms) + eps)
  * (epsilon OUTSIDE the root: standalone keras 2.2 / 2.3 `p - lr * g / (K.sqrt(new_a) + self.epsilon)` and tf.keras
