@@ -299,6 +299,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(BnApplyArgs a) {
     __syncthreads();
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int r0 = blockIdx.x * kApplyRows, r1 = min(a.B, r0 + kApplyRows);
+    if (r1 <= r0) return;                        // B == 0 (statistics only): the clamped loads below would read row -1
     for (int c0 = blockIdx.y * 64; c0 < a.H; c0 += 64 * gridDim.y) {
         const int c = c0 + tx;
         if (c >= a.H) continue;

@@ -147,6 +147,61 @@ def block_ranges(B, rows_per_wg):
     return [(min(B, w * cr), min(B, (w + 1) * cr)) for w in range(nwg)]
 
 
+MAX_CHUNKS = 256              # kMaxChunks of dcahip_layers.hip
+
+
+def chunk_ranges(B, R=None):
+    """Row chunks of col_moments / bn_bwd_sums (n_chunks, chunk_rows): R = ceil(B / 64) chunks, at most MAX_CHUNKS, of
+    ceil(B / R) rows each.  Below the cap this is block_ranges(B, 64); under it the trailing chunks can be empty."""
+    if R is None:
+        R = min(MAX_CHUNKS, max(1, -(-B // 64)))
+    cr = -(-B // R)
+    return [(min(B, r * cr), min(B, (r + 1) * cr)) for r in range(R)]
+
+
+def entries_tolerance(counts, mean, m2):
+    """t_mean, t_M2 (moments_tolerance) of a merge whose INPUTS are the entries (count, mean, M2) themselves, exact as
+    handed in: mean_mag = sum n_e |mean_e| / N, the terms of M2 are M2_e and n_e (mean_e - mean)^2 (the result is rounded
+    to fp32, so every term counts), and an error REL |mean_e| of a difference mean_e - mean moves M2 by
+    2 n_e |mean_e - mean| REL |mean_e|.  Entries with count 0 do not enter."""
+    n, gm, gq = merge_stats(counts, mean, m2)
+    c = np.asarray(counts, np.float64)[:, None]
+    am, d = np.abs(np.asarray(mean, np.float64)), np.abs(np.asarray(mean, np.float64) - gm)
+    t_mean = REL * (c * am).sum(0) / n + ulp32(gm)
+    t_m2 = REL * gq + (2.0 * c * d * REL * am).sum(0)
+    return t_mean, t_m2
+
+
+def moments_tolerance(st, g):
+    """What the statistics of a batch may be off by when an fp32 kernel forms them from (mean, M2) of row chunks:
+    st = range_stats over the chunks, g = range_stats over the one range of all rows.  Everything is a function of the
+    reference; on a column whose mean is far larger than its spread the terms exceed the flat classes (an fp32 mean
+    carries ulp32(mean), however it is added up), elsewhere they are negligible beside them.
+        t_mean = REL * mean_mag + ulp32(mean)
+        t_M2   = sum over chunks (REL * m2_mag + m2_in)  +  sum over chunks 2 count |mean_chunk - mean| REL mean_mag_chunk
+    Returns t_mean [H], t_M2 [H]."""
+    mean = g['mean'][0]
+    t_mean = REL * g['mean_mag'][0] + ulp32(mean)
+    t_m2 = (REL * st['m2_mag'] + st['m2_in']).sum(0)
+    t_m2 = t_m2 + (2.0 * st['count'][:, None] * np.abs(st['mean'] - mean) * REL * st['mean_mag']).sum(0)
+    return t_mean, t_m2
+
+
+def fwd_bounds(o, code, beta, t_mean, t_m2, n, EL, momentum=BN_MOMENTUM):
+    """Bounds of xhat, H, inv_std, mm, mv of fwd_step's result o: the flat classes EL (rtol, atol) plus the first-order
+    effect of t_mean / t_M2 (moments_tolerance) on each."""
+    flat = lambda k, ref: EL[k][1] + EL[k][0] * np.abs(ref)
+    inv = o['inv_std']
+    x = o['xhat'] + (0.0 if beta is None else np.asarray(beta, np.float64))
+    b = {'xhat': flat('xhat', o['xhat']) + inv * t_mean,
+         'H': flat('H', o['H']) + np.abs(act_slope(code, x)) * inv * t_mean,
+         'inv_std': 1e-5 * inv + 0.5 * inv ** 3 * t_m2 / n}
+    if 'mm' in o:
+        b['mm'] = flat('mm', o['mm']) + (1.0 - momentum) * t_mean
+        b['mv'] = flat('mv', o['mv']) + (1.0 - momentum) * t_m2 / n
+    return b
+
+
 def split_ranges(counts):
     r, out = 0, []
     for c in counts:

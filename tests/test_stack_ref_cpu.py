@@ -1,11 +1,14 @@
-"""The fp64 reference of the K-STACK tests (tests/_stack_ref.py) is itself checked here, without a GPU: against the network
-oracle's autodiff, for the equality of a merge over row ranges with the one-range pass, and for the slope-from-output
-forms."""
+"""The fp64 reference of the K-STACK and per-layer kernel tests (tests/_stack_ref.py) is itself checked here, without a GPU:
+against the network oracle's autodiff, for the equality of a merge over row ranges with the one-range pass, for the
+slope-from-output forms, for the chunk partition of the large-batch kernels, and -- with a numpy-fp32 restatement of
+col_moments + bn_relu_apply -- for the bounds that tests/test_layer_kernels_gpu.py holds those kernels to."""
 import numpy as np
 import pytest
 
 import _keras_acts as KA
+import _layer_cases as LC
 import _stack_ref as SR
+from _judge import EL
 from oracle import net_np as N
 
 STACKS = [(64, 32, 64), (48, 20, 7, 33)]
@@ -173,3 +176,111 @@ def test_slope_is_the_derivative_of_the_activation(code):
         np.testing.assert_allclose(SR.act_slope(code, x), KA.grad(code, x), rtol=1e-12, atol=1e-15)
     elif code <= 8:
         np.testing.assert_allclose(SR.act_fwd(code, x), N.act_fwd(code, x), rtol=1e-13, atol=1e-15)
+
+
+# ------------------------------------------------------------------ chunk_ranges and the bounds of the large-batch forward
+@pytest.mark.parametrize('B', [1, 2, 63, 64, 65, 130, 2800, 4096, 16383, 16384])
+def test_chunk_ranges_equals_block_ranges_below_the_cap(B):
+    assert SR.chunk_ranges(B) == SR.block_ranges(B, 64) == SR.chunk_ranges(B, len(SR.block_ranges(B, 64)))
+
+
+def test_chunk_ranges_under_the_cap():
+    """n_chunks / chunk_rows of dcahip_layers.hip at B = 16450: 256 chunks of 65 rows, chunk 253 holds 5, the last two none."""
+    r = SR.chunk_ranges(16450)
+    assert len(r) == 256 == SR.MAX_CHUNKS and all(b - a == 65 for a, b in r[:253])
+    assert r[253] == (16445, 16450) and r[254] == r[255] == (16450, 16450)
+    assert sum(b - a for a, b in r) == 16450
+    assert len(SR.block_ranges(16450, 64)) == 258          # what the chunks would be without the cap
+
+
+F = np.float32
+
+
+def _lane_sums(x):
+    """Column sums of fp32 x [rows, H] the way a workgroup forms them: 4 interleaved row lanes, each adding its rows one
+    after the other in fp32, the lanes added pairwise."""
+    l = [x[t::4].cumsum(0, dtype=F)[-1] if len(x[t::4]) else np.zeros(x.shape[1], F) for t in range(4)]
+    return (l[0] + l[1]) + (l[2] + l[3])
+
+
+def emu_col_moments(Z, ranges):
+    """numpy-fp32 restatement of col_moments_kernel: two passes, part[r] = (mean, M2) of chunk r."""
+    part = np.zeros((len(ranges), 2, Z.shape[1]), F)
+    for r, (a, b) in enumerate(ranges):
+        if b > a:
+            mean = _lane_sums(Z[a:b]) / F(b - a)
+            d = Z[a:b] - mean
+            part[r, 0], part[r, 1] = mean, _lane_sums(d * d)
+    return part
+
+
+def emu_bn_apply(Z, counts, part, beta, mm, mv, code, mom=F(SR.BN_MOMENTUM), eps=F(SR.BN_EPS)):
+    """numpy restatement of bn_relu_apply_kernel: merge of the entries in fp64 (two passes), everything else in fp32."""
+    c = np.asarray(counts, np.float64)[:, None]
+    n = c.sum()
+    m64 = (c * part[:, 0].astype(np.float64)).sum(0) / n
+    q64 = (np.where(c > 0, part[:, 1].astype(np.float64) + c * np.square(part[:, 0].astype(np.float64) - m64), 0.0)).sum(0)
+    mean, var = m64.astype(F), (q64 / n).astype(F)
+    inv = F(1) / np.sqrt(var + eps)
+    xh = (Z - mean) * inv
+    x = xh + beta
+    H = {0: lambda: x, 1: lambda: np.maximum(x, F(0)), 2: lambda: np.tanh(x)}[code]()
+    one = F(1) - mom
+    assert all(a.dtype == F for a in (mean, var, inv, xh, H))
+    return dict(xhat=xh, H=H, inv_std=inv, mm=mm - (mm - mean) * one, mv=mv - (mv - var) * one)
+
+
+def _ratio(err, bnd):
+    return float((np.abs(err) / (bnd + 1e-30)).max())
+
+
+def _judge_emulation(p, code):
+    """Worst error / bound of the emulation: per chunk; against fwd_step on the entries it wrote; against the statistics
+    of Z itself.  Returns the ratios and, per column, the errors of xhat / inv_std against the flat classes."""
+    B, H = p['B'], p['H']
+    Z64 = p['Z'].astype(np.float64)
+    ranges = SR.chunk_ranges(B)
+    cnt = [b - a for a, b in ranges]
+    part = emu_col_moments(p['Z'], ranges)
+    st, g = SR.range_stats(Z64, ranges), SR.range_stats(Z64, [(0, B)])
+    out = {'chunk mean': _ratio(part[:, 0] - st['mean'], SR.REL * st['mean_mag']),
+           'chunk M2': _ratio(part[:, 1] - st['m2'], SR.REL * st['m2_mag'] + st['m2_in'])}
+    t_mean, t_m2 = SR.moments_tolerance(st, g)
+    e = emu_bn_apply(p['Z'], cnt, part, p['beta'], p['mm0'], p['mv0'], code)
+    flat = {}
+    for tag, ent in (('forced', (cnt, part[:, 0], part[:, 1])), ('end to end', ([B], g['mean'], g['m2']))):
+        o = SR.fwd_step(1, Z64, ent[0], ent[1], ent[2], p['beta'].astype(np.float64), None, None, p['mm0'].astype(np.float64),
+                        p['mv0'].astype(np.float64), code)
+        LC.fwd_conditions(code, o['xhat'] + p['beta'], o['inv_std'] * t_mean)
+        bnd = SR.fwd_bounds(o, code, p['beta'], t_mean, t_m2, B, EL)
+        for k in ('xhat', 'H', 'inv_std', 'mm', 'mv'):
+            out['%s %s' % (tag, k)] = _ratio(e[k] - o[k], bnd[k])
+        flat[tag] = (np.abs(e['xhat'] - o['xhat']) / (EL['xhat'][1] + EL['xhat'][0] * np.abs(o['xhat'])),
+                     np.abs(e['inv_std'] - o['inv_std']) / (1e-5 * o['inv_std']))
+    return out, flat
+
+
+@pytest.mark.parametrize('code', [0, 1, 2])
+@pytest.mark.parametrize('B,H', LC.LARGE_SHAPES)
+def test_fp32_restatement_meets_the_large_batch_forward_bounds(B, H, code):
+    out, _ = _judge_emulation(LC.large_fwd_problem(B, H), code)
+    print('\nemulation %d x %d code %d: ' % (B, H, code) + '  '.join('%s %.3g' % kv for kv in sorted(out.items())))
+    assert max(out.values()) <= 1.0, out
+
+
+@pytest.mark.parametrize('code', [0, 1])
+@pytest.mark.parametrize('B,H', LC.COND_SHAPES)
+def test_conditioned_columns_need_the_reference_terms(B, H, code):
+    """With the conditioned columns the restatement stays inside the bounds that carry t_mean / t_M2, and on the
+    (3000, 0.3) column it MISSES the flat classes: xhat by the rounding of an fp32 mean of 3000 (ulp 2.4e-4) times
+    inv_std = 3.3, inv_std -- against the statistics of Z itself -- by the chunk means' errors entering the merge (with the
+    two chunks of 65 rows; over the 44 chunks of 2800 rows these errors average out to just under the flat class, so there
+    the figure is only printed)."""
+    out, flat = _judge_emulation(LC.large_fwd_problem(B, H, conditioned=True), code)
+    print('\nemulation %d x %d code %d conditioned: ' % (B, H, code) + '  '.join('%s %.3g' % kv for kv in sorted(out.items())))
+    assert max(out.values()) <= 1.0, out
+    c = LC.COND_COLS[H][LC.WORST_COL]
+    xh, inv = flat['end to end']
+    print('(3000, 0.3) column against the flat classes: xhat %.3g  inv_std %.3g' % (xh[:, c].max(), inv[c]))
+    assert xh[:, c].max() > 1.0 and flat['forced'][0][:, c].max() > 1.0
+    assert B != 65 or inv[c] > 1.0
