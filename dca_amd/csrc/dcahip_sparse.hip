@@ -1141,7 +1141,11 @@ __global__ __launch_bounds__(256) void enc0_fwd_reduce_kernel(const float* P, lo
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)B * hq) return;
     const int r = (int)(idx / hq), j = (int)(idx - (long)r * hq) * 4;
-    float4 v = beff ? *reinterpret_cast<const float4*>(beff + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (beff) {                                           // (a bias that is not 16-byte aligned: scalar loads, as the finish kernel stores)
+        if ((reinterpret_cast<uintptr_t>(beff) & 15) == 0) v = *reinterpret_cast<const float4*>(beff + j);
+        else v = make_float4(beff[j], beff[j + 1], beff[j + 2], beff[j + 3]);
+    }
     for (int k0 = 0; k0 < nsk; k0 += 8) {                 // batches of 8 independent loads (one round trip each), added in chunk order
         float4 t[8];
 #pragma unroll

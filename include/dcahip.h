@@ -820,6 +820,8 @@ int dcahip_enc0_dw_sparse(const unsigned char* Yc, long ldc, const int* ovf_ptr,
  * table, larger ones and escapes by the formula), W / std is split into bf16 pieces once per call, six bf16 products per
  * fp32 product as dcahip_sgemm, gene chunks added in a fixed order: deterministic.  workspace >=
  * dcahip_enc0_fwd_lut_workspace_bytes(B, G, H1), 16-byte aligned, any content; n_cells * ldc must stay below 2^32 (lutp).
+ * Alignment: Z 16 bytes and ldz a multiple of 4 (else DCAHIP_EINVAL); W, mean, stdv and bias need only that of a float
+ * (bias NULL: none; a bias that is not 16-byte aligned is read with scalar loads, same values).
  * Replaces Dense(hidden_size[0]) of dca/network.py:124-126 on the input of dca/io.py:88-111.
  */
 long dcahip_enc0_fwd_lut_workspace_bytes(int B, int G, int H1);
