@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include "dcahip.h"
 #include "h2_math.hpp"
 
@@ -798,12 +799,14 @@ __global__ __launch_bounds__(256) void gemm_p3_kernel(Gemm3Args p) {
 // Order of events in step k (stage k % 3):  wait vmcnt(6) [own requests of step k have landed; step k + 1's 6 stay in
 // flight] -> barrier [everybody's have; everybody has read step k - 1] -> request step k + 2 into the stage step k - 1
 // used -> fragments of step k -> MFMAs.
+// The image, the arithmetic and the K loop are written ONCE, for NP pieces per operand: three bf16 pieces and six products
+// (gemm_p3w_kernel), two fp16 pieces and three products (gemm_h2w_kernel and its four-wave form gemm_h2m_kernel, below).
 constexpr int kWBK = 16;
-template <bool KC>
+template <int NP, bool KC, int NCH = 8>                    // NCH: 1 KB chunks per plane (8: 256 rows / columns; 4: 128, k-contiguous only)
 struct WideImage {
     static constexpr int CHUNK = KC ? 1024 : 1088;         // bytes between the LDS destinations of consecutive waves
-    static constexpr int PLANE = 8 * CHUNK;
-    static constexpr int BYTES = 3 * PLANE;
+    static constexpr int PLANE = NCH * CHUNK;
+    static constexpr int BYTES = NP * PLANE;
     // Fragment reads are ISSUED here (inline asm: the compiler neither reorders them nor guards them with a vmcnt(0)
     // against the LDS-DMA requests in flight) and RETIRED by the caller with a counted s_waitcnt lgkmcnt.
     // lane_off: this lane's byte offset inside a plane for row / column tile 0 of the wave
@@ -826,6 +829,12 @@ struct WideImage {
             f = u32x4{lo[0], lo[1], hi[0], hi[1]};
         }
     }
+    // the NP pieces of tile TILE
+    template <int TILE>
+    static __device__ __forceinline__ void issue_tile(u32x4 (&f)[NP], unsigned addr) {
+        issue<0, TILE>(f[0], addr); issue<1, TILE>(f[1], addr);
+        if constexpr (NP == 3) issue<2, TILE>(f[2], addr);
+    }
     // this thread's source element offset inside a plane at k = 0 (add k for KC, k * ld for MN)
     static __device__ __forceinline__ long src_off(int t, long ld, int idx0, int nidx) {
         if (KC) {
@@ -842,10 +851,130 @@ struct WideImage {
     }
 };
 
-template <bool A_KC, bool B_KC, bool CS>
-__global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
-    using IA = WideImage<A_KC>;
-    using IB = WideImage<B_KC>;
+// one LDS-DMA request: this lane's 16 bytes at g to the wave's chunk at dst (lane-linear)
+__device__ __forceinline__ void request16(const unsigned short* g, unsigned char* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+// the arithmetic of NP pieces per operand: the products (piece PA[pr] of A with piece PB[pr] of B, small terms first), the
+// matrix instruction, and one word (two elements) of a B fragment added to a column sum
+template <int NP> struct PlaneMath;
+template <> struct PlaneMath<3> {
+    static constexpr int NPROD = 6;
+    static constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+    static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return MFMA16(a, b, c); }
+    static __device__ __forceinline__ float colsum(float x, unsigned w) { return x + (bf16_lo(w) + bf16_hi(w)); }
+};
+template <> struct PlaneMath<2> {
+    static constexpr int NPROD = 3;
+    static constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
+    static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h2_f16x8, a), __builtin_bit_cast(h2_f16x8, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ float colsum(float x, unsigned w) {
+        return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_f16x2, w), h2_f16x2{(_Float16)1.f, (_Float16)1.f}, x, false);
+    }
+};
+
+// s_waitcnt lgkmcnt(N): at most N of the LDS instructions issued so far still in flight (they return in order).  Every
+// fragment register is tied to the statement, so no product that reads one moves in front of it.
+template <int N, int NP>
+__device__ __forceinline__ void wait_lgkm(u32x4 (&a)[2][NP], u32x4 (&b)[2][NP]) {
+    if constexpr (NP == 3)
+        asm volatile("s_waitcnt lgkmcnt(%12)" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]),
+                                                "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[0][2]), "+v"(b[1][0]), "+v"(b[1][1]), "+v"(b[1][2]) : "n"(N));
+    else
+        asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]),
+                                               "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[1][0]), "+v"(b[1][1]) : "n"(N));
+}
+
+// one product group: a row tile's pieces with both column tiles', round-robin over the two accumulators
+template <int NP>
+__device__ __forceinline__ void products(f32x16 (&acc)[2], const u32x4 (&a)[NP], const u32x4 (&b)[2][NP]) {
+    using MATH = PlaneMath<NP>;
+#pragma unroll
+    for (int pr = 0; pr < MATH::NPROD; ++pr)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[j] = MATH::mfma(a[MATH::PA[pr]], b[j][MATH::PB[pr]], acc[j]);
+}
+
+// Step k of a wave's K loop: 128 x 64 of the output (4 row tiles x 2 column tiles) from stage `cur` of the ring, which moves on
+// (cur: stage of step k, nxt: the stage step k + 2 goes to; they start at 0 and 2).  request(stage) issues this thread's REQS
+// LDS-DMA requests of the next step to request; aoff / boff: the lane's fragment offsets inside a stage (B behind A).
+// CS: column sums of the B fragments (m/n-contiguous B only) into csum where do_colsum.
+template <int NP, class IA, class IB, int REQS, bool CS, class Request>
+__device__ __forceinline__ void wide_step(f32x16 (&acc)[4][2], int k, int nsteps, int& cur, int& nxt, unsigned aoff, unsigned boff,
+                                          bool do_colsum, float (&csum)[2], Request&& request) {
+    constexpr int STAGE = IA::BYTES + IB::BYTES, ROW = IA::READS * NP;     // ROW: LDS instructions of one row tile of A
+    if (k + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(REQS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const unsigned sa_ = (unsigned)(cur * STAGE) + aoff, sb_ = (unsigned)(cur * STAGE + IA::BYTES) + boff;
+    const int rq = nxt;
+    cur = cur == 2 ? 0 : cur + 1; nxt = nxt == 2 ? 0 : nxt + 1;
+    // fragments: B (2 column tiles x NP pieces), then A row tile by row tile, each requested one tile ahead of its
+    // products; waits are counted in LDS instructions still allowed in flight
+    u32x4 b[2][NP], a[2][NP];
+    IB::template issue_tile<0>(b[0], sb_); IB::template issue_tile<1>(b[1], sb_);
+    IA::template issue_tile<0>(a[0], sa_);
+    IA::template issue_tile<1>(a[1], sa_);
+    wait_lgkm<ROW>(a, b);
+    if constexpr (CS) {
+        if (do_colsum) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < NP; ++q)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) csum[j] = PlaneMath<NP>::colsum(csum[j], b[j][q][w]);
+        }
+    }
+    products<NP>(acc[0], a[0], b);
+    // the next-but-one step's requests go out BEHIND the first products: their issue (an M0 write and an address per
+    // piece) fills the gaps of the matrix pipe instead of standing between the barrier and the first product
+    if (k + 2 < nsteps) request(rq);
+    IA::template issue_tile<2>(a[0], sa_);
+    wait_lgkm<ROW>(a, b);
+    products<NP>(acc[1], a[1], b);
+    IA::template issue_tile<3>(a[1], sa_);
+    wait_lgkm<ROW>(a, b);
+    products<NP>(acc[2], a[0], b);
+    wait_lgkm<0>(a, b);
+    products<NP>(acc[3], a[1], b);
+}
+
+__device__ __forceinline__ void zero(f32x16 (&acc)[4][2]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// the wave's accumulators of column tile j (column n, bias value bv) to out; two pieces: scaled by un on the way
+template <int NP>
+__device__ __forceinline__ void store_column_tile(const f32x16 (&acc)[4][2], int j, float* out, long ldo, int mrow0, int n,
+                                                  int M, int N, float bv, float un) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = mrow0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * ((threadIdx.x & 63) >> 5);
+            if (m < M && n < N) {
+                if constexpr (NP == 2) out[(long)m * ldo + n] = fmaf(acc[i][j][r], un, bv);
+                else out[(long)m * ldo + n] = acc[i][j][r] + bv;
+            }
+        }
+    }
+}
+
+// the 256 x 256 kernel: eight waves (2 x 4), every thread requests one 16-byte unit per piece and operand (2 NP per step)
+template <int NP, bool A_KC, bool B_KC, bool CS, class Args>
+__device__ __forceinline__ void gemm_wide_body(Args p) {
+    using IA = WideImage<NP, A_KC>;
+    using IB = WideImage<NP, B_KC>;
     constexpr int STAGE = IA::BYTES + IB::BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -874,27 +1003,17 @@ __global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
     const unsigned short* gb = p.B + IB::src_off(t, p.ldb, n0, p.N) + (B_KC ? (long)kbeg : (long)kbeg * p.ldb);
     const long sa = A_KC ? (long)kWBK : (long)kWBK * p.lda, sb = B_KC ? (long)kWBK : (long)kWBK * p.ldb;
     const int wa = wave * IA::CHUNK, wb = IA::BYTES + wave * IB::CHUNK;
-
     auto request = [&](int stage) __attribute__((always_inline)) {
         unsigned char* st = lds + stage * STAGE;
 #pragma unroll
-        for (int q = 0; q < 3; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga + q * p.pa),
-                                             (__attribute__((address_space(3))) void*)(st + q * IA::PLANE + wa), 16, 0, 0);
+        for (int q = 0; q < NP; ++q) request16(ga + q * p.pa, st + q * IA::PLANE + wa);
 #pragma unroll
-        for (int q = 0; q < 3; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb + q * p.pb),
-                                             (__attribute__((address_space(3))) void*)(st + q * IB::PLANE + wb), 16, 0, 0);
+        for (int q = 0; q < NP; ++q) request16(gb + q * p.pb, st + q * IB::PLANE + wb);
         ga += sa; gb += sb;
     };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero(acc);
     const int wm0 = (wave >> 2) * 128, wn0 = (wave & 3) * 64;
     const unsigned aoff = IA::lane_off(wm0, lane), boff = IB::lane_off(wn0, lane);
     const bool do_colsum = CS && !B_KC && p.colsum && mt == 0 && (wave >> 2) == 0;
@@ -902,56 +1021,17 @@ __global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
 
     if (nsteps > 0) request(0);
     if (nsteps > 1) request(1);
-    int cur = 0, nxt = 2;                                  // stage of step k, stage step k + 2 goes to
+    int cur = 0, nxt = 2;
 #pragma unroll 1
-    for (int k = 0; k < nsteps; ++k) {
-        if (k + 1 < nsteps) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const unsigned sa_ = (unsigned)(cur * STAGE) + aoff, sb_ = (unsigned)(cur * STAGE + IA::BYTES) + boff;
-        const int rq = nxt;
-        cur = cur == 2 ? 0 : cur + 1; nxt = nxt == 2 ? 0 : nxt + 1;
-        // fragments: B (2 column tiles x 3 pieces), then A row tile by row tile, each requested one tile ahead of its
-        // products; waits are counted in LDS instructions still allowed in flight (they return in order)
-        u32x4 b[2][3], a[2][3];
-        IB::template issue<0, 0>(b[0][0], sb_); IB::template issue<1, 0>(b[0][1], sb_); IB::template issue<2, 0>(b[0][2], sb_);
-        IB::template issue<0, 1>(b[1][0], sb_); IB::template issue<1, 1>(b[1][1], sb_); IB::template issue<2, 1>(b[1][2], sb_);
-        IA::template issue<0, 0>(a[0][0], sa_); IA::template issue<1, 0>(a[0][1], sa_); IA::template issue<2, 0>(a[0][2], sa_);
-#define DCA_TIE6(x) "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[0][2]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[1][2])
-#define DCA_WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" : DCA_TIE6(a), DCA_TIE6(b))
-#define DCA_PRODUCTS(I, AI) do { _Pragma("unroll") for (int pr = 0; pr < 6; ++pr) { \
-            constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0}; \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[I][j] = MFMA16(a[AI][PA[pr]], b[j][PB[pr]], acc[I][j]); } } while (0)
-        IA::template issue<0, 1>(a[1][0], sa_); IA::template issue<1, 1>(a[1][1], sa_); IA::template issue<2, 1>(a[1][2], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(3); else DCA_WAIT_LGKM(6);
-        if constexpr (CS && !B_KC) {
-            if (do_colsum) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) csum[j] += bf16_lo(b[j][q][w]) + bf16_hi(b[j][q][w]);
-            }
-        }
-        DCA_PRODUCTS(0, 0);
-        // the next-but-one step's requests go out BEHIND the first products: their issue (an M0 write and an address per
-        // piece) fills the gaps of the matrix pipe instead of standing between the barrier and the first product
-        if (k + 2 < nsteps) request(rq);
-        IA::template issue<0, 2>(a[0][0], sa_); IA::template issue<1, 2>(a[0][1], sa_); IA::template issue<2, 2>(a[0][2], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(3); else DCA_WAIT_LGKM(6);
-        DCA_PRODUCTS(1, 1);
-        IA::template issue<0, 3>(a[1][0], sa_); IA::template issue<1, 3>(a[1][1], sa_); IA::template issue<2, 3>(a[1][2], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(3); else DCA_WAIT_LGKM(6);
-        DCA_PRODUCTS(2, 0);
-        DCA_WAIT_LGKM(0);
-        DCA_PRODUCTS(3, 1);
-#undef DCA_PRODUCTS
-#undef DCA_WAIT_LGKM
-#undef DCA_TIE6
-    }
+    for (int k = 0; k < nsteps; ++k)
+        wide_step<NP, IA, IB, 2 * NP, CS && !B_KC>(acc, k, nsteps, cur, nxt, aoff, boff, do_colsum, csum, request);
 
+    // two pieces: the operands' block scales out again (exact: powers of two) and the caller's factor in
+    float un = 1.f, un_b = 1.f;
+    if constexpr (NP == 2) {
+        const int ea = (p.exp_a ? *p.exp_a : 0) + p.exp_a_add, eb = (p.exp_b ? *p.exp_b : 0) + p.exp_b_add;
+        un = p.alpha * h2_pow2i(-(ea + eb)); un_b = p.alpha * h2_pow2i(-eb);
+    }
     const int Mo = p.M + (p.colsum ? 1 : 0);
     if (tail) {
         // a K slice of a tail tile: the partial tile, tile-local, into the tail workspace
@@ -961,8 +1041,10 @@ __global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    pt[(wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 256 + wn0 + j * 32 + (lane & 31)] = acc[i][j][r];
+                for (int r = 0; r < 16; ++r) {
+                    float* o = pt + (wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 256 + wn0 + j * 32 + (lane & 31);
+                    if constexpr (NP == 2) *o = acc[i][j][r] * un; else *o = acc[i][j][r];
+                }
         return;                                            // (no column sums here: the host keeps m tile 0 out of the tail)
     }
     float* out = p.split > 1 ? p.ws + (long)s * Mo * p.N : p.C;
@@ -972,21 +1054,17 @@ __global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
     for (int j = 0; j < 2; ++j) {
         const int n = n0 + wn0 + j * 32 + (lane & 31);
         const float bv = (add_bias && n < p.N) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < p.M && n < p.N) out[(long)m * ldo + n] = acc[i][j][r] + bv;
-            }
-        }
+        store_column_tile<NP>(acc, j, out, ldo, m0 + wm0, n, p.M, p.N, bv, un);
         if (CS && do_colsum) {
             // the lane holds the k rows 8 hi .. + 7 of column n: the other half's share through a lane exchange
             const float tot = csum[j] + __shfl_xor(csum[j], 32, 64);
-            if ((lane >> 5) == 0 && n < p.N) out[(long)p.M * ldo + n] = tot;
+            if ((lane >> 5) == 0 && n < p.N) out[(long)p.M * ldo + n] = NP == 2 ? tot * un_b : tot;
         }
     }
 }
+
+template <bool A_KC, bool B_KC, bool CS>
+__global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) { gemm_wide_body<3, A_KC, B_KC, CS>(p); }
 
 // =====================================================================================================
 // The plane GEMM on TWO fp16 pieces per operand and three products per fp32 product (round 6; arithmetic: h2_math.hpp,
@@ -995,7 +1073,6 @@ __global__ __launch_bounds__(512) void gemm_p3w_kernel(Gemm3Args p) {
 // gemm_p3w_kernel with two planes per operand in its ring (stages of 32 KB instead of 48), HALF the matrix instructions and a
 // third fewer fragment reads per step; the block scales leave in the epilogue together with the caller's factor `alpha`.
 // =====================================================================================================
-#define MFMAH2(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h2_f16x8, a), __builtin_bit_cast(h2_f16x8, b), c, 0, 0, 0)
 
 struct GemmH2Args {
     const unsigned short* A;
@@ -1016,211 +1093,18 @@ struct GemmH2Args {
     float alpha;
 };
 
-template <bool KC, int NCH = 8>                             // NCH: 1 KB chunks per plane (8: 256 rows / columns; 4: 128, k-contiguous only)
-struct WideImageH {
-    static constexpr int CHUNK = KC ? 1024 : 1088;         // bytes between the LDS destinations of consecutive waves
-    static constexpr int PLANE = NCH * CHUNK;
-    static constexpr int BYTES = 2 * PLANE;
-    // Fragment reads are ISSUED here (inline asm: the compiler neither reorders them nor guards them with a vmcnt(0)
-    // against the LDS-DMA requests in flight) and RETIRED by the caller with a counted s_waitcnt lgkmcnt.
-    // lane_off: this lane's byte offset inside a plane for row / column tile 0 of the wave
-    static __device__ __forceinline__ unsigned lane_off(int idx0, int lane) {
-        const int l31 = lane & 31, hi = lane >> 5;
-        if (KC) return (unsigned)((idx0 + l31) * 32 + ((hi ^ ((l31 >> 3) & 1)) * 16));   // (halves of rows 8..15 mod 16 swapped)
-        const int t16 = lane & 15, r = t16 >> 2;           // k rows 8 hi + r and 8 hi + r + 4
-        return (unsigned)(r * CHUNK + hi * 512 + (idx0 + 16 * ((lane >> 4) & 1) + 4 * (t16 & 3)) * 2);
-    }
-    static constexpr int READS = KC ? 1 : 2;               // LDS instructions per fragment
-    // fragment of piece Q, tile TILE (32 rows / columns further per tile) at LDS address `addr` (stage + operand + lane_off)
-    template <int Q, int TILE>
-    static __device__ __forceinline__ void issue(u32x4& f, unsigned addr) {
-        if constexpr (KC) {
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(addr), "n"(Q * PLANE + TILE * 32 * 32));
-        } else {
-            u32x2 lo, hi;
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(Q * PLANE + TILE * 64));
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(Q * PLANE + TILE * 64 + 4 * CHUNK));
-            f = u32x4{lo[0], lo[1], hi[0], hi[1]};
-        }
-    }
-    // this thread's source element offset inside a plane at k = 0 (add k for KC, k * ld for MN)
-    static __device__ __forceinline__ long src_off(int t, long ld, int idx0, int nidx) {
-        if (KC) {
-            // LDS slot t = (row t / 2, physical half t % 2); rows 8..15 (mod 16) keep their halves swapped, so that the
-            // 16 lanes of a ds_read_b128 phase (rows r .. r + 15, one k half) cover the 64 banks once
-            const int r = t >> 1, row = idx0 + r;
-            return (long)(row < nidx ? row : nidx - 1) * ld + (((t & 1) ^ ((r >> 3) & 1)) * 8);
-        } else {
-            const int l = t & 63, kk = (t >> 6) + 8 * (l >> 5);
-            int c = idx0 + (l & 31) * 8;
-            if (c >= nidx) c = 0;                            // (columns outside the matrix: any readable address)
-            return (long)kk * ld + c;
-        }
-    }
-};
-
 template <bool A_KC, bool B_KC, bool CS>
-__global__ __launch_bounds__(512) void gemm_h2w_kernel(GemmH2Args p) {
-    using IA = WideImageH<A_KC>;
-    using IB = WideImageH<B_KC>;
-    constexpr int STAGE = IA::BYTES + IB::BYTES;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int id = blockIdx.x;
-    int s, kbeg, kend;
-    const bool tail = p.tail_split > 1 && id >= p.tail_first;          // (tail_split > 1 only with split == 1)
-    if (tail) {
-        const int r = id - p.tail_first;
-        id = p.tail_first + r / p.tail_split;
-        s = r % p.tail_split;
-        kbeg = s * p.tail_kslab;
-        kend = min(p.K, kbeg + p.tail_kslab);
-    } else {
-        s = id % p.split; id /= p.split;
-        kbeg = s * p.kslab;
-        kend = min(p.K, kbeg + p.kslab);
-    }
-    const int tile = id;
-    const int nt = id % p.ntiles;
-    const int mt = id / p.ntiles;
-    const int m0 = mt * 256, n0 = nt * 256;
-    const int nsteps = (kend - kbeg) / kWBK;
-
-    // the source of this thread's unit in the step to request next (advanced by one step per request)
-    const unsigned short* ga = p.A + IA::src_off(t, p.lda, m0, p.M) + (A_KC ? (long)kbeg : (long)kbeg * p.lda);
-    const unsigned short* gb = p.B + IB::src_off(t, p.ldb, n0, p.N) + (B_KC ? (long)kbeg : (long)kbeg * p.ldb);
-    const long sa = A_KC ? (long)kWBK : (long)kWBK * p.lda, sb = B_KC ? (long)kWBK : (long)kWBK * p.ldb;
-    const int wa = wave * IA::CHUNK, wb = IA::BYTES + wave * IB::CHUNK;
-
-    auto request = [&](int stage) __attribute__((always_inline)) {
-        unsigned char* st = lds + stage * STAGE;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga + q * p.pa),
-                                             (__attribute__((address_space(3))) void*)(st + q * IA::PLANE + wa), 16, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb + q * p.pb),
-                                             (__attribute__((address_space(3))) void*)(st + q * IB::PLANE + wb), 16, 0, 0);
-        ga += sa; gb += sb;
-    };
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int wm0 = (wave >> 2) * 128, wn0 = (wave & 3) * 64;
-    const unsigned aoff = IA::lane_off(wm0, lane), boff = IB::lane_off(wn0, lane);
-    const bool do_colsum = CS && !B_KC && p.colsum && mt == 0 && (wave >> 2) == 0;
-    float csum[2] = {0.f, 0.f};
-
-    if (nsteps > 0) request(0);
-    if (nsteps > 1) request(1);
-    int cur = 0, nxt = 2;                                  // stage of step k, stage step k + 2 goes to
-#pragma unroll 1
-    for (int k = 0; k < nsteps; ++k) {
-        if (k + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const unsigned sa_ = (unsigned)(cur * STAGE) + aoff, sb_ = (unsigned)(cur * STAGE + IA::BYTES) + boff;
-        const int rq = nxt;
-        cur = cur == 2 ? 0 : cur + 1; nxt = nxt == 2 ? 0 : nxt + 1;
-        // fragments: B (2 column tiles x 3 pieces), then A row tile by row tile, each requested one tile ahead of its
-        // products; waits are counted in LDS instructions still allowed in flight (they return in order)
-        u32x4 b[2][2], a[2][2];
-        IB::template issue<0, 0>(b[0][0], sb_); IB::template issue<1, 0>(b[0][1], sb_);
-        IB::template issue<0, 1>(b[1][0], sb_); IB::template issue<1, 1>(b[1][1], sb_);
-        IA::template issue<0, 0>(a[0][0], sa_); IA::template issue<1, 0>(a[0][1], sa_);
-#define DCA_TIE4(x) "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1])
-#define DCA_WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" : DCA_TIE4(a), DCA_TIE4(b))
-#define DCA_PRODUCTS(I, AI) do { _Pragma("unroll") for (int pr = 0; pr < 3; ++pr) { \
-            constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0}; \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[I][j] = MFMAH2(a[AI][PA[pr]], b[j][PB[pr]], acc[I][j]); } } while (0)
-        IA::template issue<0, 1>(a[1][0], sa_); IA::template issue<1, 1>(a[1][1], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(2); else DCA_WAIT_LGKM(4);
-        if constexpr (CS && !B_KC) {
-            if (do_colsum) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q)
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) {
-                            const unsigned pw = b[j][q][w];
-                            csum[j] = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_f16x2, pw), h2_f16x2{(_Float16)1.f, (_Float16)1.f}, csum[j], false);
-                        }
-            }
-        }
-        DCA_PRODUCTS(0, 0);
-        // the next-but-one step's requests go out BEHIND the first products: their issue (an M0 write and an address per
-        // piece) fills the gaps of the matrix pipe instead of standing between the barrier and the first product
-        if (k + 2 < nsteps) request(rq);
-        IA::template issue<0, 2>(a[0][0], sa_); IA::template issue<1, 2>(a[0][1], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(2); else DCA_WAIT_LGKM(4);
-        DCA_PRODUCTS(1, 1);
-        IA::template issue<0, 3>(a[1][0], sa_); IA::template issue<1, 3>(a[1][1], sa_);
-        if constexpr (IA::READS == 1) DCA_WAIT_LGKM(2); else DCA_WAIT_LGKM(4);
-        DCA_PRODUCTS(2, 0);
-        DCA_WAIT_LGKM(0);
-        DCA_PRODUCTS(3, 1);
-#undef DCA_PRODUCTS
-#undef DCA_WAIT_LGKM
-#undef DCA_TIE4
-    }
-
-    // the operands' block scales out again (exact: powers of two) and the caller's factor in
-    const int ea = (p.exp_a ? *p.exp_a : 0) + p.exp_a_add, eb = (p.exp_b ? *p.exp_b : 0) + p.exp_b_add;
-    const float un = p.alpha * h2_pow2i(-(ea + eb)), un_b = p.alpha * h2_pow2i(-eb);
-    const int Mo = p.M + (p.colsum ? 1 : 0);
-    if (tail) {
-        // a K slice of a tail tile: the partial tile, tile-local, into the tail workspace
-        float* pt = p.tail_ws + ((long)(tile - p.tail_first) * p.tail_split + s) * (256L * 256);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    pt[(wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 256 + wn0 + j * 32 + (lane & 31)] = acc[i][j][r] * un;
-        return;                                            // (no column sums here: the host keeps m tile 0 out of the tail)
-    }
-    float* out = p.split > 1 ? p.ws + (long)s * Mo * p.N : p.C;
-    const long ldo = p.split > 1 ? (long)p.N : p.ldc;
-    const bool add_bias = p.split == 1 && p.bias != nullptr;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn0 + j * 32 + (lane & 31);
-        const float bv = (add_bias && n < p.N) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < p.M && n < p.N) out[(long)m * ldo + n] = fmaf(acc[i][j][r], un, bv);
-            }
-        }
-        if (CS && do_colsum) {
-            // the lane holds the k rows 8 hi .. + 7 of column n: the other half's share through a lane exchange
-            const float tot = csum[j] + __shfl_xor(csum[j], 32, 64);
-            if ((lane >> 5) == 0 && n < p.N) out[(long)p.M * ldo + n] = tot * un_b;
-        }
-    }
-}
-
+__global__ __launch_bounds__(512) void gemm_h2w_kernel(GemmH2Args p) { gemm_wide_body<2, A_KC, B_KC, CS>(p); }
 
 // The same products from 128 x 256 tiles by FOUR waves (A k-contiguous only: forward products and input gradients), two
 // workgroups per CU (76 KB of LDS each): a workgroup's epilogue -- 128 KB of fp32 through dword stores, during which its waves issue
 // no matrix instruction -- runs beside the other workgroup's K loop instead of idling the CU (one 8-wave workgroup per CU: 40 us of
 // a 98 us tile at K = 512).  The wave's work is that of gemm_h2w_kernel (128 x 64 per wave, the same fragment reads and product
-// order); the B image (256 columns) is requested by 256 threads in two halves.
+// order: wide_step); the B image (256 columns) is requested by 256 threads in two halves, 3 NP requests per thread and step.
 template <bool B_KC>
 __global__ __launch_bounds__(256, 2) void gemm_h2m_kernel(GemmH2Args p) {      // (two waves per SIMD: two workgroups per CU)
-    using IA = WideImageH<true, 4>;
-    using IB = WideImageH<B_KC, 8>;
+    using IA = WideImage<2, true, 4>;
+    using IB = WideImage<2, B_KC, 8>;
     constexpr int STAGE = IA::BYTES + IB::BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1236,70 +1120,29 @@ __global__ __launch_bounds__(256, 2) void gemm_h2m_kernel(GemmH2Args p) {      /
     const unsigned short* gb1 = p.B + IB::src_off(t + 256, p.ldb, n0, p.N) + (B_KC ? (long)kbeg : (long)kbeg * p.ldb);
     const long sa = (long)kWBK, sb = B_KC ? (long)kWBK : (long)kWBK * p.ldb;
     const int wa = wave * IA::CHUNK, wb0 = IA::BYTES + wave * IB::CHUNK, wb1 = IA::BYTES + (wave + 4) * IB::CHUNK;
-
     auto request = [&](int stage) __attribute__((always_inline)) {
         unsigned char* st = lds + stage * STAGE;
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga + q * p.pa),
-                                             (__attribute__((address_space(3))) void*)(st + q * IA::PLANE + wa), 16, 0, 0);
+        for (int q = 0; q < 2; ++q) request16(ga + q * p.pa, st + q * IA::PLANE + wa);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb0 + q * p.pb),
-                                             (__attribute__((address_space(3))) void*)(st + q * IB::PLANE + wb0), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb1 + q * p.pb),
-                                             (__attribute__((address_space(3))) void*)(st + q * IB::PLANE + wb1), 16, 0, 0);
+            request16(gb0 + q * p.pb, st + q * IB::PLANE + wb0);
+            request16(gb1 + q * p.pb, st + q * IB::PLANE + wb1);
         }
         ga += sa; gb0 += sb; gb1 += sb;
     };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero(acc);
     const int wn0 = wave * 64;
     const unsigned aoff = IA::lane_off(0, lane), boff = IB::lane_off(wn0, lane);
+    float csum[2];                                         // (no column sums in this form)
 
     if (nsteps > 0) request(0);
     if (nsteps > 1) request(1);
     int cur = 0, nxt = 2;
 #pragma unroll 1
-    for (int k = 0; k < nsteps; ++k) {
-        if (k + 1 < nsteps) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const unsigned sa_ = (unsigned)(cur * STAGE) + aoff, sb_ = (unsigned)(cur * STAGE + IA::BYTES) + boff;
-        const int rq = nxt;
-        cur = cur == 2 ? 0 : cur + 1; nxt = nxt == 2 ? 0 : nxt + 1;
-        u32x4 b[2][2], a[2][2];
-        IB::template issue<0, 0>(b[0][0], sb_); IB::template issue<1, 0>(b[0][1], sb_);
-        IB::template issue<0, 1>(b[1][0], sb_); IB::template issue<1, 1>(b[1][1], sb_);
-        IA::template issue<0, 0>(a[0][0], sa_); IA::template issue<1, 0>(a[0][1], sa_);
-#define DCA_TIE4(x) "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1])
-#define DCA_WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" : DCA_TIE4(a), DCA_TIE4(b))
-#define DCA_PRODUCTS(I, AI) do { _Pragma("unroll") for (int pr = 0; pr < 3; ++pr) { \
-            constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0}; \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[I][j] = MFMAH2(a[AI][PA[pr]], b[j][PB[pr]], acc[I][j]); } } while (0)
-        IA::template issue<0, 1>(a[1][0], sa_); IA::template issue<1, 1>(a[1][1], sa_);
-        DCA_WAIT_LGKM(2);
-        DCA_PRODUCTS(0, 0);
-        if (k + 2 < nsteps) request(rq);
-        IA::template issue<0, 2>(a[0][0], sa_); IA::template issue<1, 2>(a[0][1], sa_);
-        DCA_WAIT_LGKM(2);
-        DCA_PRODUCTS(1, 1);
-        IA::template issue<0, 3>(a[1][0], sa_); IA::template issue<1, 3>(a[1][1], sa_);
-        DCA_WAIT_LGKM(2);
-        DCA_PRODUCTS(2, 0);
-        DCA_WAIT_LGKM(0);
-        DCA_PRODUCTS(3, 1);
-#undef DCA_PRODUCTS
-#undef DCA_WAIT_LGKM
-#undef DCA_TIE4
-    }
+    for (int k = 0; k < nsteps; ++k) wide_step<2, IA, IB, 3 * 2, false>(acc, k, nsteps, cur, nxt, aoff, boff, false, csum, request);
 
     const int ea = (p.exp_a ? *p.exp_a : 0) + p.exp_a_add, eb = (p.exp_b ? *p.exp_b : 0) + p.exp_b_add;
     const float un = p.alpha * h2_pow2i(-(ea + eb));
@@ -1310,14 +1153,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2m_kernel(GemmH2Args p) {      /
     for (int j = 0; j < 2; ++j) {
         const int n = n0 + wn0 + j * 32 + (lane & 31);
         const float bv = (add_bias && n < p.N) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m < p.M && n < p.N) out[(long)m * ldo + n] = fmaf(acc[i][j][r], un, bv);
-            }
-        }
+        store_column_tile<2>(acc, j, out, ldo, m0, n, p.M, p.N, bv, un);
     }
 }
 
@@ -1661,44 +1497,26 @@ extern "C" long dcahip_gemm_p3_workspace_bytes(int M, int N, int K, int colsum_r
     return (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float);
 }
 
-extern "C" int dcahip_gemm_p3(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a,
-                              const void* B, long ldb, long plane_b, float* C, long ldc, const float* bias,
-                              const int* perm, const long long* cursor, int colsum_row, int split_k,
-                              void* workspace, long workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || ldc < N) return DCAHIP_EINVAL;
-    if (colsum_row && tb) return DCAHIP_EINVAL;
-    if (!al16(A) || !al16(B) || lda % 8 != 0 || ldb % 8 != 0 || plane_a % 8 != 0 || plane_b % 8 != 0) return DCAHIP_EINVAL;
+// ---- what dcahip_gemm_p3 and dcahip_gemm_h2 share on the host
+static bool plane_operands_ok(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a, const void* B, long ldb,
+                              long plane_b, const float* C, long ldc, int colsum_row) {
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || ldc < N) return false;
+    if (colsum_row && tb) return false;
+    if (!al16(A) || !al16(B) || lda % 8 != 0 || ldb % 8 != 0 || plane_a % 8 != 0 || plane_b % 8 != 0) return false;
     // k-contiguous operands are read in units of 8 k: K must be a multiple of 8 (pad both operands with zeros)
-    if ((!ta || tb) && K % 8 != 0) return DCAHIP_EINVAL;
+    if ((!ta || tb) && K % 8 != 0) return false;
     // rows must cover the 16-byte units the tile reads: ld >= the extent rounded up to 8
-    if ((ta ? lda < (M + 7) / 8 * 8 : lda < K) || (tb ? ldb < K : ldb < (N + 7) / 8 * 8)) return DCAHIP_EINVAL;
-    const Plan p = make_plan3(M, N, K, split_k, p3_wide(M, N, K, perm, cursor));
-    const TailPlan tp = tail_plan(p, M, K, colsum_row);
-    const long need = p.split > 1 ? (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float) : tp.ws_bytes;
-    if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
-    Gemm3Args a{static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(B), lda, ldb, plane_a, plane_b,
-                C, bias, perm, cursor, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
-                p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace)};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int grid = p.mtiles * p.ntiles * p.split;
-    if (tp.split > 1) grid = tp.first + (p.mtiles * p.ntiles - tp.first) * tp.split;
-    if (p.cfg == 4) {
-        // (dynamic LDS above 64 KB needs the attribute once per kernel)
-#define DCA_W(AKC, BKC, CSV) do { \
-            constexpr int bytes = 3 * (WideImage<AKC>::BYTES + WideImage<BKC>::BYTES); \
-            static bool set = false; \
-            if (!set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p3w_kernel<AKC, BKC, CSV>), \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes); set = true; } \
-            hipLaunchKernelGGL((gemm_p3w_kernel<AKC, BKC, CSV>), dim3(grid), dim3(512), bytes, s, a); } while (0)
-        if (!ta && !tb) { if (colsum_row) DCA_W(true, false, true); else DCA_W(true, false, false); }
-        else if (!ta && tb) DCA_W(true, true, false);
-        else if (ta && !tb) { if (colsum_row) DCA_W(false, false, true); else DCA_W(false, false, false); }
-        else DCA_W(false, true, false);
-#undef DCA_W
-    } else if (!ta && !tb) hipLaunchKernelGGL((gemm_p3_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_p3_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_p3_kernel<false, false>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm_p3_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
+    return !((ta ? lda < (M + 7) / 8 * 8 : lda < K) || (tb ? ldb < K : ldb < (N + 7) / 8 * 8));
+}
+
+// workspace of a plan: the split-K slabs, or the partial tiles of the tail
+static long plane_workspace(const Plan& p, const TailPlan& tp, int M, int N, int colsum_row) {
+    return p.split > 1 ? (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float) : tp.ws_bytes;
+}
+
+// after the product's launch: its status, then the ordered split-K reduce or the sum of the tail's K slices
+static int plane_finish(const Plan& p, const TailPlan& tp, const float* ws, int M, int N, int colsum_row, const float* bias,
+                        float* C, long ldc, hipStream_t s) {
     int rc = (int)hipGetLastError();
     if (rc != 0) return rc;
     if (p.split > 1) {
@@ -1706,15 +1524,75 @@ extern "C" int dcahip_gemm_p3(int ta, int tb, int M, int N, int K, const void* A
         const long total = (long)Mo * N;
         long g = (total + 255) / 256;
         if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((int)g), dim3(256), 0, s, a.ws, p.split, Mo, N, bias, M, C, ldc);
+        hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((int)g), dim3(256), 0, s, ws, p.split, Mo, N, bias, M, C, ldc);
         rc = (int)hipGetLastError();
     } else if (tp.split > 1) {
         const int ntail = p.mtiles * p.ntiles - tp.first;
-        hipLaunchKernelGGL(gemm_p3w_tail_sum_kernel, dim3(ntail * 16), dim3(256), 0, s, a.tail_ws, tp.first, tp.split, p.ntiles,
+        hipLaunchKernelGGL(gemm_p3w_tail_sum_kernel, dim3(ntail * 16), dim3(256), 0, s, ws, tp.first, tp.split, p.ntiles,
                            M, N, bias, C, ldc);
         rc = (int)hipGetLastError();
     }
     return rc;
+}
+
+// Launch of a ring kernel.  Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize once per kernel AND
+// device: one flag per device ordinal for every kernel (this function's instantiation), looked up by the current device.
+// Concurrent first calls may both set the attribute, which is harmless; it is not set per call (the small-batch steps are
+// bound by their launch gaps).  A device beyond the table gets it on every call.
+constexpr int kMaxDevices = 64;
+template <class Args, void (*KERNEL)(Args)>
+static void launch_ring(int grid, int threads, int bytes, hipStream_t s, const Args& a) {
+    static std::atomic<bool> set[kMaxDevices];
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev >= kMaxDevices) dev = -1;
+    if (dev < 0 || !set[dev].load(std::memory_order_acquire)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (dev >= 0) set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), bytes, s, a);
+}
+
+template <int NP, bool AKC, bool BKC, bool CS, class Args>
+static void launch_wide(int grid, hipStream_t s, const Args& a) {
+    constexpr int bytes = 3 * (WideImage<NP, AKC>::BYTES + WideImage<NP, BKC>::BYTES);
+    if constexpr (NP == 3) launch_ring<Args, gemm_p3w_kernel<AKC, BKC, CS>>(grid, 512, bytes, s, a);
+    else launch_ring<Args, gemm_h2w_kernel<AKC, BKC, CS>>(grid, 512, bytes, s, a);
+}
+
+// the 256 x 256 product on NP pieces by operand layout, and what follows it
+template <int NP, class Args>
+static int gemm_wide(const Args& a, int ta, int tb, const Plan& p, const TailPlan& tp, hipStream_t s) {
+    int grid = p.mtiles * p.ntiles * p.split;
+    if (tp.split > 1) grid = tp.first + (p.mtiles * p.ntiles - tp.first) * tp.split;
+    if (!ta && !tb) {
+        if (a.colsum) launch_wide<NP, true, false, true>(grid, s, a);
+        else if constexpr (NP == 3) launch_wide<NP, true, false, false>(grid, s, a);   // (two pieces: gemm_h2m_kernel takes these)
+    } else if (!ta && tb) launch_wide<NP, true, true, false>(grid, s, a);
+    else if (ta && !tb) { if (a.colsum) launch_wide<NP, false, false, true>(grid, s, a); else launch_wide<NP, false, false, false>(grid, s, a); }
+    else launch_wide<NP, false, true, false>(grid, s, a);
+    return plane_finish(p, tp, a.ws, a.M, a.N, a.colsum, a.bias, a.C, a.ldc, s);
+}
+
+extern "C" int dcahip_gemm_p3(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a,
+                              const void* B, long ldb, long plane_b, float* C, long ldc, const float* bias,
+                              const int* perm, const long long* cursor, int colsum_row, int split_k,
+                              void* workspace, long workspace_bytes, void* stream) {
+    if (!plane_operands_ok(ta, tb, M, N, K, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
+    const Plan p = make_plan3(M, N, K, split_k, p3_wide(M, N, K, perm, cursor));
+    const TailPlan tp = tail_plan(p, M, K, colsum_row);
+    const long need = plane_workspace(p, tp, M, N, colsum_row);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
+    Gemm3Args a{static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(B), lda, ldb, plane_a, plane_b,
+                C, bias, perm, cursor, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
+                p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace)};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.cfg == 4) return gemm_wide<3>(a, ta, tb, p, tp, s);
+    const int grid = p.mtiles * p.ntiles * p.split;
+    if (!ta && !tb) hipLaunchKernelGGL((gemm_p3_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
+    else if (!ta && tb) hipLaunchKernelGGL((gemm_p3_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
+    else if (ta && !tb) hipLaunchKernelGGL((gemm_p3_kernel<false, false>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemm_p3_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
+    return plane_finish(p, tp, a.ws, M, N, colsum_row, bias, C, ldc, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1751,83 +1629,32 @@ extern "C" int dcahip_gemm_h2_supported(int M, int N, int K) { return p3_wide(M,
 extern "C" long dcahip_gemm_h2_workspace_bytes(int M, int N, int K, int colsum_row, int split_k) {
     if (!p3_wide(M, N, K, nullptr, nullptr)) return 0;
     const Plan p = make_plan3(M, N, K, split_k, true);
-    if (p.split > 1) return (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float);
-    return tail_plan(p, M, K, colsum_row).ws_bytes;
+    return plane_workspace(p, tail_plan(p, M, K, colsum_row), M, N, colsum_row);
 }
 
 extern "C" int dcahip_gemm_h2(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a, const int* exp_a, int exp_a_add,
                               const void* B, long ldb, long plane_b, const int* exp_b, int exp_b_add, float alpha,
                               float* C, long ldc, const float* bias, int colsum_row, int split_k,
                               void* workspace, long workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || ldc < N) return DCAHIP_EINVAL;
+    if (!plane_operands_ok(ta, tb, M, N, K, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
     if (!p3_wide(M, N, K, nullptr, nullptr)) return DCAHIP_EINVAL;
-    if (colsum_row && tb) return DCAHIP_EINVAL;
-    if (!al16(A) || !al16(B) || lda % 8 != 0 || ldb % 8 != 0 || plane_a % 8 != 0 || plane_b % 8 != 0) return DCAHIP_EINVAL;
-    if ((!ta || tb) && K % 8 != 0) return DCAHIP_EINVAL;
-    if ((ta ? lda < (M + 7) / 8 * 8 : lda < K) || (tb ? ldb < K : ldb < (N + 7) / 8 * 8)) return DCAHIP_EINVAL;
     const Plan p = make_plan3(M, N, K, split_k, true);
     const TailPlan tp = tail_plan(p, M, K, colsum_row);
-    const long need = p.split > 1 ? (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float) : tp.ws_bytes;
+    const long need = plane_workspace(p, tp, M, N, colsum_row);
     if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
     GemmH2Args a{static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(B), lda, ldb, plane_a, plane_b,
                  C, bias, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
                  p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace), exp_a, exp_b, exp_a_add, exp_b_add, alpha};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!ta && !tb && !colsum_row) {
-        // forward products (A k-contiguous, B n-contiguous): 128 x 256 tiles by four waves, two workgroups per CU
-        // (gemm_h2m_kernel).  Measured at configs[4] (tools/ab_heads_lib.py, one box): heads forward 0.87 - 0.90 -> 0.73 - 0.74 ms,
-        // first layer forward (split-K) 0.368 -> 0.362; the input gradient (B k-contiguous, split-K) 0.50 -> 0.64: stays on
-        // the 8-wave kernel
-        GemmH2Args h = a;
-        h.mtiles = (M + 127) / 128;
-        h.tail_first = 0; h.tail_split = 1;
-        const int gridm = h.mtiles * h.ntiles * h.split;
-#define DCA_M(BKC) do { \
-            constexpr int bytes = 3 * (WideImageH<true, 4>::BYTES + WideImageH<BKC, 8>::BYTES); \
-            static bool set = false; \
-            if (!set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h2m_kernel<BKC>), \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes); set = true; } \
-            hipLaunchKernelGGL((gemm_h2m_kernel<BKC>), dim3(gridm), dim3(256), bytes, s, h); } while (0)
-        DCA_M(false);
-#undef DCA_M
-        int rcm = (int)hipGetLastError();
-        if (rcm != 0) return rcm;
-        if (h.split > 1) {
-            const long total = (long)M * N;
-            long g = (total + 255) / 256;
-            if (g > 4096) g = 4096;
-            hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((int)g), dim3(256), 0, s, h.ws, h.split, M, N, bias, M, C, ldc);
-            rcm = (int)hipGetLastError();
-        }
-        return rcm;
-    }
-    int grid = p.mtiles * p.ntiles * p.split;
-    if (tp.split > 1) grid = tp.first + (p.mtiles * p.ntiles - tp.first) * tp.split;
-#define DCA_W(AKC, BKC, CSV) do { \
-        constexpr int bytes = 3 * (WideImageH<AKC>::BYTES + WideImageH<BKC>::BYTES); \
-        static bool set = false; \
-        if (!set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_h2w_kernel<AKC, BKC, CSV>), \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes); set = true; } \
-        hipLaunchKernelGGL((gemm_h2w_kernel<AKC, BKC, CSV>), dim3(grid), dim3(512), bytes, s, a); } while (0)
-    if (!ta && !tb) { if (colsum_row) DCA_W(true, false, true); else DCA_W(true, false, false); }
-    else if (!ta && tb) DCA_W(true, true, false);
-    else if (ta && !tb) { if (colsum_row) DCA_W(false, false, true); else DCA_W(false, false, false); }
-    else DCA_W(false, true, false);
-#undef DCA_W
-    int rc = (int)hipGetLastError();
-    if (rc != 0) return rc;
-    if (p.split > 1) {
-        const int Mo = M + (colsum_row ? 1 : 0);
-        const long total = (long)Mo * N;
-        long g = (total + 255) / 256;
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3((int)g), dim3(256), 0, s, a.ws, p.split, Mo, N, bias, M, C, ldc);
-        rc = (int)hipGetLastError();
-    } else if (tp.split > 1) {
-        const int ntail = p.mtiles * p.ntiles - tp.first;
-        hipLaunchKernelGGL(gemm_p3w_tail_sum_kernel, dim3(ntail * 16), dim3(256), 0, s, a.tail_ws, tp.first, tp.split, p.ntiles,
-                           M, N, bias, C, ldc);
-        rc = (int)hipGetLastError();
-    }
-    return rc;
+    if (ta || tb || colsum_row) return gemm_wide<2>(a, ta, tb, p, tp, s);
+    // forward products (A k-contiguous, B n-contiguous): 128 x 256 tiles by four waves, two workgroups per CU
+    // (gemm_h2m_kernel).  Measured at configs[4] (tools/ab_heads_lib.py, one box): heads forward 0.87 - 0.90 -> 0.73 - 0.74 ms,
+    // first layer forward (split-K) 0.368 -> 0.362; the input gradient (B k-contiguous, split-K) 0.50 -> 0.64: stays on
+    // the 8-wave kernel
+    a.mtiles = (M + 127) / 128;
+    a.tail_first = 0; a.tail_split = 1;
+    constexpr int bytes = 3 * (WideImage<2, true, 4>::BYTES + WideImage<2, false, 8>::BYTES);
+    launch_ring<GemmH2Args, gemm_h2m_kernel<false>>(a.mtiles * a.ntiles * a.split, 256, bytes, s, a);
+    return plane_finish(p, TailPlan{0, 1, 0, 0}, a.ws, M, N, 0, bias, C, ldc, s);
 }
+

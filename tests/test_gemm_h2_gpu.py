@@ -69,7 +69,10 @@ SHAPES = [
     (0, 1, 640, 512, 1504, False, False, 0),                # input gradient
     (0, 1, 600, 520, 528, False, False, 2),
     (1, 1, 512, 600, 128, False, False, 0),
-    (0, 0, 1024, 5000, 512, True, False, 0),                # a partial last round of tiles: the tail path
+    (0, 0, 1024, 5000, 512, True, False, 0),                # a partial last round of tiles (forward: the four-wave kernel, no tail)
+    (0, 0, 600, 515, 272, True, True, 0),                   # forward layout WITH column sums (the eight-wave kernel), ragged tiles
+    (1, 0, 512, 38400, 128, False, True, 0),                # 300 tiles: 44 tail tiles x 2 K slices, column sums from m tile 0
+    (0, 1, 768, 22100, 128, False, False, 0),               # 261 tiles: 5 tail tiles x 2 K slices, ragged N, k-contiguous B
 ]
 
 
