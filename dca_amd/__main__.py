@@ -1,6 +1,7 @@
 """Command line of the reference (``dca input outputdir [flags]``, dca/__main__.py:18-154) on the
 MI355X path: same positionals, flag names, defaults and output files.  The option table below
-restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
+restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--neighbors K`` (beyond the reference) writes the latent space's
+k-nearest-neighbour lists (dca_amd/neighbors.py); ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
 dca/hyper.py with hyperopt's TPE restated in dca_amd/tpe.py); ``--tensorboard`` is accepted for
 command-line compatibility and ignored.
 """
@@ -55,6 +56,9 @@ _OPTIONS = [
     (('--score',), dict(dest='score', action='store_true',
                         help='after the result files: the fitted model\'s mean negative log-likelihood per cell (cell_nll.tsv, train and '
                              'test cells alike) and per gene (gene_nll.tsv), computed on the GPU')),
+    (('--neighbors',), dict(dest='neighbors', type=int, default=None, metavar='K',
+                            help='after the result files: every cell\'s K nearest other cells in the latent space, exact and '
+                                 'Euclidean, computed on the GPU (knn_indices.tsv: 0-based cell numbers, knn_distances.tsv)')),
     (('--mcv',), dict(dest='mcv', type=float, default=None, metavar='FRACTION',
                       help='molecular cross-validation instead of the denoising run: thin every count binomially, fit on FRACTION '
                            'of the molecules with the network and training flags given, score the held-out rest of every cell; '

@@ -191,11 +191,9 @@ class Autoencoder():
             want.add('mean')
         return want
 
-    def _run_predict(self, adata, want, chunk=None):
-        """One inference pass over all cells; returns host arrays for the requested outputs."""
+    def _bind_inputs(self, adata):
+        """Attaches the inputs of these cells to the engine for an inference pass (no targets)."""
         eng = self.engine
-        if chunk is None:       # rows per device -> host chunk: 2 page-locked staging buffers of this many rows per output
-            chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
         n = adata.n_obs
         X = adata.X
         sf = np.asarray(adata.obs['size_factors'].values, dtype=np.float32)
@@ -207,6 +205,14 @@ class Autoencoder():
                 dd.compact = eng.cc if eng.cc is not None else (False if getattr(eng, 'cc_verdict', None) is False else None)
         else:
             eng.load_data(X, None, sf)
+
+    def _run_predict(self, adata, want, chunk=None):
+        """One inference pass over all cells; returns host arrays for the requested outputs."""
+        eng = self.engine
+        if chunk is None:       # rows per device -> host chunk: 2 page-locked staging buffers of this many rows per output
+            chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
+        n = adata.n_obs
+        self._bind_inputs(adata)
         chunk = min(chunk, n)
         eng.reserve(chunk)
         lay = eng.lay
@@ -269,6 +275,43 @@ class Autoencoder():
             adata.X = outs['mean']
         if mode == 'latent':
             adata.X = adata.raw.X.copy()  # recover normalized expression values (network.py:208-209)
+
+    # ------------------------------------------------------------------ neighbours
+    def neighbors(self, adata, n_neighbors=15, copy=False):
+        """The exact k-nearest-neighbour graph of these cells in the latent space, computed on the device
+        (Engine.latent_knn -> dcahip_knn) -- beyond the reference, which leaves it to scanpy on the host.  The inputs are
+        bound as ``predict`` binds them.  Stores
+
+            adata.obsm['X_dca']               the latent representation, what ``predict(mode='latent')`` stores
+            adata.obsm['dca_knn_indices']     int32 [n, n_neighbors]: every cell's nearest OTHER cells, nearest first
+                                              (ties by index)
+            adata.obsm['dca_knn_distances']   float32 [n, n_neighbors]: their Euclidean distances
+            adata.uns['dca_neighbors']        {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
+
+        ``n_neighbors`` counts OTHER cells (a cell is left out of its own list by index; an identical cell elsewhere
+        stays, at distance 0): scanpy's ``pp.neighbors(n_neighbors=K)`` counts the cell itself, so its K corresponds to
+        ``n_neighbors = K - 1`` here.  1 <= n_neighbors <= min(64, n - 1); dca_amd.neighbors.knn_graph turns the two
+        arrays into scanpy's ``obsp['distances']`` layout.  Returns ``adata`` if ``copy`` else None, like ``predict``."""
+        eng = self.engine
+        self._wanted('latent', False)                     # hidden_size=(): no centre layer
+        k = int(n_neighbors)
+        n = adata.n_obs
+        if k > n - 1:
+            raise ValueError('dca_amd: neighbors: n_neighbors = %d, but every one of the %d cells has only %d others'
+                             % (k, n, n - 1))
+        from .neighbors import check_knn_args
+        check_knn_args(n, n, eng.lay.hidden[eng.center], k)
+        if eng.comm.world > 1:
+            raise ValueError('dca_amd: neighbors() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        adata = adata.copy() if copy else adata
+        self._bind_inputs(adata)
+        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
+        latent, idx, d2 = eng.latent_knn(k, chunk=min(chunk, n))
+        adata.obsm['X_dca'] = latent.cpu().numpy()
+        adata.obsm['dca_knn_indices'] = idx.cpu().numpy()
+        adata.obsm['dca_knn_distances'] = np.sqrt(d2.cpu().numpy())
+        adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
+        return adata if copy else None
 
     # ------------------------------------------------------------------ scoring
     def score(self, adata, output_subset=None, use_raw_as_output=True, copy=False):

@@ -523,6 +523,54 @@ class HipOps:
             out.append(CsrCounts(ptr, idx, val, n, csr.G))
         return out[0], out[1]
 
+    def knn_splits(self, nq, n, d, k):
+        """The number of candidate splits dcahip_knn takes for this shape when it is asked for 0."""
+        s = int(self.L.dcahip_knn_splits(nq, n, d, k))
+        hip.check(min(s, 0), 'knn_splits')
+        return s
+
+    def knn(self, Q, X, k, self_offset=-1, splits=0, out=None):
+        """K-NEIGHBOURS (include/dcahip.h, dcahip_knn): the k nearest rows of X [n, d] to every row of Q [nq, d] (fp32 device
+        tensors, unit column stride, any row stride), exact, Euclidean.  Returns (idx [nq, k] int32, d2 [nq, k] float32):
+        per query the k smallest under (squared distance, index), in that order; -1 / +inf where X has fewer than k rows.
+        self_offset >= 0: query q is row self_offset + q of X and is left out by index.  splits: 0 = the library's choice,
+        1 .. 64 = that many candidate ranges (same bits).  out: (idx, d2) tensors to write into (row stride >= k, the same
+        for both).  A limit of the kernel (k 1 .. 64, d 1 .. 128) or a non-finite coordinate raises ValueError."""
+        from .neighbors import check_knn_args
+        p = hip.ptr
+        for t in (Q, X):
+            if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError('dca_amd: knn: operands are 2-d float32 tensors with unit column stride')
+        (nq, d), n = Q.shape, X.shape[0]
+        if X.shape[1] != d:
+            raise ValueError('dca_amd: knn: queries have %d columns, candidates %d' % (d, X.shape[1]))
+        k, splits, self_offset = int(k), int(splits), int(self_offset)
+        check_knn_args(nq, n, d, k, splits, self_offset)
+        dev = X.device
+        if out is None:
+            idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+            d2 = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        else:
+            idx, d2 = out
+            if idx.dtype != torch.int32 or d2.dtype != torch.float32 or idx.shape != (nq, k) or d2.shape != (nq, k) or \
+                    (nq > 1 and idx.stride(0) != d2.stride(0)) or (k > 1 and (idx.stride(1) != 1 or d2.stride(1) != 1)):
+                raise ValueError('dca_amd: knn: out = (int32 [nq, k], float32 [nq, k]) with one row stride')
+        if nq == 0:
+            return idx, d2
+        ldq = Q.stride(0) if nq > 1 else d
+        ldx = X.stride(0) if n > 1 else d
+        ldo = idx.stride(0) if nq > 1 else k
+        nbytes = int(self.L.dcahip_knn_workspace_bytes(nq, n, d, k, splits))
+        hip.check(min(nbytes, 0), 'knn_workspace_bytes')
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.check(self.L.dcahip_knn(p(Q), ldq, nq, p(X) if n else None, ldx, n, d, k, self_offset, splits, p(idx), p(d2), ldo,
+                                    p(ws), p(status), hip.stream()), 'knn')
+        bad = int(status.item())
+        if bad:
+            raise ValueError('dca_amd: knn: %d coordinates are not finite (NaN or inf)' % bad)
+        return idx, d2
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];

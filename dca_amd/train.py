@@ -451,6 +451,8 @@ def train_with_args(args):
     net.predict_write(adata, args.outputdir, mode='full', colnames=columns)
     if getattr(args, 'score', False):
         write_scores(net, adata, x_in, subset, args.outputdir)
+    if getattr(args, 'neighbors', None):
+        write_neighbors(net, adata, x_in, args.neighbors, args.outputdir)
 
 
 def mcv_with_args(args, seed):
@@ -492,3 +494,20 @@ def write_scores(net, adata, x_in, subset, output_dir):
     means = cells.groupby('split', sort=True)['nll'].mean()
     print('dca: mean NLL per cell and gene -- ' + ', '.join('%s: %.6f (%d cells)' % (k, means[k], int((cells['split'] == k).sum()))
                                                             for k in means.index))
+
+
+
+def write_neighbors(net, adata, x_in, k, output_dir):
+    """--neighbors K: every cell's K nearest other cells in the latent space (train and test cells alike:
+    Autoencoder.neighbors) -> knn_indices.tsv (index = cell name; K columns of 0-based row numbers, nearest first) and
+    knn_distances.tsv (their Euclidean distances, six decimals)."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.neighbors(adata, n_neighbors=k)
+    cells = pd.Index(adata.obs_names)
+    cols = ['n%d' % (j + 1) for j in range(k)]
+    pd.DataFrame(np.asarray(adata.obsm['dca_knn_indices']), index=cells, columns=cols).to_csv(
+        os.path.join(output_dir, 'knn_indices.tsv'), sep='\t')
+    pd.DataFrame(np.asarray(adata.obsm['dca_knn_distances'], dtype=np.float64), index=cells, columns=cols).to_csv(
+        os.path.join(output_dir, 'knn_distances.tsv'), sep='\t', float_format='%.6f')

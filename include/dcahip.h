@@ -832,6 +832,42 @@ int dcahip_enc0_fwd_lut(const unsigned char* Yc, long ldc, const int* ovf_ptr, c
                         float* Z, long ldz, void* workspace, long workspace_bytes, void* stream);
 
 /*
+ * K-NEIGHBOURS (dca_amd/csrc/dcahip_knn.hip): exact (brute-force) Euclidean k-nearest neighbours of every query row among
+ * the candidate rows, distance evaluation and top-k selection fused: no nq x n matrix exists.  Beyond the reference, which
+ * leaves the neighbour graph of obsm['X_dca'] to scanpy on the host; no reference call site.
+ *
+ *   Q [nq, ldq], X [n, ldx] : queries and candidates, d columns each (ldq, ldx >= d); Q may be X
+ *   k                       : neighbours per query, 1 .. 64;  d: 1 .. 128;  n < 2^31
+ *   self_offset             : query row q IS candidate row self_offset + q and is left out BY INDEX (other copies of the
+ *                             row stay, at distance 0); -1: nothing is left out
+ *   splits                  : 0 = the library's choice, dcahip_knn_splits(nq, n, d, k): enough workgroups to fill the part
+ *                             when the query blocks are few, every split keeping about 1 000 candidates; 1 .. 64: this
+ *                             many contiguous candidate ranges (an argument of the call: the library keeps no switch)
+ *   idx_out [nq, ldo] int32, d2_out [nq, ldo] fp32 (ldo >= k): columns 0 .. k-1 of every row are written, nothing else
+ *   ws                      : >= dcahip_knn_workspace_bytes(nq, n, d, k, splits) bytes, 16-byte aligned, any content: the
+ *                             sorted list of every (split, query), and X zero-padded when d is not 8, 16, 32, 64 or 128
+ *   status                  : one int32, zeroed by the caller: += the non-finite coordinates met in Q and in X (a matrix
+ *                             passed as both is counted twice); the outputs are unspecified then, but written in bounds
+ *
+ * The distance: d2(a, b) = s0 + s1, s_p = fma(a_j - b_j, a_j - b_j, s_p) over the j of parity p in ascending order, all in
+ * fp32 -- the direct form (the Gram form |a|^2 + |b|^2 - 2 a.b cancels catastrophically on clusters far from the origin,
+ * exactly what a ReLU latent is).  The order is a function of d alone, so d2(a, b) and d2(b, a) are the same bits, d2 >= 0,
+ * equal rows are at exactly 0, and the relative error is at most (d + 3) 2^-24 to first order.
+ * The result: per query the k smallest candidates under the total order (d2, index) ascending, in that order, SQUARED
+ * distances; with fewer than k candidates the tail is index -1 at +inf.  Because the order is total the output is the same
+ * bits for every `splits`.  Three launches on the stream (check / pad, scan, merge), plain stores only (the status counter
+ * aside), every index formed in 64 bits; nothing outside the operands is read or written.
+ * DCAHIP_EINVAL (nothing launched): k outside 1 .. 64, d outside 1 .. 128, nq < 0, n < 0, splits outside 0 .. 64, a leading
+ * dimension below its row length, self_offset < -1, a missing pointer (the two size functions return it for the same
+ * shapes).  nq = 0 launches nothing and returns 0.
+ */
+int dcahip_knn_splits(int nq, int n, int d, int k);
+long dcahip_knn_workspace_bytes(int nq, int n, int d, int k, int splits);
+int dcahip_knn(const float* Q, long ldq, int nq, const float* X, long ldx, int n, int d, int k,
+               long self_offset, int splits, int* idx_out, float* d2_out, long ldo,
+               void* ws, int* status, void* stream);
+
+/*
  * K-PEER (dca_amd/csrc/dcahip_peer.hip): the small exchanges of the data-parallel step without a library call.
  *   slots[q], flags[q]: device arrays of `world` pointers to every rank's exchange buffers (rank's own: its local
  *   allocation; the others: mapped with hipIpcOpenMemHandle), each dcahip_peer_slot_bytes(world, nmax) /
