@@ -111,6 +111,121 @@ __device__ __forceinline__ float wg_rowlane_sum(float v, float* sm /*[4][64]*/) 
     return (sm[tx] + sm[64 + tx]) + (sm[128 + tx] + sm[192 + tx]);
 }
 
+// =====================================================================================================
+// Stages of a hidden layer on a tile of at most 64 columns, shared by the small-batch kernels, the small-batch chain and
+// the K-STACK step / chain kernels below.  A thread is (column or input unit tx, row lane ty) and holds the rows
+// ty + 4 j, j < NR, in registers; matrix operands lie in LDS with the row strides LDW / LDH / LD (floats).  The pieces
+// take registers and LDS pointers and issue no global loads: when the operands are requested, how the accumulators
+// start and where results are stored stays with each kernel.  UNROLL = the unroll count of a product loop (tile_fwd: 0
+// = the compiler's choice).
+// Kept apart on purpose (each checked on the compiled code):
+//  - hidden_stack_fwd / hidden_stack_bwd_kernel share only the per-element formulas.  Their product loops carry a row
+//    guard and no unroll count; through a function the compiler schedules them differently and both kernels need more
+//    registers, which the cooperative launch (every workgroup resident) does not allow.  The same holds for the merge of
+//    the blocks' backward sums, which is therefore written out in hidden_stack_bwd_kernel and stack_bwd_step_kernel.
+//  - the kernels that accumulate under `if (element exists)` (block_stats, prep, the block statistics and the lower
+//    layer's sums of the step kernels): there the compiler contracts q += d * d into one fma, in tile_col_stats /
+//    tile_dy_sums (a select, as the small-batch kernels always had) it cannot -- joining them would change their bits.
+//  - stack_bwd_chain_kernel's masked sums: sharing them costs its widest instance registers beyond 256.
+// =====================================================================================================
+
+// acc[j] += sum_k Hm[ty + 4 j][k] W[k][tx], k < K4 (a multiple of 4).  The rows beyond the batch are computed from
+// whatever the tile holds (finite): unspecified, never stored.
+template <int NR, int LDW, int LDH>
+__device__ __forceinline__ void tile_fwd_k4(float (&acc)[NR], const float* W, const float* Hm, int k, int tx, int ty) {
+    const float w0 = W[(k + 0) * LDW + tx], w1 = W[(k + 1) * LDW + tx];
+    const float w2 = W[(k + 2) * LDW + tx], w3 = W[(k + 3) * LDW + tx];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const float4 h4 = *reinterpret_cast<const float4*>(Hm + (ty + 4 * j) * LDH + k);
+        acc[j] = fmaf(h4.w, w3, fmaf(h4.z, w2, fmaf(h4.y, w1, fmaf(h4.x, w0, acc[j]))));
+    }
+}
+template <int NR, int LDW, int LDH, int UNROLL>
+__device__ __forceinline__ void tile_fwd(float (&acc)[NR], const float* W, const float* Hm, int K4, int tx, int ty) {
+    if constexpr (UNROLL == 0) {
+        for (int k = 0; k < K4; k += 4) tile_fwd_k4<NR, LDW, LDH>(acc, W, Hm, k, tx, ty);
+    } else {
+#pragma unroll UNROLL
+        for (int k = 0; k < K4; k += 4) tile_fwd_k4<NR, LDW, LDH>(acc, W, Hm, k, tx, ty);
+    }
+}
+
+// (mean, M2) of this thread's column over the rows < nrows of a register tile; cv = the column exists (the result of a
+// column that does not is unspecified).  Valid in every thread of the column.
+template <int NR>
+__device__ __forceinline__ void tile_col_stats(const float (&z)[NR], bool cv, int nrows, int ty, float* sm /*[4][64]*/,
+                                               float& mean, float& m2) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) s += (cv && ty + 4 * j < nrows) ? z[j] : 0.f;
+    mean = wg_rowlane_sum(s, sm) / (float)nrows;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) { const float d = z[j] - mean; q += (cv && ty + 4 * j < nrows) ? d * d : 0.f; }
+    m2 = wg_rowlane_sum(q, sm);
+}
+
+// Batch-norm finish of a column: biased variance of n rows (the division in fp64), 1 / std, the moving statistics
+// (moving = moving - (moving - batch) * (1 - momentum)), the normalised element.  act_fwd(act, xhat + beta) stays with
+// the callers: whether the compiler contracts the product and that sum into one fma depends on what a kernel does
+// between the two (a store of xhat behind a branch), and every kernel keeps the bits it has.
+__device__ __forceinline__ float bn_var(double m2, double n) { return (float)(m2 / n); }
+__device__ __forceinline__ float bn_inv_std(float var, float eps) { return 1.f / sqrtf(var + eps); }
+__device__ __forceinline__ float bn_moving(float moving, float batch, float momentum) {
+    return moving - (moving - batch) * (1.f - momentum);
+}
+__device__ __forceinline__ float bn_xhat(float z, float mean, float inv) { return (z - mean) * inv; }
+
+// dy[j] = dyf(j) (= dH * slope of the activation) where the element exists, else 0; s1 += sum dy, s2 += sum dy xhat.
+// (An element that does not exist enters s2 as 0 times the xhat the caller handed in: callers load from clamped, valid
+// addresses.)
+template <int NR, class F>
+__device__ __forceinline__ void tile_dy_sums(float (&dy)[NR], const float (&xh)[NR], bool cv, int nrows, int ty, F dyf,
+                                             float& s1, float& s2) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        dy[j] = (cv && ty + 4 * j < nrows) ? dyf(j) : 0.f;
+        s1 += dy[j]; s2 += dy[j] * xh[j];
+    }
+}
+
+// batch-norm backward of one element: m1 = sum dy / n, m2 = sum dy xhat / n over the whole batch
+__device__ __forceinline__ float bn_dz(float inv, float dy, float xh, float m1, float m2) {
+    return inv * (dy - m1 - xh * m2);
+}
+
+// Weight-gradient tile product: acc[j] += sum_{r < nrows} Hp[r][16 ty + j] dZ[r][tx], bs += sum_r dZ[r][tx] (the bias row)
+template <int LD, int UNROLL>
+__device__ __forceinline__ void tile_dw(float (&acc)[16], float& bs, const float* dZ, const float* Hp, int nrows, int tx, int ty) {
+#pragma unroll UNROLL
+    for (int r = 0; r < nrows; ++r) {
+        const float d = dZ[r * LD + tx];
+        bs += d;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 h4 = *reinterpret_cast<const float4*>(Hp + r * LD + 16 * ty + 4 * q4);
+            acc[4 * q4 + 0] = fmaf(h4.x, d, acc[4 * q4 + 0]); acc[4 * q4 + 1] = fmaf(h4.y, d, acc[4 * q4 + 1]);
+            acc[4 * q4 + 2] = fmaf(h4.z, d, acc[4 * q4 + 2]); acc[4 * q4 + 3] = fmaf(h4.w, d, acc[4 * q4 + 3]);
+        }
+    }
+}
+
+// Input-gradient tile product: acc[j] += sum_{c < 64} dZ[ty + 4 j][c] W[tx][c] (thread = input unit tx; the tiles are zero
+// beyond the block's rows and the layer's width)
+template <int NR, int LD, int UNROLL>
+__device__ __forceinline__ void tile_dhp(float (&acc)[NR], const float* W, const float* dZ, int tx, int ty) {
+#pragma unroll UNROLL
+    for (int c4 = 0; c4 < 64; c4 += 4) {
+        const float4 w4 = *reinterpret_cast<const float4*>(W + tx * LD + c4);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const float4 d4 = *reinterpret_cast<const float4*>(dZ + (ty + 4 * j) * LD + c4);
+            acc[j] = fmaf(d4.w, w4.w, fmaf(d4.z, w4.z, fmaf(d4.y, w4.y, fmaf(d4.x, w4.x, acc[j]))));
+        }
+    }
+}
+
 // part[r][0][c] = mean of column c over the chunk's rows, part[r][1][c] = sum (x - mean)^2
 __global__ __launch_bounds__(256) void col_moments_kernel(const float* Z, long ldz, int B, int H,
                                                           float* part) {
@@ -403,14 +518,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
 #pragma unroll
         for (int u = 0; u < kApplyRows / 4; ++u) {
             const int i = r0 + ty + 4 * u;
-            if (i < r1) a.dZ[(long)i * a.ldz + c] = inv * (d[u] * act_slope(a.act, h[u], x[u], bc) - m1 - x[u] * m2);
+            if (i < r1) a.dZ[(long)i * a.ldz + c] = bn_dz(inv, d[u] * act_slope(a.act, h[u], x[u], bc), x[u], m1, m2);
         }
     }
 }
 
 // ---- small batches (B <= kFusedRows = 64 rows, one GPU): statistics AND apply in one launch, one workgroup per 64
 // columns -- the reference-default batch of 32 cells (dca/train.py:37) spends its step in launch gaps and dependent
-// memory round trips, not in arithmetic.  Same formulas as col_moments_kernel + bn_relu_apply_kernel with one chunk.
+// memory round trips, not in arithmetic.  The statistics are tile_col_stats (col_moments_kernel with one chunk), the
+// rest the bn_* pieces bn_relu_apply_kernel spells out.
 constexpr int kFusedRows = 64;
 
 // RPT = rows per thread (4 row lanes): the column slab is read ONCE into registers -- at 32 rows these kernels are
@@ -422,7 +538,6 @@ __global__ __launch_bounds__(256) void bn_relu_small_kernel(BnApplyArgs a) {
     const int c = blockIdx.x * 64 + tx;
     const bool cv = c < a.H;
     float z[RPT];
-    float s = 0.f;
     const int ccl = cv ? c : a.H - 1;
     const float mm_in = a.mm[ccl], mv_in = a.mv[ccl], beta_in = a.beta ? a.beta[ccl] : 0.f;
 #pragma unroll
@@ -430,35 +545,23 @@ __global__ __launch_bounds__(256) void bn_relu_small_kernel(BnApplyArgs a) {
         const int i = ty + 4 * k;
         z[k] = a.Z[(long)(i < a.B ? i : a.B - 1) * a.ldz + ccl];
     }
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        z[k] = (cv && ty + 4 * k < a.B) ? z[k] : 0.f;
-        s += z[k];
-    }
-    const float mean = wg_rowlane_sum(s, sm) / (float)a.B;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        const float d = z[k] - mean;
-        q += (ty + 4 * k < a.B) ? d * d : 0.f;
-    }
-    const float m2 = wg_rowlane_sum(q, sm);
+    float mean, m2;
+    tile_col_stats(z, cv, a.B, ty, sm, mean, m2);
     if (!cv) return;
-    const float var = (float)((double)m2 / (double)a.B);             // biased variance
-    const float inv = 1.f / sqrtf(var + a.eps);
+    const float var = bn_var((double)m2, (double)a.B);
+    const float inv = bn_inv_std(var, a.eps);
     if (ty == 0) {
-        a.mm[c] = mm_in - (mm_in - mean) * (1.f - a.momentum);
-        a.mv[c] = mv_in - (mv_in - var) * (1.f - a.momentum);
+        a.mm[c] = bn_moving(mm_in, mean, a.momentum);
+        a.mv[c] = bn_moving(mv_in, var, a.momentum);
         if (a.inv_std) a.inv_std[c] = inv;
     }
-    const float beta = beta_in;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const int i = ty + 4 * k;
         if (i < a.B) {
-            const float xh = (z[k] - mean) * inv;
+            const float xh = bn_xhat(z[k], mean, inv);
             if (a.xhat) a.xhat[(long)i * a.ldx + c] = xh;
-            a.Hout[(long)i * a.ldh + c] = act_fwd(a.relu, xh + beta);
+            a.Hout[(long)i * a.ldh + c] = act_fwd(a.relu, xh + beta_in);
         }
     }
 }
@@ -469,35 +572,29 @@ __global__ __launch_bounds__(256) void bn_bwd_small_kernel(BnBwdArgs a) {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + tx;
     const bool cv = c < a.H;
-    float dy[RPT], xh[RPT], ha[RPT];
+    float dh[RPT], dy[RPT], xh[RPT], ha[RPT];
     float s1 = 0.f, s2 = 0.f;
     const int ccl = cv ? c : a.H - 1;
-    const float inv_in = a.inv_std[ccl], bc = pre_beta(a.act, a.beta, ccl);
+    const float inv = a.inv_std[ccl], bc = pre_beta(a.act, a.beta, ccl);
     // every load first (unconditional, clamped addresses), then the arithmetic: see dense_bn_bwd_small_kernel
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const int i = ty + 4 * k;
         const int ic = i < a.B ? i : a.B - 1;
-        dy[k] = a.dH[(long)ic * a.ldd + ccl];
+        dh[k] = a.dH[(long)ic * a.ldd + ccl];
         ha[k] = a.Hact[(long)ic * a.ldh + ccl];
         xh[k] = a.xhat[(long)ic * a.ldx + ccl];
     }
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        const bool ok = cv && ty + 4 * k < a.B;
-        dy[k] = ok ? dy[k] * act_slope(a.act, ha[k], xh[k], bc) : 0.f;
-        xh[k] = ok ? xh[k] : 0.f;
-        s1 += dy[k]; s2 += dy[k] * xh[k];
-    }
+    tile_dy_sums(dy, xh, cv, a.B, ty, [&](int k) { return dh[k] * act_slope(a.act, ha[k], xh[k], bc); }, s1, s2);
     const float t1 = wg_rowlane_sum(s1, sm);
     const float t2 = wg_rowlane_sum(s2, sm);
     if (!cv) return;
     if (ty == 0 && a.dbeta) a.dbeta[c] = t1;
-    const float m1 = t1 / a.n_total, m2 = t2 / a.n_total, inv = inv_in;
+    const float m1 = t1 / a.n_total, m2 = t2 / a.n_total;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const int i = ty + 4 * k;
-        if (i < a.B) a.dZ[(long)i * a.ldz + c] = inv * (dy[k] - m1 - xh[k] * m2);
+        if (i < a.B) a.dZ[(long)i * a.ldz + c] = bn_dz(inv, dy[k], xh[k], m1, m2);
     }
 }
 
@@ -572,15 +669,7 @@ __global__ __launch_bounds__(256) void dense_bn_small_kernel(DenseSmallArgs a) {
 #pragma unroll
     for (int k = 0; k < RPT; ++k) z[k] = b;
     __syncthreads();
-#pragma unroll 1
-    for (int kk = 0; kk < K4; kk += 4) {
-        const float w0 = Ws[kk][tx], w1 = Ws[kk + 1][tx], w2 = Ws[kk + 2][tx], w3 = Ws[kk + 3][tx];
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const float4 hv = *reinterpret_cast<const float4*>(&Hs[ty + 4 * k][kk]);      // rows beyond B: finite garbage, never stored
-            z[k] = fmaf(hv.w, w3, fmaf(hv.z, w2, fmaf(hv.y, w1, fmaf(hv.x, w0, z[k]))));
-        }
-    }
+    tile_fwd<RPT, 64, kSmallK + 4, 1>(z, &Ws[0][0], &Hs[0][0], K4, tx, ty);
     if (a.Z && cv) {
 #pragma unroll
         for (int k = 0; k < RPT; ++k) { const int i = ty + 4 * k; if (i < a.B) a.Z[(long)i * a.ldz + c] = z[k]; }
@@ -592,39 +681,32 @@ __global__ __launch_bounds__(256) void dense_bn_small_kernel(DenseSmallArgs a) {
         }
         return;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) s += (ty + 4 * k < a.B) ? z[k] : 0.f;
-    const float mean = wg_rowlane_sum(s, sm) / (float)a.B;
-    float q2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) { const float d = z[k] - mean; q2 += (ty + 4 * k < a.B) ? d * d : 0.f; }
-    const float m2 = wg_rowlane_sum(q2, sm);
+    float mean, m2;
+    tile_col_stats(z, cv, a.B, ty, sm, mean, m2);
     if (!cv) return;
-    const float var = (float)((double)m2 / (double)a.B);
-    const float inv = 1.f / sqrtf(var + a.eps);
+    const float var = bn_var((double)m2, (double)a.B);
+    const float inv = bn_inv_std(var, a.eps);
     if (ty == 0) {
-        a.mm[c] = mm_in - (mm_in - mean) * (1.f - a.momentum);
-        a.mv[c] = mv_in - (mv_in - var) * (1.f - a.momentum);
+        a.mm[c] = bn_moving(mm_in, mean, a.momentum);
+        a.mv[c] = bn_moving(mv_in, var, a.momentum);
         if (a.inv_std) a.inv_std[c] = inv;
     }
-    const float beta = beta_in;
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const int i = ty + 4 * k;
         if (i < a.B) {
-            const float xh = (z[k] - mean) * inv;
+            const float xh = bn_xhat(z[k], mean, inv);
             if (a.xhat) a.xhat[(long)i * a.ldx + c] = xh;
-            a.Hout[(long)i * a.ldh + c] = act_fwd(a.act, xh + beta);
+            a.Hout[(long)i * a.ldh + c] = act_fwd(a.act, xh + beta_in);
         }
     }
 }
 
 // ---- small batches: the hidden stack behind the first layer's product in ONE launch -------------------------------
 // [batch norm + activation of layer 0] -> [Dense + batch norm + activation] x (n - 1), one workgroup, stage after
-// stage (every layer at most 64 units wide: the reference's 64-32-64).  The stages are the formulas of
-// bn_relu_small_kernel / dense_bn_small_kernel; what is saved is two launches and their gaps on a step that is bound
-// by exactly those (12 -> 10 launches at batch 32).
+// stage (every layer at most 64 units wide: the reference's 64-32-64).  The stages are the shared tile pieces that
+// bn_relu_small_kernel / dense_bn_small_kernel run one layer at a time; what is saved is two launches and their gaps
+// on a step that is bound by exactly those (12 -> 10 launches at batch 32).
 constexpr int kChainMax = 4;
 
 struct SmallLayer {                     // = dcahip_small_layer (include/dcahip.h)
@@ -726,16 +808,7 @@ __global__ __launch_bounds__(256) void hidden_small_chain_kernel(SmallChainArgs 
             const float b = cv ? Ps[st][0][tx] : 0.f;
 #pragma unroll
             for (int k = 0; k < RPT; ++k) z[k] = b;
-            const float (*Wc)[64] = Ws[st & 1];
-#pragma unroll 1
-            for (int kk = 0; kk < K4; kk += 4) {
-                const float w0 = Wc[kk][tx], w1 = Wc[kk + 1][tx], w2 = Wc[kk + 2][tx], w3 = Wc[kk + 3][tx];
-#pragma unroll
-                for (int k = 0; k < RPT; ++k) {
-                    const float4 hv = *reinterpret_cast<const float4*>(&Hs[ty + 4 * k][kk]);      // rows beyond B: never stored
-                    z[k] = fmaf(hv.w, w3, fmaf(hv.z, w2, fmaf(hv.y, w1, fmaf(hv.x, w0, z[k]))));
-                }
-            }
+            tile_fwd<RPT, 64, kSmallK + 4, 1>(z, &Ws[st & 1][0][0], &Hs[0][0], K4, tx, ty);
             if (L.Z && cv) {
 #pragma unroll
                 for (int k = 0; k < RPT; ++k) { const int i = ty + 4 * k; if (i < a.B) L.Z[(long)i * L.ldz + c] = z[k]; }
@@ -750,25 +823,19 @@ __global__ __launch_bounds__(256) void hidden_small_chain_kernel(SmallChainArgs 
             for (int k = 0; k < RPT; ++k) hout[k] = act_fwd(a.act, z[k]);
             __syncthreads();            // every thread is done reading Hs and Ws[st & 1]
         } else {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < RPT; ++k) s += (cv && ty + 4 * k < a.B) ? z[k] : 0.f;
-            const float mean = wg_rowlane_sum(s, sm) / (float)a.B;
-            float q2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < RPT; ++k) { const float d = z[k] - mean; q2 += (cv && ty + 4 * k < a.B) ? d * d : 0.f; }
-            const float m2 = wg_rowlane_sum(q2, sm);
-            const float var = (float)((double)m2 / (double)a.B);             // biased variance
-            const float inv = 1.f / sqrtf(var + a.eps);
+            float mean, m2;
+            tile_col_stats(z, cv, a.B, ty, sm, mean, m2);
+            const float var = bn_var((double)m2, (double)a.B);
+            const float inv = bn_inv_std(var, a.eps);
             if (cv && ty == 0) {
-                L.mm[c] = mm_in - (mm_in - mean) * (1.f - a.momentum);
-                L.mv[c] = mv_in - (mv_in - var) * (1.f - a.momentum);
+                L.mm[c] = bn_moving(mm_in, mean, a.momentum);
+                L.mv[c] = bn_moving(mv_in, var, a.momentum);
                 if (L.inv_std) L.inv_std[c] = inv;
             }
 #pragma unroll
             for (int k = 0; k < RPT; ++k) {
                 const int i = ty + 4 * k;
-                const float xh = (z[k] - mean) * inv;
+                const float xh = bn_xhat(z[k], mean, inv);
                 if (cv && i < a.B && L.xhat) L.xhat[(long)i * L.ldx + c] = xh;
                 hout[k] = act_fwd(a.act, xh + beta_in);
             }
@@ -821,7 +888,7 @@ __global__ __launch_bounds__(256) void dense_bn_bwd_small_kernel(DenseSmallBwdAr
     {
         const int c = tx;
         const bool cv = c < a.H;
-        float dy[RPT], xh[RPT], ha[RPT];
+        float dh[RPT], dy[RPT], xh[RPT], ha[RPT];
         float s1 = 0.f, s2 = 0.f;
         const float bc = a.batchnorm ? pre_beta(a.act, a.beta, cv ? c : a.H - 1) : 0.f;
         // every load first (unconditional, clamped addresses): the activation derivative below may branch, and a branch
@@ -830,18 +897,14 @@ __global__ __launch_bounds__(256) void dense_bn_bwd_small_kernel(DenseSmallBwdAr
         for (int k = 0; k < RPT; ++k) {
             const int i = ty + 4 * k;
             const int ic = i < a.B ? i : a.B - 1, ccl = cv ? c : a.H - 1;
-            dy[k] = a.dH[(long)ic * a.ldd + ccl];
+            dh[k] = a.dH[(long)ic * a.ldd + ccl];
             ha[k] = a.Hact[(long)ic * a.ldh + ccl];
             xh[k] = a.batchnorm ? a.xhat[(long)ic * a.ldx + ccl] : 0.f;
         }
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const bool ok = cv && ty + 4 * k < a.B;
-            // (without batch norm the Hact operand of codes >= kActPre is the pre-activation Z: act_grad reads it as x)
-            dy[k] = ok ? dy[k] * (a.batchnorm ? act_slope(a.act, ha[k], xh[k], bc) : act_grad(a.act, ha[k])) : 0.f;
-            xh[k] = ok ? xh[k] : 0.f;
-            s1 += dy[k]; s2 += dy[k] * xh[k];
-        }
+        // (without batch norm the Hact operand of codes >= kActPre is the pre-activation Z: act_grad reads it as x)
+        tile_dy_sums(dy, xh, cv, a.B, ty, [&](int k) {
+            return dh[k] * (a.batchnorm ? act_slope(a.act, ha[k], xh[k], bc) : act_grad(a.act, ha[k]));
+        }, s1, s2);
         float m1 = 0.f, m2 = 0.f, inv = 1.f;
         if (a.batchnorm) {
             const float t1 = wg_rowlane_sum(s1, sm);
@@ -852,7 +915,7 @@ __global__ __launch_bounds__(256) void dense_bn_bwd_small_kernel(DenseSmallBwdAr
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
             const int i = ty + 4 * k;
-            if (i < a.B) dZs[i][c] = cv ? (a.batchnorm ? inv * (dy[k] - m1 - xh[k] * m2) : dy[k]) : 0.f;
+            if (i < a.B) dZs[i][c] = cv ? (a.batchnorm ? bn_dz(inv, dy[k], xh[k], m1, m2) : dy[k]) : 0.f;
         }
     }
     __syncthreads();
@@ -1065,7 +1128,8 @@ __global__ __launch_bounds__(256) void transpose64_kernel(const float* __restric
 // barriers (an arrival counter polled with agent-scope loads, release before / acquire after: the forms
 // MI355X_MICROARCH.md lists as valid).  Every workgroup must be resident at once: at most 256 of them, launched on an
 // otherwise idle device (the stream order of the training step guarantees it); every spin is bounded.
-// Same formulas, same merge (merge_entries_wg) and same summation structure as the per-operation kernels above.
+// Same merge (merge_entries_wg) and same summation structure as the per-operation kernels above; the per-element
+// formulas are the bn_* pieces.
 // =====================================================================================================
 constexpr int kStackMaxLayers = 8;
 constexpr int kStackRows = 64;          // most rows a workgroup owns
@@ -1228,18 +1292,18 @@ __global__ __launch_bounds__(256) void hidden_stack_fwd_kernel(StackFwdArgs a) {
         double n_, m_, m2_;
         stack_merge(part, nwg, H, c, a.B, smd, n_, m_, m2_);
         const float mean = (float)m_;
-        const float var = (float)(m2_ / n_);
-        const float inv = 1.f / sqrtf(var + a.eps);
+        const float var = bn_var(m2_, n_);
+        const float inv = bn_inv_std(var, a.eps);
         if (wg == 0 && ty == 0 && c < H) {
-            L.mm[c] = L.mm[c] - (L.mm[c] - mean) * (1.f - a.momentum);
-            L.mv[c] = L.mv[c] - (L.mv[c] - var) * (1.f - a.momentum);
+            L.mm[c] = bn_moving(L.mm[c], mean, a.momentum);
+            L.mv[c] = bn_moving(L.mv[c], var, a.momentum);
             if (L.inv_std) L.inv_std[c] = inv;
         }
         // ---- normalise + activation of the block's rows
         if (c < H) {
             const float beta = L.beta ? L.beta[c] : 0.f;
             for (int r = ty; r < nrows; r += 4) {
-                const float xh = (zt[r * kStackLd + c] - mean) * inv;
+                const float xh = bn_xhat(zt[r * kStackLd + c], mean, inv);
                 const float h = act_fwd(a.act, xh + beta);
                 if (L.xhat) L.xhat[(long)(r0 + r) * L.ldx + c] = xh;
                 L.Hout[(long)(r0 + r) * L.ldh + c] = h;
@@ -1369,7 +1433,7 @@ __global__ __launch_bounds__(256) void hidden_stack_bwd_kernel(StackBwdArgs a) {
         if (c < H) {
             const float m1 = v1 / a.n_total, m2 = v2 / a.n_total, inv = L.inv_std[c];
             for (int r = ty; r < nrows; r += 4) {
-                const float dz = inv * (dyt[r * kStackLd + c] - m1 - xt[r * kStackLd + c] * m2);
+                const float dz = bn_dz(inv, dyt[r * kStackLd + c], xt[r * kStackLd + c], m1, m2);
                 dyt[r * kStackLd + c] = dz;
                 if (i == 0) a.dZ0[(long)(r0 + r) * a.ldz0 + c] = dz;
             }
@@ -1608,11 +1672,11 @@ __global__ __launch_bounds__(256) void stack_fwd_step_kernel(StepFwdArgs a) {
         const float mean = (float)meand;
         double m2 = sq - n * meand * meand;
         if (m2 < 0.0) m2 = 0.0;
-        const float var = n > 0.0 ? (float)(m2 / n) : 0.f;
-        const float inv = 1.f / sqrtf(var + a.eps);
+        const float var = n > 0.0 ? bn_var(m2, n) : 0.f;
+        const float inv = bn_inv_std(var, a.eps);
         if (wg == 0 && ty == 0 && c < H) {
-            L.mm[c] = L.mm[c] - (L.mm[c] - mean) * (1.f - a.momentum);
-            L.mv[c] = L.mv[c] - (L.mv[c] - var) * (1.f - a.momentum);
+            L.mm[c] = bn_moving(L.mm[c], mean, a.momentum);
+            L.mv[c] = bn_moving(L.mv[c], var, a.momentum);
             if (L.inv_std) L.inv_std[c] = inv;
         }
         // ---- normalise + activation; kernel and activations -> LDS
@@ -1621,7 +1685,7 @@ __global__ __launch_bounds__(256) void stack_fwd_step_kernel(StepFwdArgs a) {
             const int r = ty + 4 * j;
             float h = 0.f;
             if (r < nrows && c < H) {
-                const float xh = (z[j] - mean) * inv;
+                const float xh = bn_xhat(z[j], mean, inv);
                 h = act_fwd(a.act, xh + beta);
                 if (L.xhat) L.xhat[(long)(r0 + r) * L.ldx + c] = xh;
                 L.Hout[(long)(r0 + r) * L.ldh + c] = h;
@@ -1634,16 +1698,7 @@ __global__ __launch_bounds__(256) void stack_fwd_step_kernel(StepFwdArgs a) {
         float acc[kStepRows / 4];
 #pragma unroll
         for (int j = 0; j < kStepRows / 4; ++j) acc[j] = 0.f;
-        const int K4 = (K + 3) & ~3;
-        for (int k = 0; k < K4; k += 4) {
-            const float w0 = wl[(k + 0) * kStackLd + c], w1 = wl[(k + 1) * kStackLd + c];
-            const float w2 = wl[(k + 2) * kStackLd + c], w3 = wl[(k + 3) * kStackLd + c];
-#pragma unroll
-            for (int j = 0; j < kStepRows / 4; ++j) {
-                const float4 h4 = *reinterpret_cast<const float4*>(ht + (ty + 4 * j) * kStackLd + k);
-                acc[j] = fmaf(h4.w, w3, fmaf(h4.z, w2, fmaf(h4.y, w1, fmaf(h4.x, w0, acc[j]))));
-            }
-        }
+        tile_fwd<kStepRows / 4, kStackLd, kStackLd, 0>(acc, wl, ht, (K + 3) & ~3, tx, ty);
         Hs = HN;
 #pragma unroll
         for (int j = 0; j < kStepRows / 4; ++j) {
@@ -1707,11 +1762,7 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
     const float bc = pre_beta(a.act, L.beta, cc);
     if (a.sums_only) {
         float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < kStepRows / 4; ++j) {
-            const float d = (ty + 4 * j < nrows && c < H) ? dh[j] * act_slope(a.act, hv[j], xv[j], bc) : 0.f;
-            s1 += d; s2 += d * xv[j];
-        }
+        tile_dy_sums(dy, xv, c < H, nrows, ty, [&](int j) { return dh[j] * act_slope(a.act, hv[j], xv[j], bc); }, s1, s2);
         const float t1 = wg_rowlane_sum(s1, smf), t2 = wg_rowlane_sum(s2, smf);
         if (c < H && ty == 0) { a.part_out[((long)wg * 2 + 0) * H + c] = t1; a.part_out[((long)wg * 2 + 1) * H + c] = t2; }
         return;
@@ -1761,7 +1812,7 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
         const int r = ty + 4 * j;
         float dz = 0.f;
         if (r < nrows && c < H) {
-            dz = inv * (dh[j] * act_slope(a.act, hv[j], xv[j], bc) - m1 - xv[j] * m2);
+            dz = bn_dz(inv, dh[j] * act_slope(a.act, hv[j], xv[j], bc), xv[j], m1, m2);
             if (!has_low) a.dZ0[(long)(r0 + r) * a.ldz0 + c] = dz;
         }
         dyt[r * kStackLd + c] = dz;
@@ -1787,17 +1838,7 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[j] = 0.f;
         float bs = 0.f;
-#pragma unroll 2
-        for (int r = 0; r < nrows; ++r) {
-            const float d = dyt[r * kStackLd + c];
-            bs += d;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const float4 h4 = *reinterpret_cast<const float4*>(ht + r * kStackLd + 16 * ty + 4 * q4);
-                acc[4 * q4 + 0] = fmaf(h4.x, d, acc[4 * q4 + 0]); acc[4 * q4 + 1] = fmaf(h4.y, d, acc[4 * q4 + 1]);
-                acc[4 * q4 + 2] = fmaf(h4.z, d, acc[4 * q4 + 2]); acc[4 * q4 + 3] = fmaf(h4.w, d, acc[4 * q4 + 3]);
-            }
-        }
+        tile_dw<kStackLd, 2>(acc, bs, dyt, ht, nrows, tx, ty);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int k = 16 * ty + j;
@@ -1809,15 +1850,7 @@ __global__ __launch_bounds__(256) void stack_bwd_step_kernel(StepBwdArgs a) {
     float acc[kStepRows / 4];
 #pragma unroll
     for (int j = 0; j < kStepRows / 4; ++j) acc[j] = 0.f;
-#pragma unroll 2
-    for (int c4 = 0; c4 < 64; c4 += 4) {
-        const float4 w4 = *reinterpret_cast<const float4*>(wl + tx * kStackLd + c4);
-#pragma unroll
-        for (int j = 0; j < kStepRows / 4; ++j) {
-            const float4 d4 = *reinterpret_cast<const float4*>(dyt + (ty + 4 * j) * kStackLd + c4);
-            acc[j] = fmaf(d4.w, w4.w, fmaf(d4.z, w4.z, fmaf(d4.y, w4.y, fmaf(d4.x, w4.x, acc[j]))));
-        }
-    }
+    tile_dhp<kStepRows / 4, kStackLd, 2>(acc, wl, dyt, tx, ty);
     // the layer below (k = its column): dH handed on through memory, dy and its block sums
     const StackBwdLayer& P = a.low;
     const float pbc = pre_beta(a.act, P.beta, tx < K ? tx : (K > 0 ? K - 1 : 0));
@@ -1905,7 +1938,7 @@ __global__ __launch_bounds__(256) void stack_bwd_chain_kernel(ChainBwdArgs a) {
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const int r = ty + 4 * j;
-            const float dz = (r < nrows && c < H) ? inv[i] * (dy[j] - m1 - xv[i][j] * m2) : 0.f;
+            const float dz = (r < nrows && c < H) ? bn_dz(inv[i], dy[j], xv[i][j], m1, m2) : 0.f;
             if (i == 0 && r < nrows && c < H) a.dZ0[(long)r * a.ldz0 + c] = dz;
             dyt[r * kStackLd + c] = dz;
             if (i > 0) ht[r * kStackLd + tx] = (r < nrows && tx < K) ? hv[i > 0 ? i - 1 : 0][j] : 0.f;
@@ -1919,17 +1952,7 @@ __global__ __launch_bounds__(256) void stack_bwd_chain_kernel(ChainBwdArgs a) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) acc[j] = 0.f;
             float bs = 0.f;
-#pragma unroll 4
-            for (int r = 0; r < nrows; ++r) {
-                const float d = dyt[r * kStackLd + c];
-                bs += d;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const float4 h4 = *reinterpret_cast<const float4*>(ht + r * kStackLd + 16 * ty + 4 * q4);
-                    acc[4 * q4 + 0] = fmaf(h4.x, d, acc[4 * q4 + 0]); acc[4 * q4 + 1] = fmaf(h4.y, d, acc[4 * q4 + 1]);
-                    acc[4 * q4 + 2] = fmaf(h4.z, d, acc[4 * q4 + 2]); acc[4 * q4 + 3] = fmaf(h4.w, d, acc[4 * q4 + 3]);
-                }
-            }
+            tile_dw<kStackLd, 4>(acc, bs, dyt, ht, nrows, tx, ty);
             if (c < H) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
@@ -1943,15 +1966,7 @@ __global__ __launch_bounds__(256) void stack_bwd_chain_kernel(ChainBwdArgs a) {
         // the element layout of the layer below, so it never leaves the registers
 #pragma unroll
         for (int j = 0; j < R; ++j) dh[j] = 0.f;
-#pragma unroll 4
-        for (int c4 = 0; c4 < 64; c4 += 4) {
-            const float4 w4 = *reinterpret_cast<const float4*>(wl + tx * kStackLd + c4);
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const float4 d4 = *reinterpret_cast<const float4*>(dyt + (ty + 4 * j) * kStackLd + c4);
-                dh[j] = fmaf(d4.w, w4.w, fmaf(d4.z, w4.z, fmaf(d4.y, w4.y, fmaf(d4.x, w4.x, dh[j]))));
-            }
-        }
+        tile_dhp<R, kStackLd, 4>(dh, wl, dyt, tx, ty);
         const StackBwdLayer& P = a.l[i > 0 ? i - 1 : 0];
         if (P.dHin) {
 #pragma unroll
