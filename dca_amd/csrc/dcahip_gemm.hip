@@ -1345,6 +1345,41 @@ Plan make_plan(int M, int N, int K, int split_k) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Everything dcahip_sgemm decides on the host: the tile and split (make_plan), the arithmetic and the loader width.  The one
+// definition behind both the launch and the query dcahip_sgemm_plan.
+struct SgemmPlan {
+    Plan p;
+    bool exact, vec;
+};
+
+inline bool sgemm_args_ok(int ta, int tb, int M, int N, int K, const float* A, const float* B, int colsum_row) {
+    if (M <= 0 || N <= 0 || K <= 0 || !A || !B) return false;
+    if (ta && tb) return false;
+    if (colsum_row && tb) return false;                  // the column sums are taken where B is stored [K, N]
+    return true;
+}
+
+SgemmPlan sgemm_plan(int ta, int tb, int M, int N, int K, int split_k, const float* A, long lda, const float* B, long ldb) {
+    SgemmPlan sp;
+    sp.p = make_plan(M, N, K, split_k);
+    // 16-byte vector loads need aligned bases and leading dimensions
+    sp.vec = al16(A) && al16(B) && (lda % 4 == 0) && (ldb % 4 == 0);
+    // Which arithmetic (a pure function of the layout and the shape; results of both are fp32-accurate):
+    //   NT (both operands k-contiguous: direct 16-byte LDS operand reads)       split-bf16, measured 1.35x - 2.1x faster
+    //   NN with >= 128 columns (B through the transposing read)                 split-bf16, 1.07x - 1.13x
+    //   NN with fewer columns, TN                                               exact fp32 MFMA (the split kernel's larger LDS
+    //       images cost more occupancy than the shorter matrix phase returns on these latency-bound shapes: 0.158 vs 0.157 ms
+    //       and 0.195 vs 0.150 ms on the first layer at B = 4096; profiles/r02e_gemm_ab.txt)
+    sp.exact = split_k < 0 || ta || (!tb && N < 128);
+    return sp;
+}
+
+// lanes of splitk_reduce_kernel per output (include/dcahip.h states the rule): 0 = no reduce launch
+inline int reduce_lanes(int split, long outputs) {
+    if (split <= 1) return 0;
+    return split >= 16 && outputs <= 65536 ? 16 : 1;
+}
+
 template <int BM, int BN, int WGM, int WGN>
 int launch_cfg(const GemmArgs& a, int ta, int tb, bool vec, int grid, hipStream_t s, bool exact) {
 #define DCA_L(TA, TB, V) do { if (exact) hipLaunchKernelGGL((gemm_kernel<BM, BN, kBK, WGM, WGN, TA, TB, V>), dim3(grid), dim3(256), 0, s, a); \
@@ -1372,26 +1407,17 @@ extern "C" int dcahip_sgemm(int ta, int tb, int M, int N, int K, const float* A,
                             const float* B, long ldb, float* C, long ldc, const float* bias,
                             const int* perm, const long long* cursor, int colsum_row, int split_k,
                             void* workspace, long workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return DCAHIP_EINVAL;
-    if (ta && tb) return DCAHIP_EINVAL;
-    if (colsum_row && tb) return DCAHIP_EINVAL;          // the column sums are taken where B is stored [K, N]
-    const Plan p = make_plan(M, N, K, split_k);
+    if (!sgemm_args_ok(ta, tb, M, N, K, A, B, colsum_row) || !C) return DCAHIP_EINVAL;
+    const SgemmPlan sp = sgemm_plan(ta, tb, M, N, K, split_k, A, lda, B, ldb);
+    const Plan& p = sp.p;
+    const bool vec = sp.vec, exact = sp.exact;
     const long need = dcahip_sgemm_workspace_bytes(ta, tb, M, N, K, colsum_row, split_k);
     if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
-    // 16-byte vector loads need aligned bases and leading dimensions
-    const bool vec = al16(A) && al16(B) && (lda % 4 == 0) && (ldb % 4 == 0);
     GemmArgs a{A, B, C, bias, perm, cursor, static_cast<float*>(workspace), lda, ldb, ldc,
                M, N, K, p.split, p.kslab, colsum_row, p.mtiles, p.ntiles};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = p.mtiles * p.ntiles * p.split;
     int rc;
-    // Which arithmetic (a pure function of the layout and the shape; results of both are fp32-accurate):
-    //   NT (both operands k-contiguous: direct 16-byte LDS operand reads)       split-bf16, measured 1.35x - 2.1x faster
-    //   NN with >= 128 columns (B through the transposing read)                 split-bf16, 1.07x - 1.13x
-    //   NN with fewer columns, TN                                               exact fp32 MFMA (the split kernel's larger LDS
-    //       images cost more occupancy than the shorter matrix phase returns on these latency-bound shapes: 0.158 vs 0.157 ms
-    //       and 0.195 vs 0.150 ms on the first layer at B = 4096; profiles/r02e_gemm_ab.txt)
-    const bool exact = split_k < 0 || ta || (!tb && N < 128);
     if (p.cfg == 0) rc = launch_cfg<128, 64, 4, 1>(a, ta, tb, vec, grid, s, exact);
     else if (p.cfg == 1) rc = launch_cfg<64, 128, 1, 4>(a, ta, tb, vec, grid, s, exact);
     else if (p.cfg == 3) rc = launch_cfg<64, 64, 2, 2>(a, ta, tb, vec, grid, s, exact);
@@ -1402,7 +1428,7 @@ extern "C" int dcahip_sgemm(int ta, int tb, int M, int N, int K, const float* A,
         const long total = (long)Mo * N;
         long g = (total + 255) / 256;
         if (g > 4096) g = 4096;
-        if (p.split >= 16 && total <= 65536) {
+        if (reduce_lanes(p.split, total) == 16) {
             long g16 = (total + 15) / 16;
             if (g16 > 4096) g16 = 4096;
             hipLaunchKernelGGL(splitk_reduce_kernel<16>, dim3((int)g16), dim3(256), 0, s, a.ws, p.split, Mo, N,
@@ -1414,6 +1440,15 @@ extern "C" int dcahip_sgemm(int ta, int tb, int M, int N, int K, const float* A,
         rc = (int)hipGetLastError();
     }
     return rc;
+}
+
+extern "C" int dcahip_sgemm_plan(int ta, int tb, int M, int N, int K, int colsum_row, int split_k,
+                                 const float* A, long lda, const float* B, long ldb, int out[8]) {
+    if (!sgemm_args_ok(ta, tb, M, N, K, A, B, colsum_row) || !out) return DCAHIP_EINVAL;
+    const SgemmPlan sp = sgemm_plan(ta, tb, M, N, K, split_k, A, lda, B, ldb);
+    out[0] = sp.p.BM; out[1] = sp.p.BN; out[2] = sp.p.mtiles; out[3] = sp.p.ntiles;
+    out[4] = sp.p.split; out[5] = sp.p.kslab; out[6] = sp.exact ? 0 : 1; out[7] = sp.vec ? 4 : 1;
+    return 0;
 }
 
 

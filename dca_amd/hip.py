@@ -58,7 +58,9 @@ _POINTEES = set(_SCALARS) | {'void', 'unsigned', 'unsigned char'}
 
 
 def _ctype(param):
-    """ctypes type of one parameter of a declaration ('long ldh', 'const float* beta', 'unsigned* const* flags')."""
+    """ctypes type of one parameter of a declaration ('long ldh', 'const float* beta', 'unsigned* const* flags',
+    'int out[8]': an array parameter is a pointer)."""
+    param = re.sub(r'^(.*\S)\s+(\w+)\s*\[\s*\d*\s*\]$', r'\1* \2', param)
     words = param.replace('*', ' * ').split()
     if '*' in words:
         base = ' '.join(w for w in words[:words.index('*')] if w != 'const')

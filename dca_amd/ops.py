@@ -172,6 +172,22 @@ class HipOps:
                                       p(bias), p(perm), p(cursor), int(colsum_row), split_k, p(ws),
                                       wsb, hip.stream()), 'sgemm')
 
+    def sgemm_plan(self, ta, tb, M, N, K, A, lda, B, ldb, colsum_row=False, split_k=0):
+        """What sgemm would launch for these arguments (nothing is launched; A and B give their alignment only): the tuple
+        (tile rows, tile columns, m tiles, n tiles, split, k slab, arithmetic 0 exact / 1 three bf16 pieces, loader width 4 / 1)."""
+        out = (ctypes.c_int * 8)()
+        hip.check(self.L.dcahip_sgemm_plan(int(ta), int(tb), M, N, K, int(colsum_row), split_k, hip.ptr(A), lda,
+                                           hip.ptr(B), ldb, ctypes.addressof(out)), 'sgemm_plan')
+        return tuple(out)
+
+    @staticmethod
+    def sgemm_reduce_lanes(split, outputs):
+        """Lanes per output of the reduce behind a split product of `outputs` = (M + colsum_row) * N elements, as
+        include/dcahip.h states the rule under dcahip_sgemm_plan: 0 (no reduce launch), 1 or 16."""
+        if split <= 1:
+            return 0
+        return 16 if split >= 16 and outputs <= 65536 else 1
+
     # ------------------------------------------------------------------ products from pre-split operands
     def planes_alloc(self, rows, cols, device):
         """Three bf16 planes [3, rows, r8(cols)] (zeros)."""

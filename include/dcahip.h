@@ -254,6 +254,21 @@ int dcahip_sgemm(int ta, int tb, int M, int N, int K,
                  int colsum_row, int split_k, void* workspace, long workspace_bytes,
                  void* stream);
 long dcahip_sgemm_workspace_bytes(int ta, int tb, int M, int N, int K, int colsum_row, int split_k);
+/* What dcahip_sgemm would launch for these arguments, exposed for testing (as dcahip_x3_product_32x32 is): nothing is
+ * launched, A and B are looked at for their 16-byte alignment only and never dereferenced.  dcahip_sgemm takes its tile, its
+ * arithmetic and its loader width from the function that fills `out`, so the answer cannot differ from the launch.
+ *   out[0], out[1] : tile rows, tile columns (128x64, 64x128, 128x128 or 64x64)
+ *   out[2], out[3] : tiles along M, along N
+ *   out[4], out[5] : K splits (1 = none; empty trailing splits are dropped), K elements per split
+ *   out[6]         : arithmetic, 0 = exact fp32 MFMA, 1 = three bf16 pieces (the contract above)
+ *   out[7]         : floats per load of the tile loaders: 4 (16-byte loads: A and B 16-byte aligned, lda and ldb multiples
+ *                    of 4) or 1
+ * The ending follows from out[4] and the outputs (M + (colsum_row ? 1 : 0)) * N: no reduce launch for out[4] == 1; else one
+ * ordered reduce, 16 lanes per output when out[4] >= 16 and there are at most 65536 outputs, one lane per output otherwise.
+ * DCAHIP_EINVAL wherever dcahip_sgemm returns it for the same arguments (non-positive sizes, NULL A or B, ta && tb,
+ * colsum_row && tb), and for a NULL out. */
+int dcahip_sgemm_plan(int ta, int tb, int M, int N, int K, int colsum_row, int split_k,
+                      const float* A, long lda, const float* B, long ldb, int out[8]);
 /*
  * The same products from PRE-SPLIT operands.  "Planes" = the three bf16 pieces of a matrix as three images
  * [3][rows][ld] of bf16 (ld % 8 == 0; plane_stride elements from one piece to the next): x = p0 + p1 + p2 to 2^-24 |x|,

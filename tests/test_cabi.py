@@ -44,6 +44,8 @@ def test_binding_table_is_derived_from_the_header():
                                                                     c.c_long, vp])
     assert hip._SIGNATURES['dcahip_sgemm_workspace_bytes'] == (c.c_long, [c.c_int] * 7)
     assert hip._SIGNATURES['dcahip_version'] == (c.c_int, [])
+    # an array parameter (`int out[8]`) is a pointer
+    assert hip._SIGNATURES['dcahip_sgemm_plan'] == (c.c_int, [c.c_int] * 7 + [vp, c.c_long, vp, c.c_long, vp])
     assert hip._parse_header('int dcahip_a(const unsigned long long* p, unsigned long long seed, double x, void* stream);') == {
         'dcahip_a': (c.c_int, [vp, c.c_ulonglong, c.c_double, vp])}
     for bad in ('int dcahip_made_up(const float* x, size_t n, void* stream);',         # a type without a ctypes counterpart

@@ -292,16 +292,16 @@ GEMM_SHAPES = [
     (0, 0, 32, 64, 1000, True, True, False, 0),      # enc0 fwd, B=32 (auto split-K)
     (0, 0, 200, 64, 517, True, True, False, 3),      # ragged K, forced split
     (0, 0, 32, 3000, 64, False, True, False, 0),     # heads fwd, small M (cfg 64x128)
-    (0, 0, 300, 1500, 64, False, True, False, 0),    # heads fwd, large M (cfg 128x128)
+    (0, 0, 300, 1500, 64, False, True, False, 0),    # heads fwd, large M (mid-size: cfg 64x64)
     (0, 0, 45, 6, 3, False, True, False, 0),         # tiny odd (biochemists-like)
     (1, 0, 64, 3000, 32, False, False, True, 0),     # dW heads + bias grad row
     (1, 0, 64, 700, 300, False, False, True, 2),     # dW heads, split-K with colsum row
     (1, 0, 1000, 64, 32, True, False, True, 0),      # dW0 with gathered K rows
     (1, 0, 333, 33, 130, True, False, True, 0),      # odd sizes (scalar tails)
-    (1, 0, 150, 200, 260, False, False, True, 0),    # cfg 128x128, TN
+    (1, 0, 150, 200, 260, False, False, True, 0),    # TN, mid-size: cfg 64x64
     (0, 1, 32, 64, 3000, False, False, False, 0),    # dH (NT), big K
     (0, 1, 130, 32, 64, False, False, False, 0),     # dH mid layer
-    (0, 1, 257, 190, 99, False, False, False, 0),    # cfg 128x128, NT, odd
+    (0, 1, 257, 190, 99, False, False, False, 0),    # NT, odd, mid-size: cfg 64x64
     (0, 0, 17, 5, 9, False, False, False, 0),        # unaligned ld -> scalar loads
     # skinny outputs over many rows (the first layer at throughput batches: the A-direct kernel), every layout
     (0, 0, 2100, 64, 300, True, True, False, 0),     # enc0 fwd, gathered rows, ragged M and K
