@@ -50,6 +50,9 @@
 //     dW and dH both only read the cells, so their order is free: dW comes first, and the workgroup's dH partial of the
 //     row tile (8 KB from beyond L2) is requested right after Z into the registers of the dH accumulators -- a whole
 //     matrix phase ahead of the products that start from it.
+//     A wave's row tiles are the same in every work item: what its first tile needs that does not depend on the gene
+//     tile (storage rows, size factors, exponent, first forward operands) is carried from item to item in registers, and
+//     an item's head is ONE batch of requests -- weight tile, biases, the count bytes of the first group.
 //     No workgroup barrier inside the loop: waves drift apart, one wave's element-wise phase runs beside
 //     its SIMD partner's matrix phases.
 //   * HBM traffic per element: y (1 B from the byte store) + the dH partial instead of 36 B for materialised
@@ -288,6 +291,23 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
     int eHmin = 1 << 20;
     for (int t = s_wg * WR + r; t < p.NT; t += p.S * WR) { const int e = p.eH[t]; eHmin = (e != kEHZero && e < eHmin) ? e : eHmin; }
     eHmin = __builtin_amdgcn_readfirstlane(eHmin == (1 << 20) ? 0 : eHmin);
+    // What a wave CARRIES from one work item to the next.  Its row tiles are the same in every item, and the tile loop
+    // requests "the next tile" one tile ahead -- for the last tile of an item that next tile is the wave's FIRST one, so
+    // every item ends holding what the next item's first tile needs that does not depend on the gene tile: the storage
+    // rows (lane l31: row l31 of the tile), their size factors, the tile's exponent and its first forward operands.  Only
+    // the first item of a wave requests them from memory (carried == false).  The protocol of the row table Rt / Sft:
+    //   * the table lies in the wave's staging slot, which the dW reduce of an item's end overwrites: nothing in LDS
+    //     survives an item.  The item head writes Rt[0 .. 31] from the carried srow_l, the tile loop starts at rb = 0
+    //     ("this tile" = half 0) whatever rb the last item ended with, and Sft is written from sf_l in front of the loop;
+    //   * inside the loop a tile writes Rt[rb ^ 1] (next tile's rows) at its top and Sft (next tile's factors) at its
+    //     end, then flips rb; the wave_sync() after the staging stores of F orders the top-of-tile write before the
+    //     dense pass reads that half, the wave_sync() at the end of the tile orders the Sft write before the next pass;
+    //   * the item head's own wave_sync() orders its Rt write before the read that forms the count addresses of group 0.
+    int srow_l = 0;
+    float sf_l = 1.f;
+    int eHt = 0;
+    u32x4 ha0[2] = {};
+    bool carried = false;
 #pragma unroll 1
     for (int j = 0; j < nrounds; ++j) {
     const int gb = j * p.npart + ((j & 1) ? p.npart - 1 - wq : wq);
@@ -314,6 +334,54 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
     int* const Rt = reinterpret_cast<int*>(lds + W_FLOATS + wave * PW_FLOATS + PW_FLOATS - ROWT);      // [2][32]
     float* const Sft = reinterpret_cast<float*>(Rt + 64);                                              // [32]
 
+    const int gene_c = gvalid ? gene : p.G - 1;
+    const float* const ycol = p.y + gene_c;
+    const unsigned char* const ycolc = p.yc + gene_c;
+    const unsigned ldy_u = YC ? (unsigned)p.ldc : (unsigned)p.ldy;
+    auto count_at = [&](int sr) -> YV {
+        if constexpr (YC) return (unsigned)ycolc[(unsigned long long)(unsigned)sr * ldy_u];
+        else return ycol[(unsigned long long)(unsigned)sr * ldy_u];
+    };
+    YV yA[kZU], yB[kZU];
+    auto row_clamped = [&](int tt) { const int rl = tt * kTR + l31; return rl < p.B ? rl : p.B - 1; };
+    auto load_srow = [&](int tt) { const int rlc = row_clamped(tt); return p.perm ? p.perm[cur + rlc] : (int)(cur + rlc); };
+    // split decoder output through buffer resources: (per-lane offset fixed for the whole kernel) + (tile offset
+    // in an SGPR) + immediate
+    const __amdgpu_buffer_rsrc_t ha_rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(p.HA), 0, p.NT * (kHTile * 2), 0x00020000);
+    const int ha_lane = l31 * 128 + hi * 64;       // row l31, this lane half's 32 hidden units (4 K steps x 8)
+    // forward A operands [piece] of one K step.  The lane offset is made opaque where it is used: the constants
+    // then stay immediates of the loads -- hoisted out of the tile loop, every (offset + constant) holds a register
+    // of its own through every phase.
+    auto load_ha = [&](int tt, int ks, u32x4 (&dst)[2]) {
+        const int so = tt * (kHTile * 2);
+        int ha_o = ha_lane;
+        asm volatile("" : "+v"(ha_o));
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+            dst[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ha_rs, ha_o + q * 4096 + ks * 16, so, 0));
+    };
+    // ---- the head of the item's first row tile (t0: the same tile in every item of the wave).  What does not depend on
+    // the gene tile is carried from the last item (see above the item loop); only a wave's first item requests it, here,
+    // AHEAD of the weight loads: storage rows and exponent, then size factors and forward operands.  The count bytes of
+    // the tile's first group depend on the gene tile: every item gathers them through the row table BEHIND the weight
+    // requests (item_head) -- straight-line code, so that the wait for the weights counts them as younger requests and
+    // leaves them in flight across the prologue's first barrier: they share the weight tile's round trip.
+    // (A wave without row tiles gathers the bytes of storage row 0 and never reads them.)
+    const int t0 = s * WR + r;
+    if (tile_ok && t0 < p.NT && !carried) {
+        srow_l = load_srow(t0);
+        eHt = p.eH[t0];
+        sf_l = p.sf[srow_l];
+        load_ha(t0, 0, ha0);
+    }
+    auto item_head = [&]() {
+        if (lane < 32) Rt[l31] = srow_l;
+        wave_sync();
+        const int4 r4 = *reinterpret_cast<const int4*>(Rt + 4 * hi);
+        yA[0] = count_at(r4.x); yA[1] = count_at(r4.y); yA[2] = count_at(r4.z); yA[3] = count_at(r4.w);
+    };
+
     // ---- head weights of this gene tile -> LDS as fp16 pieces scaled by 2^eW (eW from the tile's largest weight), image
     // [head][piece][k][32 genes], the four 16-byte units of a row rotated by (k >> 2): conflict-free for the direct
     // 16-byte reads of dH (lanes = rows k) and for the transposing reads of F (4 consecutive rows per lane group)
@@ -323,19 +391,30 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         constexpr int UNR = (NH * 64 * 8 + NTHREADS - 1) / NTHREADS;
         constexpr int ITEMS = NH * 64 * 8;
         float4 v[UNR];
+        // (the thread index is made opaque per item: the load offsets derived from it are then recomputed here -- as loop
+        // invariants of the item loop they are spilled, and a reload between the requests waits for every request in flight)
+        int tidp = tid;
+        asm volatile("" : "+v"(tidp));
         float m = 0.f;
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const int idx = tid + u * NTHREADS;
+            const int idx = tidp + u * NTHREADS;
             const int c4 = idx & 7, kq = (idx >> 3) & 63, h = (idx >> 9) < NH ? (idx >> 9) : NH - 1;
             const int kc = kq < p.hL ? kq : p.hL - 1;
             long gcol = g0 + c4 * 4;
             if (gcol > p.plane - 4) gcol = p.plane - 4;
             v[u] = *reinterpret_cast<const float4*>(p.Wh + (long)kc * p.ldw + (long)h * p.plane + gcol);
         }
+        // biases / log-dispersion of the lane's gene, requested with the weights (every wave: no branch in front of the
+        // gathers); wave 0 puts them into LDS behind the split
+        float bv[NH + 1];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) bv[h] = p.bh[(long)h * p.plane + gene_c];
+        bv[NH] = CONST_DISP ? p.theta_w[gene_c] : 0.f;
+        item_head();
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const int idx = tid + u * NTHREADS;
+            const int idx = tidp + u * NTHREADS;
             const int c4 = idx & 7, kq = (idx >> 3) & 63;
             const int gcol = g0 + c4 * 4;
             const bool kv = idx < ITEMS && kq < p.hL && gcol <= p.plane - 4;
@@ -353,7 +432,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         const float wsc = pow2i(eW);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const int idx = tid + u * NTHREADS;
+            const int idx = tidp + u * NTHREADS;
             if (idx >= ITEMS) continue;
             const int c4 = idx & 7, kq = (idx >> 3) & 63, h = idx >> 9;
             unsigned a0, a1, b0, b1;
@@ -363,11 +442,10 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             *reinterpret_cast<u32x2*>(Wimg + (h * 2 + 0) * W_PIECE + off) = u32x2{a0, b0};
             *reinterpret_cast<u32x2*>(Wimg + (h * 2 + 1) * W_PIECE + off) = u32x2{a1, b1};
         }
-        if (tid < 32) {
-            const bool gv = g0 + tid < p.G;
+        if (tid < 32) {                  // (wave 0, lane = l31: the lane's gene is g0 + tid)
 #pragma unroll
-            for (int h = 0; h < NH; ++h) Bs[h * 32 + tid] = gv ? p.bh[(long)h * p.plane + g0 + tid] : 0.f;
-            Bs[NH * 32 + tid] = (CONST_DISP && gv) ? p.theta_w[g0 + tid] : 0.f;
+            for (int h = 0; h < NH; ++h) Bs[h * 32 + tid] = gvalid ? bv[h] : 0.f;
+            Bs[NH * 32 + tid] = (CONST_DISP && gvalid) ? bv[NH] : 0.f;
         }
     }
     __syncthreads();
@@ -387,47 +465,18 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
     if (tile_ok) {
         // biases / log-dispersion of the lane's gene are read from LDS where they are used: three registers and --
         // more to the point -- no spill slot whose reload would wait for every global prefetch in flight
-        const int gene_c = gvalid ? gene : p.G - 1;
-        const float* const ycol = p.y + gene_c;
-        const unsigned char* const ycolc = p.yc + gene_c;
-        const unsigned ldy_u = YC ? (unsigned)p.ldc : (unsigned)p.ldy;
-        auto count_at = [&](int sr) -> YV {
-            if constexpr (YC) return (unsigned)ycolc[(unsigned long long)(unsigned)sr * ldy_u];
-            else return ycol[(unsigned long long)(unsigned)sr * ldy_u];
-        };
         const int tstep = p.S * WR;
-        int t = s * WR + r;
+        int t = t0;
         const long dh_tstride = (long)p.npart * (kTR * KT);
         float* const dh_part = p.ws_dh + (long)(blockIdx.x / p.S) * (kTR * KT);            // this workgroup's partials
         // the lane's 16-byte units of a dH partial: batch row of ROW POSITION l31 (bits 2 and 3 swapped), hidden units 4 hi ..
         const int dh_lane = ((((l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1)) * KT) + 4 * hi) * 4;
-        int srow_l = 0;
-        float sf_l = 1.f;
-        YV yA[kZU], yB[kZU];
-        auto row_clamped = [&](int tt) { const int rl = tt * kTR + l31; return rl < p.B ? rl : p.B - 1; };
-        auto load_srow = [&](int tt) { const int rlc = row_clamped(tt); return p.perm ? p.perm[cur + rlc] : (int)(cur + rlc); };
-        // split decoder output through buffer resources: (per-lane offset fixed for the whole kernel) + (tile offset
-        // in an SGPR) + immediate
-        const __amdgpu_buffer_rsrc_t ha_rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<unsigned short*>(p.HA), 0, p.NT * (kHTile * 2), 0x00020000);
         const __amdgpu_buffer_rsrc_t ht_rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<unsigned short*>(p.HT), 0, p.NT * (kHTile * 2), 0x00020000);
-        const int ha_lane = l31 * 128 + hi * 64;       // row l31, this lane half's 32 hidden units (4 K steps x 8)
         const int ht_lane = l31 * 64 + hi * 16;        // hidden unit l31 (+ 32 ib), rows of K-step half hi
-        // forward A operands [piece] of one K step and dW A operands [piece][ib] of one K step: requested one step
+        // dW A operands [piece][ib] of one K step (and the forward A operands, load_ha above): requested one step
         // ahead of their use (the first forward step of the NEXT tile during the dH products of this one, the first dW
-        // step ahead of the last non-zero batch of Z).  The lane offset is made opaque where it is used: the constants
-        // then stay immediates of the loads -- hoisted out of the tile loop, every (offset + constant) holds a register
-        // of its own through every phase.
-        u32x4 ha0[2];
-        auto load_ha = [&](int tt, int ks, u32x4 (&dst)[2]) {
-            const int so = tt * (kHTile * 2);
-            int ha_o = ha_lane;
-            asm volatile("" : "+v"(ha_o));
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                dst[q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ha_rs, ha_o + q * 4096 + ks * 16, so, 0));
-        };
+        // step ahead of the last non-zero batch of Z), the lane offset opaque as in load_ha.
         auto load_ht = [&](int tt, int ks, u32x4 (&dst)[2][2]) {
             const int so = tt * (kHTile * 2);
             int ht_o = ht_lane;
@@ -473,26 +522,16 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
         const int cell_lane = l31 * CELL_LD + 2 * hi * 16;          // + ((g & 1) + 4 (g >> 1)) * 16
         const int dtr = (8 * hi + (t16 >> 2)) * CELL_LD + c8 * 16;
 
-        int eHt = 0;
-        if (t < p.NT) {
-            srow_l = load_srow(t);
-            sf_l = p.sf[srow_l];
-            eHt = p.eH[t];
-            load_ha(t, 0, ha0);
-            if (lane < 32) { Rt[l31] = srow_l; Sft[l31] = sf_l; }
-            wave_sync();
-            {
-                const int4 r4 = *reinterpret_cast<const int4*>(Rt + 4 * hi);
-                yA[0] = count_at(r4.x); yA[1] = count_at(r4.y); yA[2] = count_at(r4.z); yA[3] = count_at(r4.w);
-            }
-        }
+        // (the first tile's rows, operands and counts: item_head, in the weight prologue.  The first dense pass reads the
+        // size factors behind the wave_sync() that follows F's staging stores.)
+        if (t < p.NT && lane < 32) Sft[l31] = sf_l;
         int rb = 0;                                  // which half of Rt holds the current tile's rows
         int accE = eHmin + kD0;                      // the exponent the dW accumulators carry
         int tile_no = wave >> 2;
         for (; t < p.NT; t += tstep) {
             if ((tile_no++) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
             const int row0 = t * kTR;
-            const int tn = t + tstep < p.NT ? t + tstep : t;
+            const int tn = t + tstep < p.NT ? t + tstep : t0;       // behind the last tile: the first one, for the next item
             // the tile's scales (wave-uniform): forward products carry 2^(eH[t] + eW), the gradient D = g 2^kDt
             eHt = __builtin_amdgcn_readfirstlane(eHt);
             const bool hzero = eHt == kEHZero;       // an all-zero row tile: H^T D = 0 at any scale
@@ -659,10 +698,16 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             };
             u32x4 htb[2][2][2];                          // dW A operands [K step][piece][ib]
             auto z_loop = [&](auto fullv) {             // (ONE call site of the dense pass: its code, and the non-zero pass
+                // The row-table entries behind the counts of the next group are read one group ahead: iteration grp gathers
+                // the counts of group grp + 1 (the last: of the next tile's first group, through the other half of Rt) from
+                // registers, without an LDS wait in front of the addresses, and reads the entries of group grp + 2 (what the
+                // last iteration reads, the next tile's second row group, is never used).
+                int4 rn = *reinterpret_cast<const int4*>(Rt + rb * 32 + 8 + 4 * hi);
 #pragma unroll 1                                        //  inside it, exist once per row-range variant)
                 for (int grp = 0; grp < 16 / kZU; ++grp) {
-                    if (grp + 1 < 16 / kZU) load_y(0, grp + 1, yB);
-                    else load_y(1, 0, yB);               // the next tile's first group
+                    yB[0] = count_at(rn.x); yB[1] = count_at(rn.y); yB[2] = count_at(rn.z); yB[3] = count_at(rn.w);
+                    const int g2 = grp + 2;
+                    rn = *reinterpret_cast<const int4*>(Rt + (g2 < 16 / kZU ? rb * 32 + 8 * g2 : (rb ^ 1) * 32 + 8 * (g2 - 16 / kZU)) + 4 * hi);
                     z_dense(fullv, grp, yA);
 #pragma unroll
                     for (int j = 0; j < kZU; ++j) yA[j] = yB[j];
@@ -864,6 +909,7 @@ __global__ __launch_bounds__(64 * kWR2) void heads_fused_h2_kernel(HeadsArgs2 p)
             rb ^= 1;
             wave_sync();
         }
+        carried = carried || t0 < p.NT;              // the last tile's "next" was the first: srow_l, sf_l, eHt, ha0 are its
         // the wave's weight gradient back to g units x H (exact: a power of two) before the waves are summed
         {
 #pragma unroll
