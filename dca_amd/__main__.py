@@ -1,7 +1,8 @@
 """Command line of the reference (``dca input outputdir [flags]``, dca/__main__.py:18-154) on the
 MI355X path: same positionals, flag names, defaults and output files.  The option table below
 restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--neighbors K`` (beyond the reference) writes the latent space's
-k-nearest-neighbour lists (dca_amd/neighbors.py); ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
+k-nearest-neighbour lists (dca_amd/neighbors.py); ``--groupstats FILE`` (beyond the reference) compares groups of cells on the
+denoised expression (dca_amd/groups.py); ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
 dca/hyper.py with hyperopt's TPE restated in dca_amd/tpe.py); ``--tensorboard`` is accepted for
 command-line compatibility and ignored.
 """
@@ -59,6 +60,12 @@ _OPTIONS = [
     (('--neighbors',), dict(dest='neighbors', type=int, default=None, metavar='K',
                             help='after the result files: every cell\'s K nearest other cells in the latent space, exact and '
                                  'Euclidean, computed on the GPU (knn_indices.tsv: 0-based cell numbers, knn_distances.tsv)')),
+    (('--groupstats',), dict(dest='groupstats', type=str, default=None, metavar='FILE',
+                             help='after the result files: groups of cells compared on the denoised expression, the pass over '
+                                  'the cells computed on the GPU.  FILE: tab-separated, no header, cell name and label per line '
+                                  '(cells not listed are left out).  Writes group_sizes.tsv, group_mean.tsv, group_var.tsv, '
+                                  'group_scores.tsv (Welch t against the rest), group_pvals_adj.tsv, group_logfoldchanges.tsv '
+                                  'of the log1p of the mean without size factors')),
     (('--mcv',), dict(dest='mcv', type=float, default=None, metavar='FRACTION',
                       help='molecular cross-validation instead of the denoising run: thin every count binomially, fit on FRACTION '
                            'of the molecules with the network and training flags given, score the held-out rest of every cell; '

@@ -1869,6 +1869,59 @@ class Engine:
                               cell[s - r0:], gene, ws)
         return {'cell': cell, 'gene': gene}
 
+    def group_moments(self, codes, n_groups, no_sf=False, log1p=False, r0=0, r1=None, chunk=None):
+        """Per-group first and second moments of the denoised expression over storage rows [r0, r1) (all rows by default),
+        inference mode: {'sum': [n_groups, G_out], 'sumsq': [n_groups, G_out] float64, 'count': [n_groups] int64} device
+        tensors.  codes: int32 [n] (host array or device tensor), the group of every STORAGE row, -1 = in no group.  The
+        value summed is the one predict_chunk writes as 'mean' (mean * size factor; no_sf: the mean alone; log1p: log1p of
+        either).  Per chunk of rows: predict_chunk's forward pass, then one pass over the mean head's pre-activation plane
+        (dcahip_group_moments), so every network type and both residency modes take the same path.  No targets are
+        needed; training state is not touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: group_moments() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not hasattr(ops, 'group_moments'):
+            raise NotImplementedError('dca_amd: group_moments() needs ops with group_moments (ops %s has none)' % ops.name)
+        if self.csr is None and self.X is None:
+            raise ValueError('dca_amd: group_moments() needs data: load_data / attach_counts first')
+        K = int(n_groups)
+        if not 1 <= K <= 4096:
+            raise ValueError('dca_amd: group_moments(): %d groups (1 .. 4096)' % K)
+        if log1p and self.flags & 8:
+            raise ValueError("dca_amd: group_moments(): log1p does not apply to the linear mean of ae_type 'normal': it may "
+                             'be <= -1')
+        host = codes.cpu().numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        if host.shape != (self.n,) or host.dtype.kind not in 'iu':
+            raise ValueError('dca_amd: group_moments(): codes must be %d integers, one per cell (got %s %s)'
+                             % (self.n, host.dtype, host.shape))
+        if host.size and (host.min() < -1 or host.max() >= K):
+            raise ValueError('dca_amd: group_moments(): codes must lie in -1 .. %d (found %d .. %d)'
+                             % (K - 1, host.min(), host.max()))
+        r1 = self.n if r1 is None else r1
+        if not 0 <= r0 <= r1 <= self.n:
+            raise ValueError('dca_amd: group_moments() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        s1, s2 = torch.zeros(K, lay.G_out, **f64), torch.zeros(K, lay.G_out, **f64)
+        inside = host[r0:r1]
+        count = torch.as_tensor(np.bincount(inside[inside >= 0], minlength=K).astype(np.int64)).to(self.dev)
+        res = {'sum': s1, 'sumsq': s2, 'count': count}
+        if r1 == r0:
+            return res
+        cdev = torch.as_tensor(np.ascontiguousarray(host, dtype=np.int32)).to(self.dev)
+        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
+        self.reserve(chunk)
+        ws = torch.zeros(ops.group_moments_workspace_doubles(chunk, lay.G_out, K), **f64)
+        flags = (self.flags & 8) | (16 if no_sf else 0) | (32 if log1p else 0)
+        A = self.A
+        for s in range(r0, r1, chunk):
+            b = min(chunk, r1 - s)
+            o = self._range_rows(s, b)
+            KL = self._hidden_forward(b, ('range', o), False)
+            self._heads_forward(b, KL)
+            ops.group_moments(self._plane(A, 'mean'), lay.ldA, self.sf[o:], cdev[s:], b, lay.G_out, K, flags,
+                              s1, s2, lay.G_out, ws)
+        return res
+
     def predict_chunk(self, r0, b, want):
         """Inference forward over storage rows [r0, r0+b).  Returns device views (valid until
         the next call): dict with 'mean' (mean*sf), 'dispersion', 'dropout', 'latent'."""

@@ -1,0 +1,188 @@
+"""Groups of cells compared on the denoised expression (beyond the reference, which leaves it to scanpy on the host after
+``dca()``): per-group mean and variance, Welch's t against the rest or against one reference group, Benjamini-Hochberg
+adjusted p-values and log fold changes.
+
+The only pass over cells x genes runs on the device (Engine.group_moments -> dcahip_group_moments: per group the sums of
+x and x^2 of every gene, in double); everything here is host arithmetic on [groups, genes] float64 arrays.
+``Autoencoder.group_stats`` is the public entry; ``rank_genes_groups`` re-lays its result the way scanpy's function of
+that name leaves its own.
+"""
+import numpy as np
+import pandas as pd
+
+MAX_GROUPS = 4096            # include/dcahip.h, dcahip_group_moments
+VALUES = ('denoised', 'normalized')
+
+
+def label_codes(labels, groups=None, reference='rest'):
+    """(names, codes): the sorted distinct labels and, per cell, the index of its label in names as int32 -- -1 for a
+    NaN / None label and, with `groups`, for every label not listed (a named `reference` group always stays)."""
+    lab = pd.Series(np.asarray(labels, dtype=object) if not isinstance(labels, (pd.Series, pd.Categorical)) else labels)
+    lab = lab.astype(object).reset_index(drop=True)
+    present = lab[lab.notna()]
+    try:
+        names = sorted(set(present.tolist()))
+    except TypeError:
+        raise ValueError('dca_amd: group_stats: the labels mix types that cannot be ordered (%s)'
+                         % ', '.join(sorted({type(v).__name__ for v in present.tolist()}))) from None
+    if groups is not None:
+        keep = list(groups) + ([] if reference == 'rest' else [reference])
+        unknown = [g for g in keep if g not in names]
+        if unknown:
+            raise ValueError('dca_amd: group_stats: no cell carries the label %r' % (unknown[0],))
+        names = [g for g in names if g in keep]
+    elif reference != 'rest' and reference not in names:
+        raise ValueError('dca_amd: group_stats: no cell carries the reference label %r' % (reference,))
+    index = {g: i for i, g in enumerate(names)}
+    codes = np.array([-1 if na else index.get(v, -1) for v, na in zip(lab.tolist(), lab.isna().tolist())], dtype=np.int32)
+    return names, codes
+
+
+def moments_to_mean_var(s1, s2, n):
+    """Mean and UNBIASED variance [K, G] from the sums of x and x^2 and the counts n [K]: (S2 - S1^2 / n) / (n - 1), clamped
+    at 0; NaN for n < 2 (the mean: for n < 1)."""
+    n = np.asarray(n, np.float64)[:, None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = np.where(n >= 1, s1 / n, np.nan)
+        var = np.where(n >= 2, np.maximum((s2 - s1 * s1 / n) / (n - 1.0), 0.0), np.nan)
+    return mean, var
+
+
+def welch_from_moments(m1, v1, n1, m2, v2, n2):
+    """Welch's t and its two-sided p-value (Welch-Satterthwaite degrees of freedom) from means, unbiased variances and
+    counts -- what scipy.stats.ttest_ind_from_stats(equal_var=False) computes.  A zero denominator gives t = 0, p = 1; a
+    side with fewer than two cells gives NaN."""
+    from scipy import stats
+    n1 = np.broadcast_to(np.asarray(n1, np.float64).reshape(-1, 1), m1.shape)           # one count per group (row)
+    n2 = np.broadcast_to(np.asarray(n2, np.float64).reshape(-1, 1), m1.shape)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        vn1, vn2 = v1 / n1, v2 / n2
+        den = np.sqrt(vn1 + vn2)
+        t = (m1 - m2) / den
+        df = (vn1 + vn2) ** 2 / (vn1 ** 2 / (n1 - 1.0) + vn2 ** 2 / (n2 - 1.0))
+    zero = den == 0
+    t = np.where(zero, 0.0, t)
+    p = np.full(t.shape, np.nan)
+    ok = np.isfinite(t) & np.isfinite(df) & ~zero
+    p[ok] = 2.0 * stats.t.sf(np.abs(t[ok]), df[ok])
+    p[zero] = 1.0
+    return t, p
+
+
+def benjamini_hochberg(p):
+    """Benjamini-Hochberg adjusted p-values of one vector; NaN entries stay NaN and do not count as tests."""
+    p = np.asarray(p, np.float64)
+    out = np.full(p.shape, np.nan)
+    ok = np.flatnonzero(np.isfinite(p))
+    m = len(ok)
+    if m:
+        order = ok[np.argsort(p[ok], kind='stable')]
+        adj = p[order] * m / np.arange(1, m + 1)
+        out[order] = np.minimum(np.minimum.accumulate(adj[::-1])[::-1], 1.0)
+    return out
+
+
+def stats_from_moments(s1, s2, n, log1p=False, reference=None):
+    """The statistics of every group [K, G] from the group moments: dict with mean, var, scores, pvals, pvals_adj,
+    logfoldchanges.  reference: None = every group against all other cells of the K groups together (their moments are the
+    totals minus the group's), or the index of the one group every other group is compared with (its own row: NaN)."""
+    s1, s2, n = np.asarray(s1, np.float64), np.asarray(s2, np.float64), np.asarray(n, np.float64)
+    mean, var = moments_to_mean_var(s1, s2, n)
+    if reference is None:
+        nr = n.sum() - n
+        mr, vr = moments_to_mean_var(s1.sum(axis=0)[None] - s1, s2.sum(axis=0)[None] - s2, nr)
+    else:
+        nr = np.full_like(n, n[reference])
+        mr, vr = np.broadcast_to(mean[reference], mean.shape), np.broadcast_to(var[reference], var.shape)
+    t, p = welch_from_moments(mean, var, n, mr, vr, nr)
+    back = np.expm1 if log1p else (lambda a: a)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        lfc = np.log2((back(mean) + 1e-9) / (back(mr) + 1e-9))
+    if reference is not None:
+        t[reference], p[reference], lfc[reference] = np.nan, np.nan, np.nan
+    return {'mean': mean, 'var': var, 'scores': t, 'pvals': p,
+            'pvals_adj': np.stack([benjamini_hochberg(row) for row in p]) if len(p) else p.copy(), 'logfoldchanges': lfc}
+
+
+def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
+                output_subset=None):
+    """Autoencoder.group_stats (documented there)."""
+    eng = net.engine
+    if value not in VALUES:
+        raise ValueError('dca_amd: group_stats: value must be one of %s (got %r)' % (', '.join(VALUES), value))
+    if log1p and eng.flags & 8:
+        raise ValueError("dca_amd: group_stats: log1p does not apply to ae_type='normal': its mean is linear and may be "
+                         '<= -1')
+    n = adata.n_obs
+    if isinstance(groupby, str):
+        if groupby not in adata.obs.columns:
+            raise ValueError('dca_amd: group_stats: adata.obs has no column %r' % groupby)
+        labels, key = adata.obs[groupby], groupby
+    else:
+        labels, key = groupby, None
+        if np.ndim(labels) != 1 or len(labels) != n:
+            raise ValueError('dca_amd: group_stats: %d labels for %d cells' % (np.size(labels), n))
+    names, codes = label_codes(labels, groups, reference)
+    if not names:
+        raise ValueError('dca_amd: group_stats: no cell carries a label: there is no group')
+    if len(names) > MAX_GROUPS:
+        raise ValueError('dca_amd: group_stats: %d groups (at most %d)' % (len(names), MAX_GROUPS))
+    G_out = eng.lay.G_out
+    cols = None
+    if output_subset:
+        cols = [int(np.where(adata.var_names == x)[0][0]) for x in output_subset]
+    if (len(cols) if cols is not None else adata.n_vars) != G_out:
+        raise ValueError('dca_amd: group_stats: the network fits %d genes, the data has %d: name the fitted genes with '
+                         'output_subset, in the order the network was trained with'
+                         % (G_out, len(cols) if cols is not None else adata.n_vars))
+    adata = adata.copy() if copy else adata
+    net._bind_inputs(adata)
+    chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
+    res = eng.group_moments(codes, len(names), no_sf=(value == 'normalized'), log1p=log1p, chunk=min(chunk, n))
+    counts = res['count'].cpu().numpy()
+    ref = None if reference == 'rest' else names.index(reference)
+    st = stats_from_moments(res['sum'].cpu().numpy(), res['sumsq'].cpu().numpy(), counts, log1p, ref)
+    if len(names) < 2:                                  # one group: its moments alone; nothing to compare it with
+        for k in ('scores', 'pvals', 'pvals_adj', 'logfoldchanges'):
+            st[k] = np.full_like(st['mean'], np.nan)
+    if cols is not None:                                # genes the network does not fit: NaN
+        for k, v in st.items():
+            full = np.full((len(names), adata.n_vars), np.nan)
+            full[:, cols] = v
+            st[k] = full
+    out = {'groupby': key, 'names': np.array(names, dtype=object), 'counts': counts.astype(np.int64), 'value': value,
+           'log1p': bool(log1p), 'reference': reference}
+    out.update(st)
+    adata.uns['dca_groups'] = out
+    return adata if copy else None
+
+
+def rank_genes_groups(adata, n_genes=100, key_added='rank_genes_groups'):
+    """Re-lays ``adata.uns['dca_groups']`` (Autoencoder.group_stats) into the structure scanpy's
+    ``tl.rank_genes_groups`` leaves in ``adata.uns[key_added]``: ``params`` plus ``names``, ``scores``, ``pvals``,
+    ``pvals_adj`` and ``logfoldchanges`` as numpy record arrays with one field per group, n_genes rows, the genes of every
+    group sorted by score descending (ties by gene index).  The genes a gene-subset network does not fit (no mean in any
+    group) are left out; a group without statistics (a single cell: its scores are NaN) keeps its field, the fitted genes in
+    index order with NaN entries.
+    The group compared against (``reference`` other than 'rest') has no field, as in scanpy.  scanpy is not a dependency of
+    this package and this layout is taken from its documentation, not verified against an installed scanpy: the tests
+    check the structure only.  Returns the stored dict."""
+    d = adata.uns['dca_groups']
+    var_names = np.asarray(adata.var_names)
+    groups = [(i, str(g)) for i, g in enumerate(d['names']) if d['reference'] == 'rest' or g != d['reference']]
+    fitted = np.flatnonzero(np.isfinite(d['mean']).any(axis=0))
+    rows = min(int(n_genes), len(fitted))
+    order = {}
+    for i, g in groups:
+        o = fitted[np.argsort(-d['scores'][i, fitted], kind='stable')]         # NaN sorts last, in index order
+        order[g] = o[:rows]
+    out = {'params': {'groupby': d['groupby'], 'reference': d['reference'], 'method': 't-test', 'use_raw': False,
+                      'layer': None, 'corr_method': 'benjamini-hochberg'}}
+    width = max([len(str(v)) for v in var_names] + [1])
+    out['names'] = np.rec.fromarrays([var_names[order[g]].astype('U%d' % width) for _, g in groups],
+                                     names=[g for _, g in groups]) if groups else np.recarray((0,), dtype=[])
+    for key, dt in (('scores', np.float32), ('pvals', np.float64), ('pvals_adj', np.float64), ('logfoldchanges', np.float32)):
+        out[key] = np.rec.fromarrays([d[key][i, order[g]].astype(dt) for i, g in groups],
+                                     names=[g for _, g in groups]) if groups else np.recarray((0,), dtype=[])
+    adata.uns[key_added] = out
+    return out

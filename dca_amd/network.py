@@ -313,6 +313,36 @@ class Autoencoder():
         adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
         return adata if copy else None
 
+    # ------------------------------------------------------------------ groups of cells on the denoised expression
+    def group_stats(self, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
+                    output_subset=None):
+        """Groups of cells (clusters, conditions, batches) compared on the denoised expression, the cells x genes pass on
+        the device (Engine.group_moments -> dcahip_group_moments) -- beyond the reference, whose users run
+        ``sc.tl.rank_genes_groups`` on the denoised matrix on the host.  The inputs are bound as ``predict`` binds them.
+
+        groupby     a column of ``adata.obs`` (categorical, string or integer) or an array of n labels; cells with a
+                    NaN / None label are left out
+        groups      only these labels take part (the cells of every other label are left out, of 'rest' too)
+        value       'denoised': what ``predict()`` writes, mean x size factor; 'normalized': the mean without the size
+                    factor
+        log1p       statistics of log1p(value).  ``value='normalized', log1p=True`` is the natural input of a t-test
+                    (what scanpy's workflow tests after normalize_total + log1p); not for ae_type 'normal'
+        reference   'rest': every group against all other cells that take part; or the one label every other group is
+                    compared with (that group's own scores are NaN)
+        output_subset   the fitted genes of a gene-subset network, in training order (as ``score`` takes them)
+
+        Stores ``adata.uns['dca_groups']``: groupby, names (the sorted labels), counts [K], value, log1p, reference and
+        float64 arrays [K, n_vars] ALIGNED to ``var_names`` (not ranked; NaN for the genes a gene-subset network does not
+        fit): mean, var (unbiased), scores (Welch's t), pvals (two-sided, Welch-Satterthwaite degrees of freedom),
+        pvals_adj (Benjamini-Hochberg per group over the fitted genes), logfoldchanges (scanpy's convention:
+        log2((m_group + 1e-9) / (m_reference + 1e-9)), expm1 of both means first when log1p).  Where the t denominator is 0
+        the score is 0 and the p-value 1.  With a single group its mean and var are stored and the statistics are NaN.
+        dca_amd.groups.rank_genes_groups re-lays the result into scanpy's ``uns['rank_genes_groups']``.  Returns ``adata``
+        if ``copy`` else None, like ``predict``."""
+        from .groups import group_stats
+        return group_stats(self, adata, groupby, groups=groups, value=value, log1p=log1p, reference=reference, copy=copy,
+                           output_subset=output_subset)
+
     # ------------------------------------------------------------------ scoring
     def score(self, adata, output_subset=None, use_raw_as_output=True, copy=False):
         """The fitted model's negative log-likelihood of these cells, computed on the device (Engine.score) -- beyond the

@@ -67,6 +67,19 @@ class HipOps:
         hip.check(self.L.dcahip_nll_marginals(p(a_mean), p(a_disp), p(a_pi), lda, p(theta_w), p(Y), ldy, p(sf), B, G,
                                               ridge, flags, p(cell_out), p(gene_acc), p(ws), hip.stream()), 'nll_marginals')
 
+    def group_moments_workspace_doubles(self, B, G, K):
+        n = int(self.L.dcahip_group_moments_workspace_doubles(B, G, K))
+        hip.check(min(n, 0), 'group_moments_workspace_doubles')
+        return n
+
+    def group_moments(self, a_mean, lda, sf, codes, B, G, K, flags, sum_acc, sumsq_acc, ldg, ws):
+        """Per group code (codes [B] int32; outside [0, K): left out) the column sums of the denoised mean and of its
+        square over B consecutive rows, in double, ADDED to sum_acc / sumsq_acc [K, ldg]; flags: 8 linear mean, 16 without
+        the size factor, 32 log1p.  sf / codes start at the first row."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_group_moments(p(a_mean), lda, p(sf), p(codes), B, G, K, flags, p(sum_acc), p(sumsq_acc),
+                                              ldg, p(ws), hip.stream()), 'group_moments')
+
     def loss_finalize(self, partials, n, scale, loss_out):
         hip.check(self.L.dcahip_loss_finalize(hip.ptr(partials), n, scale, hip.ptr(loss_out),
                                               hip.stream()), 'loss_finalize')

@@ -417,6 +417,10 @@ def train_with_args(args):
     adata = io.normalize(adata, size_factors=args.sizefactors, logtrans_input=args.loginput,
                          normalize_input=args.norminput)
 
+    labels = read_group_labels(args.groupstats, adata) if getattr(args, 'groupstats', None) else None
+    if labels is not None and args.type == 'normal':  # refused here, not after the fit
+        raise ValueError("dca: --groupstats compares log1p of the mean: not for --type normal, whose mean is linear")
+
     subset = None                                   # --denoisesubset: the loss sees these output genes only
     if args.denoisesubset:
         subset = list(set(io.read_genelist(args.denoisesubset)))
@@ -453,6 +457,8 @@ def train_with_args(args):
         write_scores(net, adata, x_in, subset, args.outputdir)
     if getattr(args, 'neighbors', None):
         write_neighbors(net, adata, x_in, args.neighbors, args.outputdir)
+    if labels is not None:
+        write_group_stats(net, adata, x_in, labels, subset, args.outputdir)
 
 
 def mcv_with_args(args, seed):
@@ -511,3 +517,41 @@ def write_neighbors(net, adata, x_in, k, output_dir):
         os.path.join(output_dir, 'knn_indices.tsv'), sep='\t')
     pd.DataFrame(np.asarray(adata.obsm['dca_knn_distances'], dtype=np.float64), index=cells, columns=cols).to_csv(
         os.path.join(output_dir, 'knn_distances.tsv'), sep='\t', float_format='%.6f')
+
+
+def read_group_labels(path, adata):
+    """--groupstats FILE: tab-separated lines `cell name<TAB>label`, no header -> one label per cell of adata (None for the
+    cells the file does not list).  A listed name that is not a cell of the (filtered) input is an error, and so is a name
+    listed twice."""
+    import pandas as pd
+    tab = pd.read_csv(path, sep='\t', header=None, names=['cell', 'label'], dtype=str, keep_default_na=False)
+    twice = tab['cell'].values[tab['cell'].duplicated().values]
+    if len(twice):
+        raise ValueError('dca: --groupstats: the cell %r is listed more than once (%d such lines)' % (twice[0], len(twice)))
+    where = pd.Index(adata.obs_names).get_indexer(tab['cell'].values)
+    if (where < 0).any():
+        raise ValueError('dca: --groupstats: %r is not a cell of the input (%d of the %d listed names are not)'
+                         % (tab['cell'].values[int(np.argmax(where < 0))], int((where < 0).sum()), len(tab)))
+    labels = np.full(adata.n_obs, None, dtype=object)
+    labels[where] = tab['label'].values
+    return labels
+
+
+def write_group_stats(net, adata, x_in, labels, subset, output_dir):
+    """--groupstats FILE: the groups of FILE compared on log1p of the denoised mean without size factors (train and test
+    cells alike: Autoencoder.group_stats(value='normalized', log1p=True), every group against the rest) -> group_sizes.tsv
+    (index = group; cells) and, genes x groups with a header, group_mean.tsv, group_var.tsv, group_scores.tsv,
+    group_logfoldchanges.tsv (six decimals) and group_pvals_adj.tsv (%.6e); the genes a --denoisesubset network does not
+    fit: empty."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.group_stats(adata, labels, value='normalized', log1p=True, output_subset=subset)
+    d = adata.uns['dca_groups']
+    names = [str(g) for g in d['names']]
+    pd.DataFrame({'cells': d['counts']}, index=pd.Index(names, name='group')).to_csv(
+        os.path.join(output_dir, 'group_sizes.tsv'), sep='\t')
+    genes = pd.Index(adata.var_names)
+    for key, fmt in (('mean', '%.6f'), ('var', '%.6f'), ('scores', '%.6f'), ('pvals_adj', '%.6e'), ('logfoldchanges', '%.6f')):
+        pd.DataFrame(d[key].T, index=genes, columns=names).to_csv(os.path.join(output_dir, 'group_%s.tsv' % key), sep='\t',
+                                                                  float_format=fmt)

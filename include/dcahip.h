@@ -138,6 +138,40 @@ int dcahip_nll_marginals(const float* a_mean, const float* a_disp, const float* 
                          double* cell_out, double* gene_acc, double* workspace, void* stream);
 
 /*
+ * K-GROUPS: first and second moments of the denoised expression per group of cells -- what a comparison of groups
+ * (clusters, conditions, batches) on the denoised data starts from (mean, variance, Welch's t), without the cells x genes
+ * matrix leaving the device.
+ *
+ *   a_mean, lda     : B consecutive rows of the mean head's PRE-activation plane (as dcahip_nll_marginals reads it)
+ *   sf, codes       : size factor and group code of the B rows, already offset to the first row
+ *   flags           : DCAHIP_NLL_MSE (linear mean head), DCAHIP_GROUP_NO_SF, DCAHIP_GROUP_LOG1P
+ *   sum_acc, sumsq_acc : [K][ldg] doubles, ADDED to, so that chunks of cells accumulate
+ *   workspace       : [>= dcahip_group_moments_workspace_doubles(B, G, K)] doubles (0 for B, G or K <= 0, DCAHIP_EINVAL
+ *                     when the count does not fit an int or K > 4096); non-decreasing in B, so a workspace sized for a
+ *                     chunk of rows serves every shorter chunk of the same G and K; needs no initialisation
+ *
+ * Element value, in fp32 and by the device function dcahip_zinb_heads_infer stores its mean with (the same bits):
+ * x = fminf(fmaxf(expf(a), 1e-5f), 1e6f) * sf[row], or a * sf[row] with DCAHIP_NLL_MSE; DCAHIP_GROUP_NO_SF drops the
+ * factor, DCAHIP_GROUP_LOG1P takes log1pf of the result.  For every row with 0 <= codes[row] < K:
+ *   sum_acc[code * ldg + g] += (double)x,  sumsq_acc[code * ldg + g] += (double)x * (double)x.
+ * Any other code leaves the row out (-1 is "in no group"; no code is ever used as an index without the range check).
+ *
+ * Fixed summation order (ascending row within a group), no atomics: two calls on the same inputs give bit-identical
+ * outputs.  Any B >= 1, G >= 1, 1 <= K <= 4096, ldg >= G; a 16-byte aligned plane with lda a multiple of 4 takes 16-byte
+ * loads, anything else the scalar path; columns >= G of the plane never reach an output.
+ * DCAHIP_EINVAL (nothing launched): NULL a_mean / codes / sum_acc / sumsq_acc / workspace, NULL sf without
+ * DCAHIP_GROUP_NO_SF, lda < G, ldg < G, K outside 1 .. 4096, B or G <= 0, DCAHIP_NLL_MSE together with DCAHIP_GROUP_LOG1P
+ * (a linear mean may be <= -1).
+ */
+#define DCAHIP_GROUP_NO_SF   16  /* x = mean, not mean * sf[row]                     */
+#define DCAHIP_GROUP_LOG1P   32  /* x = log1pf(...) of the above                     */
+int dcahip_group_moments_workspace_doubles(int B, int G, int K);
+int dcahip_group_moments(const float* a_mean, long lda, const float* sf, const int* codes,
+                         int B, int G, int K, int flags,
+                         double* sum_acc, double* sumsq_acc, long ldg,
+                         double* workspace, void* stream);
+
+/*
  * Deterministic second stage of the loss reduction: loss = scale * sum(partials) with
  * nan -> inf (dca/loss.py:148), written to *loss_out (fp32, device).
  */
