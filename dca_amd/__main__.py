@@ -2,7 +2,8 @@
 MI355X path: same positionals, flag names, defaults and output files.  The option table below
 restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--neighbors K`` (beyond the reference) writes the latent space's
 k-nearest-neighbour lists (dca_amd/neighbors.py); ``--groupstats FILE`` (beyond the reference) compares groups of cells on the
-denoised expression (dca_amd/groups.py); ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
+denoised expression (dca_amd/groups.py); ``--kmeans K`` (beyond the reference) clusters the latent space (dca_amd/cluster.py);
+``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
 dca/hyper.py with hyperopt's TPE restated in dca_amd/tpe.py); ``--tensorboard`` is accepted for
 command-line compatibility and ignored.
 """
@@ -66,6 +67,14 @@ _OPTIONS = [
                                   '(cells not listed are left out).  Writes group_sizes.tsv, group_mean.tsv, group_var.tsv, '
                                   'group_scores.tsv (Welch t against the rest), group_pvals_adj.tsv, group_logfoldchanges.tsv '
                                   'of the log1p of the mean without size factors')),
+    (('--kmeans',), dict(dest='kmeans', type=int, default=None, metavar='K',
+                         help='after the result files: k-means of the cells in the latent space into K clusters (1 .. 256), '
+                              'computed on the GPU (kmeans_labels.tsv: cell name and label per line, the format --groupstats '
+                              'reads; kmeans_centers.tsv)')),
+    (('--kmeansstats',), dict(dest='kmeansstats', action='store_true',
+                              help='with --kmeans: the group_*.tsv files of --groupstats for the k-means clusters (not together '
+                                   'with --groupstats)')),
+    (('--kmeans-seed',), dict(dest='kmeans_seed', type=int, default=0, metavar='N', help='seed of the k-means++ draws (default: 0)')),
     (('--mcv',), dict(dest='mcv', type=float, default=None, metavar='FRACTION',
                       help='molecular cross-validation instead of the denoising run: thin every count binomially, fit on FRACTION '
                            'of the molecules with the network and training flags given, score the held-out rest of every cell; '
@@ -74,7 +83,7 @@ _OPTIONS = [
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,
                  checkcounts=True, norminput=True, hyper=False, debug=False, tensorboard=False,
-                 loginput=True, score=False)
+                 loginput=True, score=False, kmeansstats=False)
 
 
 def build_parser():

@@ -20,15 +20,16 @@
 // (2^31 + s): above every finite key, distinct inside a list, and recognised by its low word (n < 2^31) when it is written
 // out as index -1 at +inf.  A NaN distance is above the empty keys and is never inserted.
 //
-// d2 = (sum over even k) + (sum over odd k) of fma(a_k - b_k, a_k - b_k, .), k ascending: a function of d alone (the zero
-// padding adds +0 exactly), symmetric in a and b bit for bit, never negative, 0 for equal rows.
+// d2 (knn_dist.hpp, shared with K-MEANS) = (sum over even k) + (sum over odd k) of fma(a_k - b_k, a_k - b_k, .), k
+// ascending: a function of d alone (the zero padding adds +0 exactly), symmetric in a and b bit for bit, never negative, 0
+// for equal rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dcahip.h"
+#include "knn_dist.hpp"
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
 
 constexpr unsigned kInfBits = 0x7F800000u;
@@ -64,18 +65,6 @@ struct KnnArgs {
     int splits;
     u64* keys;                              // [splits][nq][k]
 };
-
-template <int DP>
-__device__ __forceinline__ float dist2(const v2f (&q)[DP / 2], const float* __restrict__ x) {
-    v2f acc = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < DP / 2; ++j) {
-        const v2f xv = {x[2 * j], x[2 * j + 1]};
-        const v2f df = q[j] - xv;
-        acc = __builtin_elementwise_fma(df, df, acc);
-    }
-    return acc.x + acc.y;
-}
 
 template <int DP, int KP>
 __global__ __launch_bounds__(KP == 64 ? 128 : 256) void knn_scan_kernel(KnnArgs a) {

@@ -1,0 +1,24 @@
+// The squared Euclidean distance of K-NEIGHBOURS (dcahip_knn.hip) and K-MEANS (dcahip_kmeans.hip): one definition, so that a
+// (point, centre) pair gets the bits the neighbour search gives it.  d2 = s0 + s1, s_p = fma(a_j - b_j, a_j - b_j, s_p) over
+// the j of parity p ascending, fp32: a function of d alone (rows zero-padded to DP add +0 exactly), symmetric bit for bit,
+// never negative, 0 for equal rows.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+template <int DP>
+__device__ __forceinline__ float dist2(const v2f (&q)[DP / 2], const float* __restrict__ x) {
+    v2f acc = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < DP / 2; ++j) {
+        const v2f xv = {x[2 * j], x[2 * j + 1]};
+        const v2f df = q[j] - xv;
+        acc = __builtin_elementwise_fma(df, df, acc);
+    }
+    return acc.x + acc.y;
+}
+
+}  // namespace

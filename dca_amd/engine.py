@@ -1983,6 +1983,15 @@ class Engine:
         k = int(k)
         if not 1 <= k <= n - 1:
             raise ValueError('dca_amd: latent_knn(): k = %d neighbours of %d cells (every cell has %d others)' % (k, n, n - 1))
+        latent = self._latent_all(chunk)
+        idx, d2 = ops.knn(latent, latent, k, self_offset=0, splits=splits)
+        return latent, idx, d2
+
+    def _latent_all(self, chunk=None):
+        """The centre layer of every storage row ([n, h] float32 device tensor): the inference forward of the hidden stack,
+        chunk by chunk along the path predict_chunk takes (dense and counts-resident data alike).  What latent_knn and
+        latent_kmeans work on; training state is not touched."""
+        n, h = self.n, self.lay.hidden[self.center]
         chunk = min(chunk or self.Bmax or 1024, n)
         self.reserve(chunk)
         latent = torch.empty(n, h, dtype=torch.float32, device=self.dev)
@@ -1990,8 +1999,29 @@ class Engine:
             b = min(chunk, n - s)
             self._hidden_forward(b, ('range', self._range_rows(s, b)), False)
             latent[s:s + b].copy_(self.Z[self.center][:b, :h])
-        idx, d2 = ops.knn(latent, latent, k, self_offset=0, splits=splits)
-        return latent, idx, d2
+        return latent
+
+    def latent_kmeans(self, k, n_init=10, max_iter=300, seed=0, chunk=None):
+        """K-means of the cells in the latent space, on the device: the latent exactly as latent_knn collects it, then
+        dca_amd.cluster.kmeans on it (dcahip_kmeans_seed / dcahip_kmeans_step).  Returns (latent [n, h] float32,
+        cluster.KMeansResult of device tensors: labels, centers, inertia, n_iter, converged, sizes).  Training state is not
+        touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: latent_kmeans() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not lay.hidden:
+            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
+        if not hasattr(ops, 'kmeans_step'):
+            raise NotImplementedError('dca_amd: latent_kmeans() needs ops with kmeans_step (ops %s has none)' % ops.name)
+        if self.csr is None and self.X is None:
+            raise ValueError('dca_amd: latent_kmeans() needs data: load_data / attach_counts first')
+        from .cluster import check_kmeans_args, kmeans
+        k = int(k)
+        check_kmeans_args(self.n, lay.hidden[self.center], k)
+        if k > self.n:
+            raise ValueError('dca_amd: latent_kmeans(): %d clusters of %d cells' % (k, self.n))
+        latent = self._latent_all(chunk)
+        return latent, kmeans(latent, k, n_init=n_init, max_iter=max_iter, seed=seed, ops=ops, on_device=True)
 
     def heads_gene_block(self, g0, gb, want, out):
         """The heads of genes [g0, g0 + gb) for ALL cells, written gene-major: out[k] [gb, >= n] device tensors for k in

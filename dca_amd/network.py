@@ -313,6 +313,44 @@ class Autoencoder():
         adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
         return adata if copy else None
 
+    # ------------------------------------------------------------------ clusters
+    def cluster(self, adata, n_clusters, n_init=10, max_iter=300, seed=0, key_added='dca_kmeans', copy=False):
+        """K-means of these cells in the latent space, computed on the device (Engine.latent_kmeans -> dcahip_kmeans_seed /
+        dcahip_kmeans_step; dca_amd.cluster.kmeans documents the algorithm) -- beyond the reference, which leaves clustering
+        to the host.  The inputs are bound as ``predict`` binds them.  Stores
+
+            adata.obsm['X_dca']        the latent representation, what ``predict(mode='latent')`` stores
+            adata.obs[key_added]       pandas categorical of the strings '0' .. 'k-1' (categories in numeric order),
+                                       clusters numbered by size descending
+            adata.uns[key_added]       {'centers' float32 [k, h], 'inertia', 'n_iter', 'converged', 'sizes' int64 [k],
+                                        'params': {'n_clusters', 'n_init', 'max_iter', 'seed'}}
+
+        ``group_stats(adata, key_added)`` then compares the clusters on the denoised expression.  1 <= n_clusters <=
+        min(256, n); the latent space has at most 128 dimensions.  Returns ``adata`` if ``copy`` else None, like
+        ``predict``."""
+        import pandas as pd
+        from .cluster import check_kmeans_args
+        eng = self.engine
+        self._wanted('latent', False)                     # hidden_size=(): no centre layer
+        k, n = int(n_clusters), adata.n_obs
+        check_kmeans_args(n, eng.lay.hidden[eng.center], k)
+        if k > n:
+            raise ValueError('dca_amd: cluster: %d clusters of %d cells' % (k, n))
+        if eng.comm.world > 1:
+            raise ValueError('dca_amd: cluster() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        adata = adata.copy() if copy else adata
+        self._bind_inputs(adata)
+        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
+        latent, res = eng.latent_kmeans(k, n_init=n_init, max_iter=max_iter, seed=seed, chunk=min(chunk, n))
+        adata.obsm['X_dca'] = latent.cpu().numpy()
+        cats = [str(c) for c in range(k)]
+        adata.obs[key_added] = pd.Categorical.from_codes(res.labels.cpu().numpy().astype(np.int64), categories=cats)
+        adata.uns[key_added] = {'centers': res.centers.cpu().numpy(), 'inertia': float(res.inertia), 'n_iter': int(res.n_iter),
+                                'converged': bool(res.converged), 'sizes': res.sizes.cpu().numpy().astype(np.int64),
+                                'params': {'n_clusters': k, 'n_init': int(n_init), 'max_iter': int(max_iter),
+                                           'seed': int(seed)}}
+        return adata if copy else None
+
     # ------------------------------------------------------------------ groups of cells on the denoised expression
     def group_stats(self, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
                     output_subset=None):

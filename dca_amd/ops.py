@@ -600,6 +600,103 @@ class HipOps:
             raise ValueError('dca_amd: knn: %d coordinates are not finite (NaN or inf)' % bad)
         return idx, d2
 
+    def kmeans_workspace_bytes(self, n, d, k):
+        """The workspace of kmeans_seed and kmeans_step for this shape, in bytes."""
+        from .cluster import check_kmeans_args
+        check_kmeans_args(int(n), int(d), int(k))
+        nbytes = int(self.L.dcahip_kmeans_workspace_bytes(n, d, k))
+        hip.check(min(nbytes, 0), 'kmeans_workspace_bytes')
+        return nbytes
+
+    @staticmethod
+    def _kmeans_points(X, what='points'):
+        if X.dtype != torch.float32 or X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+            raise ValueError('dca_amd: kmeans: the %s are a 2-d float32 tensor with unit column stride' % what)
+        return X.stride(0) if X.shape[0] > 1 else X.shape[1]
+
+    def kmeans_raise(self, status):
+        """Reads the status word of kmeans_seed / kmeans_step (a synchronisation) and raises on non-finite coordinates."""
+        bad = int(status.item())
+        if bad:
+            raise ValueError('dca_amd: kmeans: %d coordinates are not finite (NaN or inf)' % bad)
+
+    def kmeans_seed(self, X, k, seed=0, init=0, ws=None):
+        """K-MEANS (include/dcahip.h, dcahip_kmeans_seed): k-means++ seeds of the rows of X [n, d] (fp32 device tensor, unit
+        column stride), drawn on the device with the integer arithmetic tests/_kmeans_ref.seed_ref restates.  Returns
+        (rows int32 [k], C float32 [k, d] = those rows of X).  (seed, init) name the draw.  A limit of the kernel or a
+        non-finite coordinate raises ValueError."""
+        from .cluster import check_kmeans_args
+        p = hip.ptr
+        ldx = self._kmeans_points(X)
+        n, d = X.shape
+        k, seed, init = int(k), int(seed), int(init)
+        check_kmeans_args(n, d, k)
+        if n < 1:
+            raise ValueError('dca_amd: kmeans: no points to draw seeds from')
+        if not 0 <= seed < 1 << 64 or not 0 <= init < 1 << 31:
+            raise ValueError('dca_amd: kmeans: seed is an unsigned 64-bit, init a non-negative 32-bit integer (got %d, %d)'
+                             % (seed, init))
+        dev = X.device
+        need = self.kmeans_workspace_bytes(n, d, k)
+        if ws is None:
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError('dca_amd: kmeans: the workspace holds %d bytes, %d are needed' % (ws.numel() * ws.element_size(), need))
+        rows = torch.empty(k, dtype=torch.int32, device=dev)
+        C = torch.empty(k, d, dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.check(self.L.dcahip_kmeans_seed(p(X), ldx, n, d, k, seed, init, p(rows), p(C), d, p(ws), p(status), hip.stream()),
+                  'kmeans_seed')
+        self.kmeans_raise(status)
+        return rows, C
+
+    def kmeans_bind(self, X, C_in, C_out, labels, d2, counts, sums, inertia, info, ws, status):
+        """The arguments of kmeans_step checked once: returns ``step(it)``, which enqueues iteration ``it`` >= 1 on these
+        tensors and nothing else (a Lloyd loop is launch-bound: the checks are not repeated per iteration)."""
+        from .cluster import check_kmeans_args
+        p = hip.ptr
+        ldx = self._kmeans_points(X)
+        ldc = self._kmeans_points(C_in, 'centres')
+        ldco = self._kmeans_points(C_out, 'centres')
+        n, d = X.shape
+        k = C_in.shape[0]
+        check_kmeans_args(n, d, k)
+        if C_in.shape[1] != d or tuple(C_out.shape) != (k, d):
+            raise ValueError('dca_amd: kmeans: points have %d columns, the centres are %s and %s'
+                             % (d, tuple(C_in.shape), tuple(C_out.shape)))
+        for t, dt, shape, name in ((labels, torch.int32, (n,), 'labels'), (d2, torch.float32, (n,), 'd2'),
+                                   (counts, torch.int32, (k,), 'counts'), (sums, torch.float64, (k, d), 'sums'),
+                                   (inertia, torch.float64, (1,), 'inertia'), (info, torch.int32, (3,), 'info'),
+                                   (status, torch.int32, (1,), 'status')):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError('dca_amd: kmeans: %s is a contiguous %s tensor of shape %s' % (name, dt, shape))
+        need = self.kmeans_workspace_bytes(n, d, k)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError('dca_amd: kmeans: the workspace holds %d bytes, %d are needed' % (ws.numel() * ws.element_size(), need))
+        fn = self.L.dcahip_kmeans_step
+        head = (p(X), ldx, n, d, k, p(C_in), ldc, p(C_out), ldco, p(labels), p(d2), p(counts), p(sums), d, p(inertia),
+                p(info), p(info) + 4, p(info) + 8) if n else None
+        tail = (p(ws), p(status)) if n else None
+        keep = (X, C_in, C_out, labels, d2, counts, sums, inertia, info, ws, status)      # alive as long as the closure
+
+        def step(it):
+            if int(it) < 1:
+                raise ValueError('dca_amd: kmeans: iterations are numbered from 1 (got %d)' % it)
+            if keep[0].shape[0]:
+                hip.check(fn(*head, int(it), *tail, hip.stream()), 'kmeans_step')
+        return step
+
+    def kmeans_step(self, X, C_in, C_out, labels, d2, counts, sums, inertia, info, it, ws, status, check=True):
+        """K-MEANS (include/dcahip.h, dcahip_kmeans_step): one Lloyd iteration, number ``it`` >= 1, of the points X [n, d]
+        from the centres C_in [k, d] -> C_out [k, d] (may be C_in); labels int32 [n] in / out (-1 before the first
+        iteration), d2 float32 [n], counts int32 [k], sums float64 [k, d], inertia float64 [1], info int32 [3] = (changed,
+        reseeded, state: zeroed before the first iteration, the first converged iteration afterwards).  status: int32 [1],
+        zeroed by the caller; check=True reads it (a synchronisation) and raises on non-finite coordinates, check=False
+        leaves that to a later kmeans_raise(status)."""
+        self.kmeans_bind(X, C_in, C_out, labels, d2, counts, sums, inertia, info, ws, status)(it)
+        if check:
+            self.kmeans_raise(status)
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];

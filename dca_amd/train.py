@@ -421,6 +421,25 @@ def train_with_args(args):
     if labels is not None and args.type == 'normal':  # refused here, not after the fit
         raise ValueError("dca: --groupstats compares log1p of the mean: not for --type normal, whose mean is linear")
 
+    kmeans_k = getattr(args, 'kmeans', None)        # --kmeans / --kmeansstats / --kmeans-seed: refused here, not after the fit
+    if getattr(args, 'kmeansstats', False):
+        if kmeans_k is None:
+            raise ValueError('dca: --kmeansstats describes the clusters of --kmeans K: give --kmeans')
+        if labels is not None:
+            raise ValueError('dca: --kmeansstats and --groupstats both write the group_*.tsv files: give one of them')
+        if args.type == 'normal':
+            raise ValueError("dca: --kmeansstats compares log1p of the mean: not for --type normal, whose mean is linear")
+    if kmeans_k is not None:
+        from .cluster import check_kmeans_args
+        widths_k = [int(w) for w in args.hiddensize.split(',') if w.strip()]
+        if not widths_k:
+            raise ValueError('dca: --kmeans clusters the latent space: not for a network without hidden layers')
+        check_kmeans_args(adata.n_obs, widths_k[len(widths_k) // 2], kmeans_k)
+        if kmeans_k > adata.n_obs:
+            raise ValueError('dca: --kmeans: %d clusters of %d cells' % (kmeans_k, adata.n_obs))
+        if not 0 <= getattr(args, 'kmeans_seed', 0) < 1 << 64:
+            raise ValueError('dca: --kmeans-seed is a non-negative integer below 2^64 (got %d)' % args.kmeans_seed)
+
     subset = None                                   # --denoisesubset: the loss sees these output genes only
     if args.denoisesubset:
         subset = list(set(io.read_genelist(args.denoisesubset)))
@@ -459,6 +478,10 @@ def train_with_args(args):
         write_neighbors(net, adata, x_in, args.neighbors, args.outputdir)
     if labels is not None:
         write_group_stats(net, adata, x_in, labels, subset, args.outputdir)
+    if kmeans_k is not None:
+        klabels = write_kmeans(net, adata, x_in, kmeans_k, getattr(args, 'kmeans_seed', 0), args.outputdir)
+        if getattr(args, 'kmeansstats', False):
+            write_group_stats(net, adata, x_in, klabels, subset, args.outputdir)
 
 
 def mcv_with_args(args, seed):
@@ -517,6 +540,24 @@ def write_neighbors(net, adata, x_in, k, output_dir):
         os.path.join(output_dir, 'knn_indices.tsv'), sep='\t')
     pd.DataFrame(np.asarray(adata.obsm['dca_knn_distances'], dtype=np.float64), index=cells, columns=cols).to_csv(
         os.path.join(output_dir, 'knn_distances.tsv'), sep='\t', float_format='%.6f')
+
+
+def write_kmeans(net, adata, x_in, k, seed, output_dir):
+    """--kmeans K: k-means of all cells in the latent space (train and test cells alike: Autoencoder.cluster) ->
+    kmeans_labels.tsv (`cell name<TAB>label`, no header: the format --groupstats reads) and kmeans_centers.tsv (clusters x
+    latent dimensions, six decimals).  Returns the labels, one string per cell."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.cluster(adata, k, seed=seed)
+    labels = np.asarray(adata.obs['dca_kmeans']).astype(str).astype(object)
+    pd.DataFrame({'label': labels}, index=pd.Index(adata.obs_names)).to_csv(
+        os.path.join(output_dir, 'kmeans_labels.tsv'), sep='\t', header=False)
+    centers = np.asarray(adata.uns['dca_kmeans']['centers'], dtype=np.float64)
+    pd.DataFrame(centers, index=pd.Index([str(c) for c in range(k)], name='cluster'),
+                 columns=['z%d' % (j + 1) for j in range(centers.shape[1])]).to_csv(
+        os.path.join(output_dir, 'kmeans_centers.tsv'), sep='\t', float_format='%.6f')
+    return labels
 
 
 def read_group_labels(path, adata):

@@ -917,6 +917,60 @@ int dcahip_knn(const float* Q, long ldq, int nq, const float* X, long ldx, int n
                void* ws, int* status, void* stream);
 
 /*
+ * K-MEANS (dca_amd/csrc/dcahip_kmeans.hip): Lloyd's k-means of the rows of X and its k-means++ seeding, on the device.  Beyond
+ * the reference, which leaves clustering of obsm['X_dca'] to the host; no reference call site.
+ *
+ *   X [n, ldx]              : the points, d columns (ldx >= d);  1 <= d <= 128, 1 <= k <= 256, 0 <= n < 2^31 (k may exceed n)
+ *   ws                      : >= dcahip_kmeans_workspace_bytes(n, d, k) bytes, 16-byte aligned, any content (the same size
+ *                             serves the step and the seeding; nothing in it is carried from one call to the next)
+ *   status                  : one int32, zeroed by the caller: += the non-finite coordinates met in X and in C_in (seeding: in
+ *                             X); the outputs are unspecified then, but written in bounds
+ *
+ * The distance is dcahip_knn's, the same function compiled from the same definition (csrc/knn_dist.hpp): d2 = s0 + s1, fma
+ * over the coordinates of each parity ascending, fp32.  A (point, centre) pair gets the bits the neighbour search gives it.
+ *
+ * dcahip_kmeans_step: one Lloyd iteration, two launches, no floating-point atomic.
+ *   C_in [k, ldc]           : the centres (ldc >= d);  C_out [k, ldco] (ldco >= d) the new ones; C_out may be C_in
+ *   labels [n] int32        : IN the labels of the previous iteration (-1 everywhere before the first), OUT labels[i] = the c
+ *                             that minimises the total order (d2(x_i, C_in[c]), c): what dcahip_knn(Q = X, X = C_in, k = 1,
+ *                             self_offset = -1) returns, bit for bit
+ *   d2_out [n] fp32         : that squared distance
+ *   counts [k] int32        : the members of every cluster;  sums [k, lds] double (lds >= d): sums[c][j] = the sum of
+ *                             (double)x_ij over the members of c (columns 0 .. d-1 are written)
+ *   inertia [1] double      : the sum of (double)d2_out[i];  changed [1] int32: the i whose label differs from the one passed in
+ *   C_out[c] = (float)(sums[c] / counts[c]): the division in double, one rounding to fp32.  An empty cluster keeps C_in[c],
+ *   except that, when a cluster is empty and the largest d2 of the iteration is > 0, the LOWEST-NUMBERED empty cluster takes
+ *   the coordinates of the point with the largest key (d2, index) (re-seeding; at most one cluster per iteration; its count
+ *   and sums of this iteration stay 0).  reseeded [1] int32: 1 for such an iteration, else 0.
+ *   state [1] int32, iter   : zeroed by the caller before the first iteration; the first iteration number `iter` (>= 1) with
+ *                             changed == 0 and reseeded == 0 is stored in it, later iterations leave it.  An iteration after
+ *                             that one (C_in = its C_out) is a no-op bit for bit -- same labels, d2, sums, centres -- so a host
+ *                             may read state every few iterations only.
+ *   Sums and inertia are added in an order that depends on (n, d, k) alone: two calls on the same inputs give the same bits.
+ *   Plan (a pure function of the shape): the per-workgroup cluster sums live in LDS while k * pad(d) <= 5120 doubles (pad = the
+ *   next of 8, 16, 32, 64, 128), else in the workgroup's slice of the workspace.
+ *
+ * dcahip_kmeans_seed: k-means++ (Arthur & Vassilvitskii 2007), k rounds on the stream without a host round trip, integer
+ * arithmetic after the distances and so reproducible on the host to the row.  Round t = 0 .. k-1 takes one Philox4x32-10 block,
+ * key = seed, counter (t, init, 0, 0x6B6D2B2B), r64 = (word1 << 32) | word0.  Round 0: row floor(r64 n / 2^64).  Round t >= 1:
+ * m_i = min(m_i, d2(x_i, last centre)), M = max m_i; M = 0: row floor(r64 n / 2^64); else e with M 2^e in [2^30, 2^31),
+ * q_i = floor(m_i 2^e) (exact), S = sum q_i (< 2^62), T = floor(r64 S / 2^64), the row is the smallest i whose inclusive prefix
+ * sum of q exceeds T.  A point whose weight is below 2^-30 of the largest has q_i = 0 and cannot be drawn (a bias of order
+ * 1e-9).  init (>= 0) numbers the initialisation.
+ *   rows_out [k] int32      : the rows drawn;  C_out [k, ldc] (ldc >= d): those rows of X
+ *
+ * Every index is formed in 64 bits; nothing outside the documented outputs and the workspace is written.
+ * DCAHIP_EINVAL (nothing launched): k outside 1 .. 256, d outside 1 .. 128, n < 0, a leading dimension below d, iter < 1,
+ * init < 0, a missing pointer (the size function returns it for the same shapes).  n = 0 launches nothing and returns 0.
+ */
+long dcahip_kmeans_workspace_bytes(int n, int d, int k);
+int dcahip_kmeans_step(const float* X, long ldx, int n, int d, int k, const float* C_in, long ldc, float* C_out, long ldco,
+                       int* labels, float* d2_out, int* counts, double* sums, long lds, double* inertia,
+                       int* changed, int* reseeded, int* state, int iter, void* ws, int* status, void* stream);
+int dcahip_kmeans_seed(const float* X, long ldx, int n, int d, int k, unsigned long long seed, int init,
+                       int* rows_out, float* C_out, long ldc, void* ws, int* status, void* stream);
+
+/*
  * K-PEER (dca_amd/csrc/dcahip_peer.hip): the small exchanges of the data-parallel step without a library call.
  *   slots[q], flags[q]: device arrays of `world` pointers to every rank's exchange buffers (rank's own: its local
  *   allocation; the others: mapped with hipIpcOpenMemHandle), each dcahip_peer_slot_bytes(world, nmax) /
