@@ -170,3 +170,53 @@ def repeat_floor(kDe, H, W):
     Wt = np.stack([Wa[:, 32 * j:32 * j + 32].sum(1) for j in range(ntg)], 1)         # [K, ntg]
     fh = f @ Wt.T                                                                     # [T, K]
     return fw[:, col], np.repeat(fh, 32, axis=0)
+
+
+# ------------------------------------------------------------------ K-HEADS' dispersion gradient of a y > 0 element in fp32
+# d nll / d theta of the NB case (dca/loss.py:87-88) as the kernels sum it (zinb_nz_elem / nll_elem in zinb_math.hpp):
+#     dth = -dpsi + l1p + (y tp - theta mu) / (tp (tp + mu)),   dpsi = psi(y + tp) - psi(tp),  l1p = log1p(mu / tp).
+# Each term is good to a few ulp of ITSELF; where mu << theta the first and the last cancel (dth ~ -mu / theta^2 for y = 1),
+# and what is left carries the terms' absolute error.  Roundings, in units of 2^-23 of the term: dpsi 1.5 (reciprocals of
+# 1 ulp, their sum), l1p 3 (v_log_f32, the ln 2 product, the compensation), the last 3.5 (two products, their difference,
+# two reciprocals of 1 ulp, two products) -- 4 each bounds them all, the two additions included.
+DTH_ULPS = 4.0
+D_ELEM_REL = 3e-6       # what tests/test_heads_fused_gpu.py::product_tol carries for the fp32 likelihood arithmetic of one element
+
+EPS_NB = 1e-10          # dca/loss.py:65
+
+
+def dth_terms(mu, theta, y):
+    """(dpsi, l1p, last) of dth in fp64, element-wise."""
+    from scipy.special import digamma
+    tp = theta + EPS_NB
+    return digamma(y + tp) - digamma(tp), np.log1p(mu / tp), (y * tp - theta * mu) / (tp * (tp + mu))
+
+
+def disp_grad_floor(mu, theta, gd, y, d_disp):
+    """What the fp32 evaluation of g_disp = dth gd (the unscaled gradient of the dispersion head's pre-activation) may be off
+    by BEYOND the D_ELEM_REL |g_disp| that product_tol carries: max(0, DTH_ULPS 2^-23 (dpsi + |l1p| + (y tp + theta mu) /
+    (tp (tp + mu))) gd - D_ELEM_REL |g_disp|), for y > 0; zero for y = 0 (its own formula, a series where it would cancel).
+    Non-zero only where the sum has lost about three decimal digits to cancellation."""
+    tp = theta + EPS_NB
+    dpsi, l1p, _ = dth_terms(mu, theta, y)
+    terms = dpsi + np.abs(l1p) + (y * tp + theta * mu) / (tp * (tp + mu))
+    eps = DTH_ULPS * 2.0 ** -23 * terms * np.abs(gd)
+    return np.where(y > 0, np.maximum(eps - D_ELEM_REL * np.abs(d_disp), 0.0), 0.0)
+
+
+def dth_fp32(mu, theta, y):
+    """dth of an integer count 1 <= y <= 16 summed as zinb_nz_elem does, every operation rounded to fp32 (correctly rounded:
+    the kernel's reciprocal and logarithm are good to 1 ulp, so this is the favourable end of what the kernel may return)."""
+    f = np.float32
+    mu, theta, y = f(mu), f(theta), f(y)
+    tp = (theta + f(EPS_NB)).astype(f)
+    rtp, rtm = (f(1) / tp).astype(f), (f(1) / (tp + mu).astype(f)).astype(f)
+    x = (mu * rtp).astype(f)
+    u = (f(1) + x).astype(f)
+    l1p = ((x - (u - f(1)).astype(f)).astype(f) * (tp * rtm).astype(f) + np.log(u.astype(np.float64)).astype(f)).astype(f)
+    dpsi = np.zeros_like(tp)
+    for i in range(16):
+        dpsi = np.where(i < y, (dpsi + (f(1) / (tp + f(i)).astype(f)).astype(f)).astype(f), dpsi)
+    num = ((y * tp).astype(f) - (theta * mu).astype(f)).astype(f)
+    last = ((num * rtp).astype(f) * rtm).astype(f)
+    return (((-dpsi + l1p).astype(f)) + last).astype(f)

@@ -59,15 +59,16 @@ def tile_scales(out, d_exp):
     return m, over, kde
 
 
-def check_repeat(out, d_exp, floor_keys=()):
+def check_repeat(out, d_exp, floor_keys=(), extra=None):
     """check() without the product bound, then per element: product_tol where no tile of its sum may have repeated, the
     repeat path's derived bound (product_tol sum|ab| + 2^-(kDe + 25) sum|b|, in loss units: / n_total) where one may.  Below
     d_exp = -3 (kD0 < 5) and for floor_keys the derived bound holds for every element: D's fp16 floor 2^-(kD0 + 25) is then
-    beyond what product_tol leaves for the smallest gradients."""
+    beyond what product_tol leaves for the smallest gradients.  extra: as in check() (an absolute term beside either bound)."""
     if d_exp < -3:
         floor_keys = tuple(out['_mag'])
     mag = out['_mag']
-    check({k: v for k, v in out.items() if k != '_mag'})
+    extra = extra or {}
+    check({k: v for k, v in out.items() if k != '_mag'}, extra=extra)
     m, over, kde = tile_scales(out, d_exp)
     r = out['_ref']
     rows, genes = out['dH'][0].shape[0], out['gW_mean'][0].shape[1]
@@ -79,14 +80,15 @@ def check_repeat(out, d_exp, floor_keys=()):
     for k in mag:
         g, ref = out[k]
         err = np.abs(g - ref)
+        x = extra.get(k, 0.0)
         tol = product_tol(k, rows, genes)
         strict_mask = ~row_over[:, None] if k == 'dH' else ~col_over[None, :]
         if k in floor_keys:
             strict_mask = np.zeros_like(strict_mask)
-        strict = np.where(strict_mask, err / np.maximum(mag[k], 1e-300), 0.0).max()
+        strict = np.where(strict_mask, np.maximum(err - x, 0.0) / np.maximum(mag[k], 1e-300), 0.0).max()
         assert strict <= tol, (k, 'no repeated tile in the sum', float(strict), tol)
         floor = fh if k == 'dH' else fw
-        derived = np.where(strict_mask, 0.0, err / (tol * mag[k] + floor)).max()
+        derived = np.where(strict_mask, 0.0, err / (tol * mag[k] + floor + x)).max()
         assert derived <= 1.0, (k, 'repeat path: err / derived bound', float(derived))
         worst[k] = (float(strict), float(derived))
     print('repeat check: tiles over %d of %d; per key (strict err/sum|ab|, repeated err/derived bound): %s'

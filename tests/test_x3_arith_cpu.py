@@ -245,3 +245,95 @@ def test_heads_repeat_path_bound(count, d_exp):
     h1, h2 = X.split2(Dt, int(o['kDe'][0, gl // 32]))
     err = np.abs(np.ldexp(h1.astype(np.float64) + h2, -int(o['kDe'][0, gl // 32])) - Dt)
     assert (err <= np.maximum(2.0 ** -22 * np.abs(Dt), 2.0 ** -(o['kDe'][0, gl // 32] + 25))).all()
+
+
+@pytest.mark.parametrize('flags', [1, 0, 3, 2])
+@pytest.mark.parametrize('B,name', [(128, 'spread'), (32, '2^15')])
+def test_heads_big_row_tile_forward_bound(flags, B, name):
+    """A row tile of H at 2^15 and more (tests/test_heads_small_edges_gpu.py, case (d)): the pre-activations are 1e5 .. 1e7, an
+    fp32 forward product is off by 0.1 .. 10 there, and the few elements of the tile that are NOT saturated move with it.
+    The bound the GPU test holds such a launch to adds, per output element, what the likelihood's gradient can change by
+    when each pre-activation of the big tile moves inside the forward product's error box
+        delta = 5e-7 sum|h w| + 2^-24 |a|        (the contract of dcahip_x3_product_32x32, then one fp32 rounding of a' + b)
+    -- tests/_heads_small_cases.py::forward_error_terms; nothing for the rows of ordinary tiles.  Shown here on the model of
+    the kernel's forward (X.matmul_h2 per 32 x 32 tile pair with the kernel's block scales, fp64 everywhere else):
+      - the model's forward stays inside the box (asserted by forward_error_terms),
+      - the model's gradients, with EXACT backward products, meet the added term alone, and
+      - they miss product_tol (for some flags by five orders of magnitude): that bound speaks of the backward products, it
+        cannot hold the conditioning of the likelihood on a forward product of this size."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _heads_small_cases as C
+
+    def model_forward(heads, Hb, W, b):
+        G = W[heads[0]].shape[1]
+        A = {h: np.zeros((Hb.shape[0], G)) for h in heads}
+        for r0 in range(0, Hb.shape[0], 32):
+            Ht = Hb[r0:r0 + 32].astype(np.float32)
+            eH = X.block_exp(Ht)
+            for g0 in range(0, G, 32):
+                eW = X.block_exp(np.stack([W[h][:, g0:g0 + 32] for h in heads]))
+                for h in heads:
+                    acc = X.matmul_h2(Ht, W[h][:, g0:g0 + 32].astype(np.float32), 3, ea=eH, eb=eW)
+                    A[h][r0:r0 + 32, g0:g0 + 32] = (acc.astype(np.float32) + b[h][g0:g0 + 32].astype(np.float32)).astype(np.float64)
+        return A
+
+    om, add, diff, (heads, H, W) = C.forward_error_terms(A_of=model_forward, **C.hscale_case(flags, B, name))
+    o = C.oracle_case(**C.hscale_case(flags, B, name))
+    # (1e-18, in loss units: the rounding of the oracle's own fp64 sums; a sigmoid beyond |a| = 100, see LIVE, is far below)
+    assert all((np.abs(diff[k]) <= om[k] + 1e-18).all() for k in om)
+    missed = 0.0
+    for h in heads:
+        err = np.abs(H.T @ diff[h])
+        assert (err <= add['gW_' + h] * (1 + 1e-12) + 1e-9).all()
+        assert (np.abs(diff[h].sum(0)) <= add['gb_' + h] * (1 + 1e-12) + 1e-9).all()
+        mag = np.abs(H).T @ np.abs(o['_ref']['D'][heads.index(h)])
+        missed = max(missed, float((err / np.maximum(_product_tol('gW_' + h, B) * mag, 1e-300)).max()))
+    errh = np.abs(sum(diff[h] @ W[h].T for h in heads))
+    assert (errh <= add['dH'] * (1 + 1e-12) + 1e-9).all()
+    if 'theta' in om:
+        assert (np.abs(diff['theta'].sum(0)) <= add['g_theta'] * (1 + 1e-12) + 1e-9).all()
+    print('%s flags %d: the model misses product_tol on gW by a factor %.3g' % (name, flags, missed))
+    if not flags & 2:                                # (DispAct's window is 1e4 wide: every launch has elements inside it)
+        assert missed > 1.0
+
+
+@pytest.mark.parametrize('flags', [1, 0])
+@pytest.mark.parametrize('case,B', [('wscale', 32), ('wscale', 128), ('compact', 32), ('rescale', 33)])
+def test_heads_disp_gradient_floor(flags, case, B):
+    """The dispersion head's gradient of a y > 0 element, g_disp = dth gd with
+        dth = -dpsi + log1p(mu / tp) + (y tp - theta mu) / (tp (tp + mu)),
+    summed in fp32 as zinb_nz_elem does (X.dth_fp32, every operation correctly rounded), against fp64 on the inputs of the
+    four-wave edge cases: the sum stays inside DTH_ULPS 2^-23 of its terms, the bound X.disp_grad_floor is built on; where
+    mu << theta it cancels, and the fp32 sum is then off by MORE than the 3e-6 of the element that product_tol carries (up to
+    1e-3 of it) -- so the floor is needed.  (It is non-zero for about a quarter of the elements and adds a tenth to a third to
+    product_tol's bound of a typical gW_disp element: the cancellation is mild nearly everywhere.)"""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _heads_small_cases as C
+    from oracle import zinb_np as Z
+    kw = {'wscale': lambda: C.wscale_case(flags, B), 'compact': lambda: C.compact_case(flags, B),
+          'rescale': lambda: C.rescale_case(flags, B, 'outliers')}[case]()
+    o = C.oracle_case(**kw)
+    _, _, n_total, heads, H, W, b, tw, y, sf = C._oracle_inputs(kw)
+    am, ad = H @ W['mean'] + b['mean'], H @ W['disp'] + b['disp']
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)
+    mu, theta, gd = f32(Z.mean_act(am) * sf[:, None]), f32(Z.disp_act(ad)), Z._act_grads(am, ad)[1]
+    dpsi, l1p, last = X.dth_terms(mu, theta, y)
+    dth = -dpsi + l1p + last
+    nz = y > 0
+    # the terms are the oracle's gradient (mu and theta rounded to fp32 move it by 1e-7 of its terms at most)
+    D = o['_ref']['D'][heads.index('disp')] * n_total
+    terms = dpsi + np.abs(l1p) + (y * (theta + X.EPS_NB) + theta * mu) / ((theta + X.EPS_NB) * (theta + X.EPS_NB + mu))
+    assert (np.abs(dth * gd - D)[nz] <= 2.0 ** -22 * (terms * gd)[nz] + 1e-300).all()
+    small = nz & (y <= 16) & (y == np.floor(y))
+    err = np.abs(X.dth_fp32(mu, theta, y).astype(np.float64) - dth) * gd
+    assert (err[small] <= X.DTH_ULPS * 2.0 ** -23 * (terms * gd)[small]).all()
+    beyond = small & (err > X.D_ELEM_REL * np.abs(dth * gd)) & (gd > 0)
+    floor = X.disp_grad_floor(mu, theta, gd, y, dth * gd)
+    print('%s B %d flags %d: fp32 sum beyond 3e-6 of the element: %d of %d (worst %.1e of it); floor non-zero for %d'
+          % (case, B, flags, int(beyond.sum()), int(small.sum()), float((err[beyond] / np.abs(dth * gd)[beyond]).max(initial=0)),
+             int((floor > 0).sum())))
+    assert beyond.any()
+    assert (err[small] <= floor[small] + X.D_ELEM_REL * np.abs(dth * gd)[small]).all()
+    assert (floor[~nz] == 0).all()
