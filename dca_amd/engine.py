@@ -1922,6 +1922,81 @@ class Engine:
                               s1, s2, lay.G_out, ws)
         return res
 
+    def gene_gram(self, cols, keep=None, no_sf=False, log1p=False, r0=0, r1=None, chunk=None):
+        """Centred cross-products of the denoised expression of the genes `cols` (1-d integer array of distinct output
+        columns, at most 8192, in the order of the result) over storage rows [r0, r1) (all rows by default), inference mode:
+        {'cross': [g, g], 'dsum': [g], 'shift': [g]} float64 device tensors and 'count' (int), the rows that took part.
+        keep: one flag per STORAGE row (host array or device tensor, bool or integer; 0 = the row is left out), None =
+        every row.  With d[r][j] = x[r][cols[j]] - shift[j], x the value predict_chunk writes as 'mean' (mean * size
+        factor; no_sf: the mean alone; log1p: log1p of either): cross = sum_r d d^T, dsum = sum_r d, so that the covariance
+        is (cross - dsum dsum^T / count) / (count - 1) and the mean shift + dsum / count.  shift is fixed once, the fp64
+        mean of the first chunk's kept rows (zeros if it keeps none), and used unchanged for every chunk: any constant
+        near the mean keeps the subtraction of the two terms harmless.  Per chunk of rows: predict_chunk's forward pass and
+        its store of the mean, then one dcahip_gram call on that plane, so every network type and both residency modes
+        take the same path.  No targets are needed; training state is not touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: gene_gram() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not hasattr(ops, 'gram'):
+            raise NotImplementedError('dca_amd: gene_gram() needs ops with gram (ops %s has none)' % ops.name)
+        if self.csr is None and self.X is None:
+            raise ValueError('dca_amd: gene_gram() needs data: load_data / attach_counts first')
+        if log1p and self.flags & 8:
+            raise ValueError("dca_amd: gene_gram(): log1p does not apply to the linear mean of ae_type 'normal': it may be "
+                             '<= -1')
+        chost = cols.cpu().numpy() if isinstance(cols, torch.Tensor) else np.asarray(cols)
+        if chost.ndim != 1 or chost.dtype.kind not in 'iu' or chost.size < 1:
+            raise ValueError('dca_amd: gene_gram(): cols must be a 1-d integer array of at least one gene (got %s %s)'
+                             % (chost.dtype, chost.shape))
+        g = int(chost.size)
+        if g > 8192:
+            raise ValueError('dca_amd: gene_gram(): %d genes (at most 8192)' % g)
+        if chost.min() < 0 or chost.max() >= lay.G_out:
+            raise ValueError('dca_amd: gene_gram(): cols must lie in 0 .. %d (found %d .. %d)'
+                             % (lay.G_out - 1, chost.min(), chost.max()))
+        if np.unique(chost).size != g:
+            raise ValueError('dca_amd: gene_gram(): cols names a gene more than once')
+        khost = None
+        if keep is not None:
+            khost = keep.cpu().numpy() if isinstance(keep, torch.Tensor) else np.asarray(keep)
+            if khost.shape != (self.n,) or khost.dtype.kind not in 'biu':
+                raise ValueError('dca_amd: gene_gram(): keep must be %d flags, one per cell (got %s %s)'
+                                 % (self.n, khost.dtype, khost.shape))
+            khost = khost != 0
+        r1 = self.n if r1 is None else r1
+        if not 0 <= r0 <= r1 <= self.n:
+            raise ValueError('dca_amd: gene_gram() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        cross, dsum, shift = torch.zeros(g, g, **f64), torch.zeros(g, **f64), torch.zeros(g, **f64)
+        res = {'cross': cross, 'dsum': dsum, 'shift': shift,
+               'count': int(khost[r0:r1].sum()) if khost is not None else r1 - r0}
+        if r1 == r0:
+            return res
+        cdev = torch.as_tensor(np.ascontiguousarray(chost, dtype=np.int32)).to(self.dev)
+        kdev = torch.as_tensor(khost.astype(np.int32)).to(self.dev) if khost is not None else None
+        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
+        self.reserve(chunk)
+        nws = ops.gram_workspace_doubles(chunk, g)
+        ws = torch.zeros(nws, **f64) if nws else None
+        ones = torch.ones(chunk, dtype=torch.float32, device=self.dev) if no_sf else None
+        A = self.A
+        for s in range(r0, r1, chunk):
+            b = min(chunk, r1 - s)
+            o = self._range_rows(s, b)
+            KL = self._hidden_forward(b, ('range', o), False)
+            self._heads_forward(b, KL)
+            m = self._plane(A, 'mean')
+            ops.heads_infer(m, None, None, lay.ldA, ones if no_sf else self.sf[o:], b, lay.G_out, m, None, None, lay.ldA,
+                            self.flags & 8)                      # no_sf: x * 1.0f is exact
+            if log1p:
+                torch.log1p_(m[:b, :lay.G_out])
+            if s == r0:
+                rows = m[:b] if kdev is None else m[:b][kdev[s:s + b] != 0]
+                if rows.shape[0]:
+                    shift.copy_(rows.index_select(1, cdev.long()).double().mean(dim=0))
+            ops.gram(m, lay.ldA, cdev, kdev[s:] if kdev is not None else None, shift, b, g, cross, g, dsum, ws)
+        return res
+
     def predict_chunk(self, r0, b, want):
         """Inference forward over storage rows [r0, r0+b).  Returns device views (valid until
         the next call): dict with 'mean' (mean*sf), 'dispersion', 'dropout', 'latent'."""

@@ -381,6 +381,30 @@ class Autoencoder():
         return group_stats(self, adata, groupby, groups=groups, value=value, log1p=log1p, reference=reference, copy=copy,
                            output_subset=output_subset)
 
+    # ------------------------------------------------------------------ gene-gene correlation of the denoised expression
+    def gene_correlation(self, adata, genes=None, groupby=None, group=None, value='denoised', log1p=False,
+                         key_added='dca_gene_corr', copy=False, output_subset=None):
+        """Pearson correlation between genes on the denoised expression, the cells x genes pass on the device
+        (Engine.gene_gram -> dcahip_gram) -- beyond the reference, whose users run ``np.corrcoef`` on the denoised matrix on
+        the host.  The inputs are bound as ``predict`` binds them.
+
+        genes       gene names from ``var_names``, in the order of the result; None: every fitted gene.  At most 8192
+        groupby, group   only the cells that carry the label ``group`` take part (correlation inside one cluster);
+                    ``groupby`` is a column of ``adata.obs`` or an array of n labels, as ``group_stats`` takes it
+        value, log1p    as in ``group_stats``: 'denoised' (mean x size factor) or 'normalized' (the mean alone), and
+                    log1p of it (not for ae_type 'normal')
+        output_subset   the fitted genes of a gene-subset network, in training order (as ``score`` takes them)
+
+        Stores ``adata.uns[key_added]``: genes, corr (float64 [g, g], symmetric, diagonal 1; a gene that is constant over
+        the cells has a NaN row and column, as in ``np.corrcoef``), mean and var (unbiased) of every gene over the cells
+        that took part, n_cells, value, log1p, groupby, group.  The sums are taken in double around a per-gene constant
+        near the mean, so a gene that denoising left nearly constant keeps its digits.
+        dca_amd.genecorr.top_partners lists a gene's strongest partners.  Returns ``adata`` if ``copy`` else None, like
+        ``predict``."""
+        from .genecorr import gene_correlation
+        return gene_correlation(self, adata, genes=genes, groupby=groupby, group=group, value=value, log1p=log1p,
+                                key_added=key_added, copy=copy, output_subset=output_subset)
+
     # ------------------------------------------------------------------ scoring
     def score(self, adata, output_subset=None, use_raw_as_output=True, copy=False):
         """The fitted model's negative log-likelihood of these cells, computed on the device (Engine.score) -- beyond the

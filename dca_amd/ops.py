@@ -80,6 +80,21 @@ class HipOps:
         hip.check(self.L.dcahip_group_moments(p(a_mean), lda, p(sf), p(codes), B, G, K, flags, p(sum_acc), p(sumsq_acc),
                                               ldg, p(ws), hip.stream()), 'group_moments')
 
+    def gram_workspace_doubles(self, B, G):
+        n = int(self.L.dcahip_gram_workspace_doubles(B, G))
+        hip.check(min(n, 0), 'gram_workspace_doubles')
+        return n
+
+    def gram(self, x, ldx, cols, keep, shift, B, G, cross, ldc, dsum, ws):
+        """Centred cross-products of G columns of B consecutive rows of the fp32 plane x, in double: with d[r][j] =
+        x[r][cols[j]] - shift[j] over the rows whose keep word is not 0 (cols int32 [G], None: column j; keep int32 [B],
+        None: every row), sum_r d[r][i] d[r][j] is ADDED to cross [G, ldc] (the full square, symmetric bit for bit) and
+        sum_r d[r][j] to dsum [G].  keep starts at the first row; ws: gram_workspace_doubles(B, G) doubles (None is
+        allowed without cols when the rows make a single slice)."""
+        p = hip.ptr
+        hip.check(self.L.dcahip_gram(p(x), ldx, p(cols), p(keep), p(shift), B, G, p(cross), ldc, p(dsum), p(ws),
+                                     hip.stream()), 'gram')
+
     def loss_finalize(self, partials, n, scale, loss_out):
         hip.check(self.L.dcahip_loss_finalize(hip.ptr(partials), n, scale, hip.ptr(loss_out),
                                               hip.stream()), 'loss_finalize')

@@ -445,6 +445,14 @@ def train_with_args(args):
         subset = list(set(io.read_genelist(args.denoisesubset)))
         unknown = set(subset) - set(adata.var_names.values)
         assert len(unknown) == 0, 'Gene list is not overlapping with genes from the dataset'
+
+    corr_genes = None                               # --genecorr / --genecorr-log1p: refused here, not after the fit
+    if getattr(args, 'genecorr_log1p', False) and not getattr(args, 'genecorr', None):
+        raise ValueError('dca: --genecorr-log1p describes the values of --genecorr FILE: give --genecorr')
+    if getattr(args, 'genecorr', None):
+        corr_genes = read_corr_genes(args.genecorr, adata, subset)
+        if args.genecorr_log1p and args.type == 'normal':
+            raise ValueError("dca: --genecorr-log1p correlates log1p of the mean: not for --type normal, whose mean is linear")
     n_out = len(subset) if subset else adata.n_vars
 
     widths = [int(w) for w in args.hiddensize.split(',')]
@@ -482,6 +490,8 @@ def train_with_args(args):
         klabels = write_kmeans(net, adata, x_in, kmeans_k, getattr(args, 'kmeans_seed', 0), args.outputdir)
         if getattr(args, 'kmeansstats', False):
             write_group_stats(net, adata, x_in, klabels, subset, args.outputdir)
+    if corr_genes is not None:
+        write_gene_corr(net, adata, x_in, corr_genes, args.genecorr_log1p, subset, args.outputdir)
 
 
 def mcv_with_args(args, seed):
@@ -576,6 +586,37 @@ def read_group_labels(path, adata):
     labels = np.full(adata.n_obs, None, dtype=object)
     labels[where] = tab['label'].values
     return labels
+
+
+def read_corr_genes(path, adata, subset=None):
+    """--genecorr FILE: gene names, one per line, read as --denoisesubset reads its file (a name listed twice counts once)
+    -> the names in the order of the input's genes.  A name that is not a gene of the (filtered) input, or not one of the
+    genes a --denoisesubset network fits, is an error, and so are more than 8192 names."""
+    from . import io
+    from .genecorr import MAX_GENES
+    listed = set(io.read_genelist(path))
+    known = set(subset) if subset else set(adata.var_names.values)
+    unknown = sorted(listed - known)
+    if unknown:
+        raise ValueError('dca: --genecorr: %r is not a gene %s (%d of the %d listed names are not)'
+                         % (unknown[0], 'of --denoisesubset' if subset else 'of the input', len(unknown), len(listed)))
+    if len(listed) > MAX_GENES:
+        raise ValueError('dca: --genecorr: %d genes (at most %d)' % (len(listed), MAX_GENES))
+    return [g for g in adata.var_names.values if g in listed]
+
+
+def write_gene_corr(net, adata, x_in, genes, log1p, subset, output_dir):
+    """--genecorr FILE: Pearson correlation between the listed genes over all cells (train and test cells alike:
+    Autoencoder.gene_correlation) on the denoised mean, with --genecorr-log1p on log1p of the mean without size factors
+    -> gene_corr.tsv (genes x genes with both name vectors, six decimals; a gene that is constant over the cells: empty)."""
+    from .io import write_text_matrix
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.gene_correlation(adata, genes=genes, value='normalized' if log1p else 'denoised', log1p=bool(log1p),
+                         output_subset=subset)
+    d = adata.uns['dca_gene_corr']
+    names = [str(g) for g in d['genes']]
+    write_text_matrix(d['corr'], os.path.join(output_dir, 'gene_corr.tsv'), rownames=names, colnames=names)
 
 
 def write_group_stats(net, adata, x_in, labels, subset, output_dir):

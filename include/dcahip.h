@@ -172,6 +172,40 @@ int dcahip_group_moments(const float* a_mean, long lda, const float* sf, const i
                          double* workspace, void* stream);
 
 /*
+ * K-GRAM: centred cross-products of selected columns of an fp32 plane, in double -- what a gene-gene correlation of the
+ * denoised expression starts from (covariance = (cross - dsum dsum^T / n) / (n - 1)), without the cells x genes matrix
+ * leaving the device.
+ *
+ *   x, ldx          : B consecutive rows of an fp32 plane (the values dcahip_zinb_heads_infer wrote, or their log1p)
+ *   cols            : [G] int32 column of x per selected gene, NULL = column j; the entries are the CALLER's
+ *                     responsibility (no range check: x[r * ldx + cols[j]] is read as it stands)
+ *   keep            : [B] int32, a row with keep[r] == 0 is left out (whatever it holds, NaN included); NULL = every row
+ *   shift           : [G] doubles, any constant near the gene's mean (it only has to be the same in every call that
+ *                     adds to the same accumulators)
+ *   cross, ldc      : [G][ldc] doubles, ADDED to over the full G x G square;  dsum : [G] doubles, ADDED to
+ *   ws              : [>= dcahip_gram_workspace_doubles(B, G)] doubles: the selected columns of a row block as a compact
+ *                     fp32 image (gathered once, not once per tile column) and the row slices' partial tiles;
+ *                     non-decreasing in B, so a workspace sized for a chunk of rows serves every shorter chunk of the
+ *                     same G; at most 64 MiB; needs no initialisation; may be NULL for cols == NULL with a single row
+ *                     slice.  The query returns 0 for B <= 0, DCAHIP_EINVAL for G outside 1 .. 8192
+ *
+ * For the kept rows r < B and i, j < G, with d[r][j] = (double)x[r * ldx + cols[j]] - shift[j] (one rounding):
+ *   cross[i * ldc + j] += sum_r d[r][i] d[r][j],   dsum[j] += sum_r d[r][j].
+ * Products and sums in double on the fp64 matrix pipe; only the 64 x 64 tiles with tile_i <= tile_j are computed and the
+ * SAME double is added at [i][j] and at [j][i]: accumulators that were symmetric stay symmetric bit for bit.  Fixed
+ * summation order (rows ascending within a row slice, slices in index order, then one add onto the accumulator; with
+ * cols, more rows than fit the workspace -- 2 048 at 8 192 genes -- go in row blocks, one such add each, in row order), no
+ * atomics: two calls on the same inputs give bit-identical outputs.  There is more than one row slice only when the
+ * triangle's tiles alone (at most 682 of them, against 1024 resident workgroups) do not fill the chip; the plan is a
+ * pure function of (B, G), stated above the kernel in dcahip_gram.hip.  B == 0 or no kept row: the accumulators keep their bits.
+ * DCAHIP_EINVAL (nothing launched): NULL x / shift / cross / dsum, ldc < G, ldx < 1, G outside 1 .. 8192, B < 0, NULL ws
+ * where the call needs one (cols given, or more than one row slice).
+ */
+long dcahip_gram_workspace_doubles(int B, int G);
+int dcahip_gram(const float* x, long ldx, const int* cols, const int* keep, const double* shift,
+                int B, int G, double* cross, long ldc, double* dsum, double* ws, void* stream);
+
+/*
  * Deterministic second stage of the loss reduction: loss = scale * sum(partials) with
  * nan -> inf (dca/loss.py:148), written to *loss_out (fp32, device).
  */
