@@ -3,6 +3,7 @@ MI355X path: same positionals, flag names, defaults and output files.  The optio
 restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--neighbors K`` (beyond the reference) writes the latent space's
 k-nearest-neighbour lists (dca_amd/neighbors.py); ``--groupstats FILE`` (beyond the reference) compares groups of cells on the
 denoised expression (dca_amd/groups.py); ``--kmeans K`` (beyond the reference) clusters the latent space (dca_amd/cluster.py);
+``--silhouette {kmeans,groups}`` (beyond the reference) scores such a clustering (dca_amd/silhouette.py);
 ``--genecorr FILE`` (beyond the reference) correlates genes on the denoised expression (dca_amd/genecorr.py);
 ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
 dca/hyper.py with hyperopt's TPE restated in dca_amd/tpe.py); ``--tensorboard`` is accepted for
@@ -76,6 +77,11 @@ _OPTIONS = [
                               help='with --kmeans: the group_*.tsv files of --groupstats for the k-means clusters (not together '
                                    'with --groupstats)')),
     (('--kmeans-seed',), dict(dest='kmeans_seed', type=int, default=0, metavar='N', help='seed of the k-means++ draws (default: 0)')),
+    (('--silhouette',), dict(dest='silhouette', choices=('kmeans', 'groups'), default=None,
+                             help='after the result files: the silhouette coefficient of every cell in the latent space, '
+                                  'computed on the GPU, under the clusters of --kmeans K (kmeans) or the labels of --groupstats '
+                                  'FILE (groups); writes silhouette.tsv (cell, label, silhouette, nearest other cluster) and '
+                                  'silhouette_clusters.tsv (label, size, mean silhouette) and prints the overall mean')),
     (('--genecorr',), dict(dest='genecorr', type=str, default=None, metavar='FILE',
                            help='after the result files: Pearson correlation between the genes FILE names (one per line, at '
                                 'most 8192, read as --denoisesubset reads its file) on the denoised mean over all cells, the '
@@ -91,7 +97,7 @@ _OPTIONS = [
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,
                  checkcounts=True, norminput=True, hyper=False, debug=False, tensorboard=False,
-                 loginput=True, score=False, kmeansstats=False, genecorr_log1p=False)
+                 loginput=True, score=False, kmeansstats=False, silhouette=None, genecorr_log1p=False)
 
 
 def build_parser():

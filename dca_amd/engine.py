@@ -2098,6 +2098,31 @@ class Engine:
         latent = self._latent_all(chunk)
         return latent, kmeans(latent, k, n_init=n_init, max_iter=max_iter, seed=seed, ops=ops, on_device=True)
 
+    def latent_silhouette(self, codes, k, chunk=None):
+        """The silhouette of every cell in the latent space under the cluster codes [n] (int32, host array or device tensor;
+        a value outside [0, k): the cell is in no cluster), on the device: the latent exactly as latent_knn collects it, then
+        ops.silhouette on it (dcahip_silhouette).  Returns (latent [n, h] float32, dict of device tensors: s, a, b, nearest,
+        counts, cluster_mean, mean).  Training state is not touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: latent_silhouette() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not lay.hidden:
+            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
+        if not hasattr(ops, 'silhouette'):
+            raise NotImplementedError('dca_amd: latent_silhouette() needs ops with silhouette (ops %s has none)' % ops.name)
+        if self.csr is None and self.X is None:
+            raise ValueError('dca_amd: latent_silhouette() needs data: load_data / attach_counts first')
+        from .silhouette import check_silhouette_args
+        k = int(k)
+        check_silhouette_args(self.n, lay.hidden[self.center], k)
+        if not isinstance(codes, torch.Tensor):
+            codes = torch.from_numpy(np.ascontiguousarray(np.asarray(codes), dtype=np.int32))
+        if codes.dim() != 1 or codes.shape[0] != self.n:
+            raise ValueError('dca_amd: latent_silhouette(): %d codes for %d cells' % (codes.numel(), self.n))
+        codes = codes.to(device=self.dev, dtype=torch.int32).contiguous()
+        latent = self._latent_all(chunk)
+        return latent, ops.silhouette(latent, codes, k)
+
     def heads_gene_block(self, g0, gb, want, out):
         """The heads of genes [g0, g0 + gb) for ALL cells, written gene-major: out[k] [gb, >= n] device tensors for k in
         want (mean = mean * size factor, dispersion, dropout) -- a [n, hL] x [hL, gb] product per head, the inference

@@ -351,6 +351,27 @@ class Autoencoder():
                                            'seed': int(seed)}}
         return adata if copy else None
 
+    def silhouette(self, adata, groupby='dca_kmeans', key_added='dca_silhouette', copy=False):
+        """The silhouette coefficient of every cell in the latent space under a clustering, computed on the device
+        (Engine.latent_silhouette -> dcahip_silhouette; dca_amd.silhouette documents the number) -- beyond the reference,
+        which leaves the quality of a clustering to the host.  The inputs are bound as ``predict`` binds them.
+
+        groupby     a column of ``adata.obs`` (what ``cluster`` stored, or any categorical, string or integer column) or an
+                    array of n labels, as ``group_stats`` takes it; cells with a NaN / None label are in no cluster
+
+        Stores
+
+            adata.obsm['X_dca']                 the latent representation, what ``predict(mode='latent')`` stores
+            adata.obs[key_added]                float64: the cell's silhouette, NaN for a cell in no cluster
+            adata.obs[key_added + '_nearest']   the label of the nearest other cluster (None for a cell in no cluster)
+            adata.uns[key_added]                {'groupby', 'names' (the sorted labels), 'sizes' int64 [k], 'cluster_mean'
+                                                 float64 [k], 'mean' (over all labelled cells), 'params': {'metric'}}
+
+        2 .. 256 labels; the latent space has at most 128 dimensions.  Returns ``adata`` if ``copy`` else None, like
+        ``predict``."""
+        from .silhouette import model_silhouette
+        return model_silhouette(self, adata, groupby=groupby, key_added=key_added, copy=copy)
+
     # ------------------------------------------------------------------ groups of cells on the denoised expression
     def group_stats(self, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
                     output_subset=None):

@@ -712,6 +712,69 @@ class HipOps:
         if check:
             self.kmeans_raise(status)
 
+    def silhouette_splits(self, n, d, k):
+        """The number of candidate splits dcahip_silhouette takes for this shape when it is asked for 0."""
+        from .silhouette import check_silhouette_args
+        check_silhouette_args(int(n), int(d), int(k))
+        s = int(self.L.dcahip_silhouette_splits(n, d, k))
+        hip.check(min(s, 0), 'silhouette_splits')
+        return s
+
+    def silhouette_workspace_bytes(self, n, d, k, splits=0):
+        """The workspace of silhouette for this shape and this many splits (0: the library's choice), in bytes."""
+        from .silhouette import check_silhouette_args
+        check_silhouette_args(int(n), int(d), int(k), int(splits))
+        nbytes = int(self.L.dcahip_silhouette_workspace_bytes(n, d, k, splits))
+        hip.check(min(nbytes, 0), 'silhouette_workspace_bytes')
+        return nbytes
+
+    def silhouette_raise(self, status, counts):
+        """Reads the status word and the cluster sizes of silhouette (a synchronisation) and raises on non-finite coordinates
+        and on fewer than two clusters with points."""
+        bad, live = torch.stack([status[0].to(torch.int64), (counts > 0).sum()]).tolist()
+        if bad:
+            raise ValueError('dca_amd: silhouette: %d coordinates are not finite (NaN or inf)' % bad)
+        if live < 2:
+            raise ValueError('dca_amd: silhouette: %d cluster%s with points: a silhouette compares at least 2'
+                             % (live, '' if live == 1 else 's'))
+
+    def silhouette(self, X, labels, k, splits=0, ws=None):
+        """K-SILHOUETTE (include/dcahip.h, dcahip_silhouette): the silhouette coefficient of every row of X [n, d] (fp32
+        device tensor, unit column stride, any row stride) under labels [n] (int32 codes in [0, k); any other value: in no
+        cluster), Euclidean, every pair visited.  Returns a dict of device tensors: s, a, b float64 [n] (NaN for a point in no
+        cluster), nearest int32 [n] (-1), counts int32 [k], cluster_mean float64 [k], mean float64 [1].  splits: 0 = the
+        library's choice, 1 .. 64 = that many candidate ranges.  A limit of the kernel (k 2 .. 256, d 1 .. 128), a non-finite
+        coordinate or fewer than two clusters with points raises ValueError."""
+        from .silhouette import check_silhouette_args
+        p = hip.ptr
+        if X.dtype != torch.float32 or X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1):
+            raise ValueError('dca_amd: silhouette: the points are a 2-d float32 tensor with unit column stride')
+        n, d = X.shape
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+            raise ValueError('dca_amd: silhouette: labels is a contiguous int32 tensor of shape (%d,)' % n)
+        k, splits = int(k), int(splits)
+        check_silhouette_args(n, d, k, splits)
+        ldx = X.stride(0) if n > 1 else d
+        dev = X.device
+        need = self.silhouette_workspace_bytes(n, d, k, splits)
+        if ws is None:
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError('dca_amd: silhouette: the workspace holds %d bytes, %d are needed'
+                             % (ws.numel() * ws.element_size(), need))
+        nan = float('nan')
+        r = dict(s=torch.full((n,), nan, dtype=torch.float64, device=dev), a=torch.full((n,), nan, dtype=torch.float64, device=dev),
+                 b=torch.full((n,), nan, dtype=torch.float64, device=dev), nearest=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                 counts=torch.zeros(k, dtype=torch.int32, device=dev),
+                 cluster_mean=torch.full((k,), nan, dtype=torch.float64, device=dev),
+                 mean=torch.full((1,), nan, dtype=torch.float64, device=dev))
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.check(self.L.dcahip_silhouette(p(X) if n else None, ldx, n, d, p(labels) if n else None, k, splits, p(r['s']), p(r['a']),
+                                           p(r['b']), p(r['nearest']), p(r['counts']), p(r['cluster_mean']), p(r['mean']),
+                                           p(ws), p(status), hip.stream()), 'silhouette')
+        self.silhouette_raise(status, r['counts'])
+        return r
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];

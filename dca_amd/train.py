@@ -440,6 +440,21 @@ def train_with_args(args):
         if not 0 <= getattr(args, 'kmeans_seed', 0) < 1 << 64:
             raise ValueError('dca: --kmeans-seed is a non-negative integer below 2^64 (got %d)' % args.kmeans_seed)
 
+    sil = getattr(args, 'silhouette', None)         # --silhouette: refused here, not after the fit
+    if sil is not None:
+        from .silhouette import check_label_count, check_silhouette_args
+        from .groups import label_codes
+        if sil == 'kmeans' and kmeans_k is None:
+            raise ValueError('dca: --silhouette kmeans describes the clusters of --kmeans K: give --kmeans')
+        if sil == 'groups' and labels is None:
+            raise ValueError('dca: --silhouette groups describes the labels of --groupstats FILE: give --groupstats')
+        widths_s = [int(w) for w in args.hiddensize.split(',') if w.strip()]
+        if not widths_s:
+            raise ValueError('dca: --silhouette scores a clustering of the latent space: not for a network without hidden layers')
+        sil_k = kmeans_k if sil == 'kmeans' else len(label_codes(labels)[0])
+        check_label_count(sil_k, '--silhouette ' + sil)
+        check_silhouette_args(adata.n_obs, widths_s[len(widths_s) // 2], sil_k)
+
     subset = None                                   # --denoisesubset: the loss sees these output genes only
     if args.denoisesubset:
         subset = list(set(io.read_genelist(args.denoisesubset)))
@@ -490,6 +505,8 @@ def train_with_args(args):
         klabels = write_kmeans(net, adata, x_in, kmeans_k, getattr(args, 'kmeans_seed', 0), args.outputdir)
         if getattr(args, 'kmeansstats', False):
             write_group_stats(net, adata, x_in, klabels, subset, args.outputdir)
+    if sil is not None:
+        write_silhouette(net, adata, x_in, 'dca_kmeans' if sil == 'kmeans' else labels, args.outputdir)
     if corr_genes is not None:
         write_gene_corr(net, adata, x_in, corr_genes, args.genecorr_log1p, subset, args.outputdir)
 
@@ -568,6 +585,29 @@ def write_kmeans(net, adata, x_in, k, seed, output_dir):
                  columns=['z%d' % (j + 1) for j in range(centers.shape[1])]).to_csv(
         os.path.join(output_dir, 'kmeans_centers.tsv'), sep='\t', float_format='%.6f')
     return labels
+
+
+def write_silhouette(net, adata, x_in, groupby, output_dir):
+    """--silhouette {kmeans,groups}: the silhouette of all cells in the latent space (train and test cells alike:
+    Autoencoder.silhouette) under the clusters of --kmeans or the labels of --groupstats -> silhouette.tsv (index = cell name;
+    label, silhouette with six decimals, nearest = the label of the nearest other cluster; a cell without a label: empty),
+    silhouette_clusters.tsv (index = label; cells, silhouette = the mean over the cluster) and one printed line with the
+    mean over all labelled cells."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    labels = adata.obs[groupby] if isinstance(groupby, str) else groupby
+    net.silhouette(adata, groupby=groupby)
+    u = adata.uns['dca_silhouette']
+    lab = pd.Series(np.asarray(labels, dtype=object), index=pd.Index(adata.obs_names, name='cell'))
+    cells = pd.DataFrame({'label': lab.where(lab.notna(), None),
+                          'silhouette': np.asarray(adata.obs['dca_silhouette'], dtype=np.float64),
+                          'nearest': np.asarray(adata.obs['dca_silhouette_nearest'], dtype=object)}, index=lab.index)
+    cells.to_csv(os.path.join(output_dir, 'silhouette.tsv'), sep='\t', float_format='%.6f')
+    pd.DataFrame({'cells': u['sizes'], 'silhouette': u['cluster_mean']},
+                 index=pd.Index([str(g) for g in u['names']], name='label')).to_csv(
+        os.path.join(output_dir, 'silhouette_clusters.tsv'), sep='\t', float_format='%.6f')
+    print('dca: mean silhouette %.6f (%d cells in %d clusters)' % (u['mean'], int(np.sum(u['sizes'])), len(u['names'])))
 
 
 def read_group_labels(path, adata):

@@ -1005,6 +1005,54 @@ int dcahip_kmeans_seed(const float* X, long ldx, int n, int d, int k, unsigned l
                        int* rows_out, float* C_out, long ldc, void* ws, int* status, void* stream);
 
 /*
+ * K-SILHOUETTE (dca_amd/csrc/dcahip_silhouette.hip): the silhouette coefficient (Rousseeuw 1987) of every labelled row of X
+ * under a clustering, Euclidean, exact: every pair of labelled points is visited, no n x n and no n x k matrix exists.  Beyond
+ * the reference, which leaves the quality of a clustering of obsm['X_dca'] to the host; no reference call site.
+ *
+ *   X [n, ldx]              : the points, d columns (ldx >= d);  1 <= d <= 128, 0 <= n < 2^31
+ *   labels [n] int32        : codes in [0, k), 2 <= k <= 256 (k may exceed n); ANY other value, -1 included, means "in no
+ *                             cluster": such a point is neither a query nor a candidate
+ *   splits                  : 0 = the library's choice, dcahip_silhouette_splits(n, d, k): enough workgroups to fill the part
+ *                             when the query blocks of 256 are few, every split keeping about 1 000 candidates, and the
+ *                             segment partials (below) staying under 256 MiB -- 1 from 392 961 points on; 1 .. 64: this many
+ *                             equal ranges of the sorted candidates (an argument of the call: the library keeps no switch)
+ *   s_out, a_out, b_out [n] double, nearest_out [n] int32 : per point, at its ORIGINAL row (below)
+ *   counts [k] int32        : n_c, the members of every cluster
+ *   cluster_mean [k] double : the mean of s over the members of c (NaN when empty);  mean [1]: over all labelled points
+ *   ws                      : >= dcahip_silhouette_workspace_bytes(n, d, k, splits) bytes, 16-byte aligned, any content.  With
+ *                             r16 = rounding up to 16, DP = the next of 8, 16, 32, 64, 128 from d and nb = the workgroups of
+ *                             the counting sort (<= 1024):  r16(4 nb k) + r16(4 (k + 1)) + 2 r16(4 n) + r16(8 n) + r16(4 n DP)
+ *                             + (splits > 1 ? r16(8 (splits + k - 1) n) : 0)
+ *   status                  : one int32, zeroed by the caller: += the non-finite coordinates met in X (of unlabelled rows
+ *                             too); the outputs are unspecified then, but written in bounds
+ *
+ * delta(i, j) = the correctly rounded fp32 square root of d2(x_i, x_j), d2 the distance of dcahip_knn compiled from the same
+ * definition (csrc/knn_dist.hpp).  S(i, c) = the sum over the j of label c of (double)delta(i, j), in double, j ascending
+ * (j = i included: it adds exactly 0).  a_i = S(i, own) / (n_own - 1);  b_i = the minimum over the non-empty c != own of
+ * S(i, c) / n_c;  nearest_i = the lowest c that attains it;  s_i = (b_i - a_i) / max(a_i, b_i): double division and
+ * subtraction, one rounding each.  Conventions (scikit-learn's where it has one): n_own = 1 gives s = a = 0; max(a, b) = 0
+ * gives s = 0; an unlabelled point has s = a = b = NaN and nearest = -1; with fewer than two non-empty clusters b = +inf,
+ * nearest = -1 and s = NaN for every labelled point.
+ *
+ * The plan is a pure function of (n, d, k, splits): a stable counting sort of the labelled points by label (integer work)
+ * into a zero-padded copy of X in (label, index) order, so that the candidates of a cluster are contiguous; a scan, grid
+ * (query blocks of 256, splits), one lane per query with ONE double accumulator, the candidate row the same for the whole
+ * wave; with more than one split the partial sum of every (split, cluster) segment -- at most splits + k - 1 per query -- goes
+ * to the workspace and a finishing pass adds them in ascending split order; the two means are fixed trees.  No floating-point
+ * atomic: two calls give the same bits, and where the double sums are exact every `splits` gives the same bits.  Plain stores
+ * only (the status counter and the integer counters of the sort aside), every index formed in 64 bits; nothing outside the
+ * documented outputs and the workspace is written.
+ * DCAHIP_EINVAL (nothing launched): k outside 2 .. 256, d outside 1 .. 128, n < 0, splits outside 0 .. 64, ldx < d, a missing
+ * pointer (the two size functions return it for the same shapes).  n = 0 launches nothing and returns 0.
+ */
+int dcahip_silhouette_splits(int n, int d, int k);
+long dcahip_silhouette_workspace_bytes(int n, int d, int k, int splits);
+int dcahip_silhouette(const float* X, long ldx, int n, int d, const int* labels, int k, int splits,
+                      double* s_out, double* a_out, double* b_out, int* nearest_out,
+                      int* counts, double* cluster_mean, double* mean,
+                      void* ws, int* status, void* stream);
+
+/*
  * K-PEER (dca_amd/csrc/dcahip_peer.hip): the small exchanges of the data-parallel step without a library call.
  *   slots[q], flags[q]: device arrays of `world` pointers to every rank's exchange buffers (rank's own: its local
  *   allocation; the others: mapped with hipIpcOpenMemHandle), each dcahip_peer_slot_bytes(world, nmax) /
