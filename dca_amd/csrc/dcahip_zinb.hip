@@ -455,10 +455,15 @@ struct InferArgs {
     int linear_mean;
 };
 
+// clip_by_value as comparisons: a NaN stays a NaN, as in the reference (fminf / fmaxf return their other argument)
+__device__ __forceinline__ float clip_keep_nan(float x, float lo, float hi) {
+    return x < lo ? lo : (x > hi ? hi : x);
+}
+
 // the mean head's activation (dca/network.py:38 MeanAct; the linear mean of ae_type 'normal'): the one expression
 // heads_infer_kernel stores and group_moments_kernel sums
 __device__ __forceinline__ float mean_act(float a, bool linear) {
-    return linear ? a : fminf(fmaxf(expf(a), 1e-5f), 1e6f);
+    return linear ? a : clip_keep_nan(expf(a), 1e-5f, 1e6f);
 }
 
 template <int V>
@@ -485,7 +490,7 @@ __global__ __launch_bounds__(256) void heads_infer_kernel(InferArgs a) {
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float sp = fmaxf(v[j], 0.f) + log1pf(expf(-fabsf(v[j])));
-                o[j] = fminf(fmaxf(sp, 1e-4f), 1e4f);
+                o[j] = clip_keep_nan(sp, 1e-4f, 1e4f);
             }
             stv<V>(a.theta + oo, o);
         }

@@ -151,8 +151,9 @@ int dcahip_nll_marginals(const float* a_mean, const float* a_disp, const float* 
  *                     chunk of rows serves every shorter chunk of the same G and K; needs no initialisation
  *
  * Element value, in fp32 and by the device function dcahip_zinb_heads_infer stores its mean with (the same bits):
- * x = fminf(fmaxf(expf(a), 1e-5f), 1e6f) * sf[row], or a * sf[row] with DCAHIP_NLL_MSE; DCAHIP_GROUP_NO_SF drops the
- * factor, DCAHIP_GROUP_LOG1P takes log1pf of the result.  For every row with 0 <= codes[row] < K:
+ * x = clip(expf(a), 1e-5f, 1e6f) * sf[row] (the clip by comparisons: a NaN stays a NaN), or a * sf[row] with
+ * DCAHIP_NLL_MSE; DCAHIP_GROUP_NO_SF drops the factor, DCAHIP_GROUP_LOG1P takes log1pf of the result.
+ * For every row with 0 <= codes[row] < K:
  *   sum_acc[code * ldg + g] += (double)x,  sumsq_acc[code * ldg + g] += (double)x * (double)x.
  * Any other code leaves the row out (-1 is "in no group"; no code is ever used as an index without the range check).
  *
@@ -224,6 +225,8 @@ int dcahip_step_end(const float* loss, double weight, float* hist, int rows_per_
  * Replaces model.predict / extra_models['dispersion'|'pi'].predict (dca/network.py:188-211,
  * 395-405).  sf is indexed by batch row (no gather).  Outputs may be NULL.  flags &
  * DCAHIP_NLL_MSE: the mean head is linear (ae_type 'normal': mean_sf = a_mean * sf).
+ * A NaN pre-activation gives a NaN output in every head (the clips are comparisons, as tf.clip_by_value).
+ * DCAHIP_EINVAL (nothing launched): B or G <= 0, NULL sf, an output given without its input.
  */
 int dcahip_zinb_heads_infer(const float* a_mean, const float* a_disp, const float* a_pi,
                             long lda, const float* sf, int B, int G,

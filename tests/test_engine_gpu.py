@@ -284,6 +284,28 @@ def test_large_batch_step(ops):
     assert_grads_close(g, rg)
 
 
+@pytest.mark.parametrize('G', [37, 300])
+def test_predict_chunk_subsets_of_the_heads_give_the_same_bits(ops, G):
+    """predict_chunk asks dcahip_zinb_heads_infer for the heads in `want` only (NULL for the others): every subset of
+    {'mean', 'dispersion', 'dropout'} returns, for its heads, the bits of the call that asks for all three."""
+    import itertools
+    n, hs, r0, b = 90, (12, 5, 12), 5, 70
+    X, Y, sf, p = make_problem(n, G, hs, 'zinb-conddisp', True, seed=6)
+    eng = make_engine(ops, 'zinb-conddisp', G, hs, True, 0.0, p, X, Y, sf)
+    eng.reserve(b)
+    heads = ('mean', 'dispersion', 'dropout')
+    bits = lambda t: t.contiguous().view(torch.int32).clone()                                # noqa: E731
+    full = {k: bits(v) for k, v in eng.predict_chunk(r0, b, set(heads)).items()}
+    assert set(full) == set(heads) and all(v.shape == (b, G) for v in full.values())
+    assert len({k: v for k, v in full.items() if bool((v != full['mean']).any())}) == 2     # three different planes
+    for m in (1, 2, 3):
+        for want in itertools.combinations(heads, m):
+            out = eng.predict_chunk(r0, b, set(want))
+            assert set(out) == set(want)
+            for k in want:
+                assert torch.equal(bits(out[k]), full[k]), (want, k)
+
+
 @pytest.fixture(scope='module')
 def c3(ops):
     """BASELINE configs[2] at FULL size, resident in HBM exactly as bench.py builds it: 68 579 x 20 000 synthetic

@@ -130,6 +130,29 @@ def test_kernel_is_deterministic(ops, flags, shape):
     assert torch.equal(a1, b1) and torch.equal(a2, b2)
 
 
+@pytest.mark.parametrize('flags', [0, LOG1P])
+@pytest.mark.parametrize('shape', [SHAPES[1], SHAPES[3]], ids=lambda s: '%dx%d_ld%d_k%d' % s)
+def test_nan_mean_reaches_the_sums_of_its_group_and_gene_only(ops, flags, shape):
+    """One NaN pre-activation of the mean head at (row r, gene g), r in group k: the element is NaN, as it is in what
+    heads_infer_kernel stores (the clip of mean_act keeps NaN, tests/test_heads_infer_gpu.py), so sum and sumsq are NaN at
+    (k, g) and every other entry keeps the bits of the run without the NaN.  On the scalar and on the vector form, g the last
+    gene (at 2051 the last valid column of a ragged quad)."""
+    B, G, ld, K = shape
+    c = _case(flags, shape)
+    r = int(np.flatnonzero(c['codes'] >= 0)[-1])
+    k, g = int(c['codes'][r]), G - 1
+    am = c['am'].copy()
+    am[r, g] = np.nan
+    clean1, clean2 = _call(ops, c, flags, shape)
+    nan1, nan2 = _call(ops, dict(c, am=am), flags, shape)
+    hit = torch.zeros(K, G + 2, dtype=torch.bool, device='cuda')
+    hit[k, g] = True
+    for name, got, clean in (('sum', nan1, clean1), ('sumsq', nan2, clean2)):
+        print('flags %d %s: %s[%d, %d] = %r (without the NaN %r)' % (flags, shape, name, k, g, got[k, g].item(), clean[k, g].item()))
+        assert torch.equal(torch.isnan(got), hit), (name, got[k, g].item())
+        assert torch.equal(got[~hit].view(torch.int64), clean[~hit].view(torch.int64)), name
+
+
 @pytest.mark.parametrize('shape', [SHAPES[3], SHAPES[4]], ids=lambda s: '%dx%d_ld%d_k%d' % s)
 def test_codes_outside_the_range_are_left_out(ops, shape):
     """A code of K, of 10^6 and of -7 behaves as -1 (the documented rule: such a row is in no group and its code is never an
