@@ -2,7 +2,7 @@
 MI355X path: same positionals, flag names, defaults and output files.  The option table below
 restates the reference's flag set; ``--mcv`` (beyond the reference) runs dca_amd/mcv.py; ``--neighbors K`` (beyond the reference) writes the latent space's
 k-nearest-neighbour lists (dca_amd/neighbors.py); ``--groupstats FILE`` (beyond the reference) compares groups of cells on the
-denoised expression (dca_amd/groups.py); ``--kmeans K`` (beyond the reference) clusters the latent space (dca_amd/cluster.py);
+denoised expression (dca_amd/groups.py; ``--groupstats-method wilcoxon``: by the rank-sum test); ``--kmeans K`` (beyond the reference) clusters the latent space (dca_amd/cluster.py);
 ``--silhouette {kmeans,groups}`` (beyond the reference) scores such a clustering (dca_amd/silhouette.py);
 ``--genecorr FILE`` (beyond the reference) correlates genes on the denoised expression (dca_amd/genecorr.py);
 ``--hyper*`` runs dca_amd/hyper.py (the search space and outputs of
@@ -69,6 +69,12 @@ _OPTIONS = [
                                   '(cells not listed are left out).  Writes group_sizes.tsv, group_mean.tsv, group_var.tsv, '
                                   'group_scores.tsv (Welch t against the rest), group_pvals_adj.tsv, group_logfoldchanges.tsv '
                                   'of the log1p of the mean without size factors')),
+    (('--groupstats-method',), dict(dest='groupstats_method', choices=('t-test', 'wilcoxon'), default=None,
+                                    help='the test of --groupstats FILE / --kmeansstats: t-test (default: Welch t) or wilcoxon '
+                                         '(the rank-sum test, every gene sorted on the GPU; group_scores.tsv holds its z score '
+                                         'and group_auroc.tsv is written as well)')),
+    (('--groupstats-tie-correct',), dict(dest='groupstats_tie_correct', action='store_true',
+                                         help='with --groupstats-method wilcoxon: the tie correction of the variance')),
     (('--kmeans',), dict(dest='kmeans', type=int, default=None, metavar='K',
                          help='after the result files: k-means of the cells in the latent space into K clusters (1 .. 256), '
                               'computed on the GPU (kmeans_labels.tsv: cell name and label per line, the format --groupstats '
@@ -97,7 +103,8 @@ _OPTIONS = [
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,
                  checkcounts=True, norminput=True, hyper=False, debug=False, tensorboard=False,
-                 loginput=True, score=False, kmeansstats=False, silhouette=None, genecorr_log1p=False)
+                 loginput=True, score=False, kmeansstats=False, silhouette=None, genecorr_log1p=False,
+                 groupstats_tie_correct=False)
 
 
 def build_parser():

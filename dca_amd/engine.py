@@ -1997,6 +1997,95 @@ class Engine:
             ops.gram(m, lay.ldA, cdev, kdev[s:] if kdev is not None else None, shift, b, g, cross, g, dsum, ws)
         return res
 
+    RANK_MEMORY_SHARE = 0.5      # of the free device memory: what rank_sums' gene-major block may take
+
+    def rank_sums(self, codes, n_groups, reference=None, no_sf=False, log1p=False, gene_block=None, chunk=None):
+        """The Wilcoxon rank-sum statistics of groups of cells on the denoised expression, inference mode, as exact
+        integers: {'rank2': [n_groups, G_out], 'tie': [n_groups, G_out], 'count': [n_groups]} int64 device tensors.
+        codes: int32 [n] (host array or device tensor), the group of every STORAGE row, -1 = in no group (it takes no
+        part).  reference None: rank2 is twice every group's rank sum among all labelled cells; reference r (a group
+        index): twice its Mann-Whitney U against group r.  tie is the sum of t^3 - t over the runs of equal values of the
+        pooled sample of that comparison; a gene with a NaN among the labelled cells holds -1 (include/dcahip.h,
+        dcahip_ranksum).  The value ranked is the one predict_chunk writes as 'mean' (mean * size factor; no_sf: the mean
+        alone; log1p: log1p of either), the same bits.
+
+        A rank needs all cells of a gene at once, so the work goes in blocks of gene_block genes: per chunk of rows
+        predict_chunk's forward pass and its store of the mean, a transpose of the block's columns into a gene-major
+        buffer [gene_block, cells], and after the last chunk one dcahip_ranksum call on the buffer.  EVERY block repeats the
+        forward pass over all cells, so the block is as large as memory allows: gene_block defaults to all genes when
+        the buffer fits RANK_MEMORY_SHARE (half) of the free device memory after the kernel's workspace (68 579 cells x
+        20 000 genes: 5.5 GB, one pass), otherwise to what fits.  Every network type and both residency modes take
+        this path; no targets are needed; training state is not touched."""
+        lay, ops = self.lay, self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: rank_sums() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not hasattr(ops, 'ranksum'):
+            raise NotImplementedError('dca_amd: rank_sums() needs ops with ranksum (ops %s has none)' % ops.name)
+        if self.csr is None and self.X is None:
+            raise ValueError('dca_amd: rank_sums() needs data: load_data / attach_counts first')
+        K = int(n_groups)
+        if not 1 <= K <= 4096:
+            raise ValueError('dca_amd: rank_sums(): %d groups (1 .. 4096)' % K)
+        if log1p and self.flags & 8:
+            raise ValueError("dca_amd: rank_sums(): log1p does not apply to the linear mean of ae_type 'normal': it may "
+                             'be <= -1')
+        host = codes.cpu().numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        if host.shape != (self.n,) or host.dtype.kind not in 'iu':
+            raise ValueError('dca_amd: rank_sums(): codes must be %d integers, one per cell (got %s %s)'
+                             % (self.n, host.dtype, host.shape))
+        if host.size and (host.min() < -1 or host.max() >= K):
+            raise ValueError('dca_amd: rank_sums(): codes must lie in -1 .. %d (found %d .. %d)'
+                             % (K - 1, host.min(), host.max()))
+        ref = -1 if reference is None else int(reference)
+        if not -1 <= ref < K:
+            raise ValueError('dca_amd: rank_sums(): the reference group %d is not one of 0 .. %d' % (ref, K - 1))
+        n, G = self.n, lay.G_out
+        if n > 2097151:
+            raise ValueError('dca_amd: rank_sums(): %d cells (at most 2097151)' % n)
+        if gene_block is not None and int(gene_block) < 1:
+            raise ValueError('dca_amd: rank_sums(): gene_block = %d (at least one gene)' % gene_block)
+        labelled = np.flatnonzero(host >= 0)
+        order = labelled[np.argsort(host[labelled], kind='stable')].astype(np.int32)       # group after group, cells ascending
+        counts = np.bincount(host[labelled], minlength=K).astype(np.int64)
+        gstart = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        rank2, tie = torch.zeros(K, G, **i64), torch.zeros(K, G, **i64)
+        res = {'rank2': rank2, 'tie': tie, 'count': torch.as_tensor(counts).to(self.dev)}
+        m = int(order.size)
+        if m == 0:
+            return res
+        ldn = _r4(n)
+        if gene_block is None:
+            gb = G
+            if self.dev.type == 'cuda':
+                free = torch.cuda.mem_get_info(self.dev)[0]
+                room = self.RANK_MEMORY_SHARE * free - ops.ranksum_workspace_bytes(G, n)
+                gb = int(max(1, min(G, room // (4 * ldn))))
+        else:
+            gb = min(int(gene_block), G)
+        odev, gdev = torch.as_tensor(order).to(self.dev), torch.as_tensor(gstart).to(self.dev)
+        buf = torch.empty(gb, ldn, dtype=torch.float32, device=self.dev)
+        ws = torch.empty(ops.ranksum_workspace_bytes(gb, n), dtype=torch.uint8, device=self.dev)
+        chunk = min(chunk or self.Bmax or 1024, n)
+        self.reserve(chunk)
+        ones = torch.ones(chunk, dtype=torch.float32, device=self.dev) if no_sf else None
+        A = self.A
+        for g0 in range(0, G, gb):
+            g1 = min(g0 + gb, G)
+            for s in range(0, n, chunk):
+                b = min(chunk, n - s)
+                o = self._range_rows(s, b)
+                KL = self._hidden_forward(b, ('range', o), False)
+                self._heads_forward(b, KL)
+                mp = self._plane(A, 'mean')
+                ops.heads_infer(mp, None, None, lay.ldA, ones if no_sf else self.sf[o:], b, G, mp, None, None, lay.ldA,
+                                self.flags & 8)                      # no_sf: x * 1.0f is exact
+                if log1p:
+                    torch.log1p_(mp[:b, :G])
+                ops.transpose(mp[:, g0:], lay.ldA, b, g1 - g0, buf[:, s:], ldn)
+            ops.ranksum(buf, ldn, g1 - g0, n, odev, m, gdev, K, ref, rank2[:, g0:], tie[:, g0:], G, ws)
+        return res
+
     def predict_chunk(self, r0, b, want):
         """Inference forward over storage rows [r0, r0+b).  Returns device views (valid until
         the next call): dict with 'mean' (mean*sf), 'dispersion', 'dropout', 'latent'."""

@@ -4,6 +4,9 @@ adjusted p-values and log fold changes.
 
 The only pass over cells x genes runs on the device (Engine.group_moments -> dcahip_group_moments: per group the sums of
 x and x^2 of every gene, in double); everything here is host arithmetic on [groups, genes] float64 arrays.
+``method='wilcoxon'`` replaces Welch's t by the Wilcoxon rank-sum test, the test scanpy's tutorials recommend for this
+step: Engine.rank_sums -> dcahip_ranksum sorts every gene on the device and returns exact integer rank sums and tie terms,
+wilcoxon_from_ranks turns them into z scores and p-values here.
 ``Autoencoder.group_stats`` is the public entry; ``rank_genes_groups`` re-lays its result the way scanpy's function of
 that name leaves its own.
 """
@@ -12,6 +15,22 @@ import pandas as pd
 
 MAX_GROUPS = 4096            # include/dcahip.h, dcahip_group_moments
 VALUES = ('denoised', 'normalized')
+METHODS = ('t-test', 'wilcoxon')
+MAX_RANK_CELLS = 2097151     # include/dcahip.h, dcahip_ranksum: t^3 of a run of that many equal values fits 63 bits
+
+
+def check_ranksum_args(g, n, m=0, K=1, ref=-1):
+    """The limits of dcahip_ranksum (include/dcahip.h) as ValueErrors that name them."""
+    if g < 1 or n < 1:
+        raise ValueError('dca_amd: ranksum: %d genes of %d cells (at least one of each)' % (g, n))
+    if n > MAX_RANK_CELLS:
+        raise ValueError('dca_amd: ranksum: %d cells (at most %d)' % (n, MAX_RANK_CELLS))
+    if not 0 <= m <= n:
+        raise ValueError('dca_amd: ranksum: %d labelled cells of %d' % (m, n))
+    if not 1 <= K <= MAX_GROUPS:
+        raise ValueError('dca_amd: ranksum: %d groups (1 .. %d)' % (K, MAX_GROUPS))
+    if not -1 <= ref < K:
+        raise ValueError('dca_amd: ranksum: the reference group %d is not one of 0 .. %d (or -1: the rest)' % (ref, K - 1))
 
 
 def label_codes(labels, groups=None, reference='rest'):
@@ -82,6 +101,48 @@ def benjamini_hochberg(p):
     return out
 
 
+def wilcoxon_from_ranks(rank2, tie, counts, reference=None, tie_correct=False):
+    """The Wilcoxon rank-sum test of every group [K, G] from the integers of dcahip_ranksum (Engine.rank_sums): dict with
+    scores (z), pvals (two-sided, normal approximation, no continuity correction, as scanpy's 'wilcoxon'), pvals_adj
+    (Benjamini-Hochberg per group), auroc = U / (n_c n_other) and U itself.
+
+    reference None: rank2 / 2 is the rank sum R of group c among all N = sum(counts) cells: z = (R - n_c (N + 1) / 2) /
+    sigma, sigma^2 = n_c (N - n_c) (N + 1) / 12, U = R - n_c (n_c + 1) / 2.  reference r: rank2 / 2 is U of c against r, N =
+    n_c + n_r: z = (U - n_c n_r / 2) / sigma, sigma^2 = n_c n_r (N + 1) / 12.  tie_correct multiplies sigma^2 by
+    1 - tie / (N^3 - N).  sigma = 0 gives z = 0, p = 1; an empty side, the reference's own row and a gene marked -1 (a NaN
+    among its cells) give NaN."""
+    from scipy import stats
+    r2, tie = np.asarray(rank2, np.int64), np.asarray(tie, np.int64)
+    n = np.asarray(counts, np.float64).reshape(-1, 1)
+    half = r2.astype(np.float64) / 2.0                                  # rank2 < 2^44: exact
+    if reference is None:
+        N = np.full_like(n, n.sum())
+        no = N - n
+        U = half - n * (n + 1.0) / 2.0
+    else:
+        no = np.full_like(n, n[reference, 0])
+        N = n + no
+        U = half
+    with np.errstate(divide='ignore', invalid='ignore'):
+        var = n * no * (N + 1.0) / 12.0
+        if tie_correct:
+            var = var * (1.0 - tie.astype(np.float64) / (N ** 3 - N))
+        var = np.broadcast_to(var, r2.shape)
+        sigma = np.sqrt(np.maximum(var, 0.0))
+        z = (U - n * no / 2.0) / sigma
+        auroc = U / (n * no)
+    zero = sigma == 0
+    z = np.where(zero, 0.0, z)
+    p = np.where(zero, 1.0, 2.0 * stats.norm.sf(np.abs(z)))
+    bad = np.broadcast_to((n < 1) | (no < 1), r2.shape) | (r2 < 0)
+    if reference is not None:
+        bad = bad.copy()
+        bad[reference] = True
+    z, p, auroc, U = (np.where(bad, np.nan, a) for a in (z, p, auroc, np.broadcast_to(U, r2.shape)))
+    return {'scores': z, 'pvals': p, 'pvals_adj': np.stack([benjamini_hochberg(row) for row in p]) if len(p) else p.copy(),
+            'auroc': auroc, 'U': U}
+
+
 def stats_from_moments(s1, s2, n, log1p=False, reference=None):
     """The statistics of every group [K, G] from the group moments: dict with mean, var, scores, pvals, pvals_adj,
     logfoldchanges.  reference: None = every group against all other cells of the K groups together (their moments are the
@@ -105,11 +166,21 @@ def stats_from_moments(s1, s2, n, log1p=False, reference=None):
 
 
 def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
-                output_subset=None):
+                output_subset=None, method='t-test', tie_correct=False):
     """Autoencoder.group_stats (documented there)."""
     eng = net.engine
     if value not in VALUES:
         raise ValueError('dca_amd: group_stats: value must be one of %s (got %r)' % (', '.join(VALUES), value))
+    if method not in METHODS:
+        raise ValueError('dca_amd: group_stats: method must be one of %s (got %r)' % (', '.join(METHODS), method))
+    if tie_correct and method != 'wilcoxon':
+        raise ValueError("dca_amd: group_stats: tie_correct belongs to method='wilcoxon'")
+    if method == 'wilcoxon' and not hasattr(eng.ops, 'ranksum'):
+        raise NotImplementedError('dca_amd: group_stats: method=\'wilcoxon\' needs ops with ranksum (ops %s has none)'
+                                  % eng.ops.name)
+    if method == 'wilcoxon' and adata.n_obs > MAX_RANK_CELLS:
+        raise ValueError("dca_amd: group_stats: method='wilcoxon' ranks at most %d cells (got %d)"
+                         % (MAX_RANK_CELLS, adata.n_obs))
     if log1p and eng.flags & 8:
         raise ValueError("dca_amd: group_stats: log1p does not apply to ae_type='normal': its mean is linear and may be "
                          '<= -1')
@@ -142,8 +213,13 @@ def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False,
     counts = res['count'].cpu().numpy()
     ref = None if reference == 'rest' else names.index(reference)
     st = stats_from_moments(res['sum'].cpu().numpy(), res['sumsq'].cpu().numpy(), counts, log1p, ref)
+    if method == 'wilcoxon':                            # mean, var and the fold change stay; the test is the rank-sum one
+        rk = eng.rank_sums(codes, len(names), reference=ref, no_sf=(value == 'normalized'), log1p=log1p, chunk=min(chunk, n))
+        wt = wilcoxon_from_ranks(rk['rank2'].cpu().numpy(), rk['tie'].cpu().numpy(), counts, ref, tie_correct)
+        for k in ('scores', 'pvals', 'pvals_adj', 'auroc'):
+            st[k] = wt[k]
     if len(names) < 2:                                  # one group: its moments alone; nothing to compare it with
-        for k in ('scores', 'pvals', 'pvals_adj', 'logfoldchanges'):
+        for k in ('scores', 'pvals', 'pvals_adj', 'logfoldchanges') + (('auroc',) if method == 'wilcoxon' else ()):
             st[k] = np.full_like(st['mean'], np.nan)
     if cols is not None:                                # genes the network does not fit: NaN
         for k, v in st.items():
@@ -153,6 +229,8 @@ def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False,
     out = {'groupby': key, 'names': np.array(names, dtype=object), 'counts': counts.astype(np.int64), 'value': value,
            'log1p': bool(log1p), 'reference': reference}
     out.update(st)
+    if method == 'wilcoxon':
+        out['method'], out['tie_correct'] = method, bool(tie_correct)
     adata.uns['dca_groups'] = out
     return adata if copy else None
 
@@ -176,7 +254,7 @@ def rank_genes_groups(adata, n_genes=100, key_added='rank_genes_groups'):
     for i, g in groups:
         o = fitted[np.argsort(-d['scores'][i, fitted], kind='stable')]         # NaN sorts last, in index order
         order[g] = o[:rows]
-    out = {'params': {'groupby': d['groupby'], 'reference': d['reference'], 'method': 't-test', 'use_raw': False,
+    out = {'params': {'groupby': d['groupby'], 'reference': d['reference'], 'method': d.get('method', 't-test'), 'use_raw': False,
                       'layer': None, 'corr_method': 'benjamini-hochberg'}}
     width = max([len(str(v)) for v in var_names] + [1])
     out['names'] = np.rec.fromarrays([var_names[order[g]].astype('U%d' % width) for _, g in groups],

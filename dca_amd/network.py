@@ -374,7 +374,7 @@ class Autoencoder():
 
     # ------------------------------------------------------------------ groups of cells on the denoised expression
     def group_stats(self, adata, groupby, groups=None, value='denoised', log1p=False, reference='rest', copy=False,
-                    output_subset=None):
+                    output_subset=None, method='t-test', tie_correct=False):
         """Groups of cells (clusters, conditions, batches) compared on the denoised expression, the cells x genes pass on
         the device (Engine.group_moments -> dcahip_group_moments) -- beyond the reference, whose users run
         ``sc.tl.rank_genes_groups`` on the denoised matrix on the host.  The inputs are bound as ``predict`` binds them.
@@ -389,6 +389,12 @@ class Autoencoder():
         reference   'rest': every group against all other cells that take part; or the one label every other group is
                     compared with (that group's own scores are NaN)
         output_subset   the fitted genes of a gene-subset network, in training order (as ``score`` takes them)
+        method      't-test' (Welch's t from the group moments) or 'wilcoxon': the Wilcoxon rank-sum test, what scanpy's
+                    tutorials recommend here -- every gene is sorted on the device (Engine.rank_sums -> dcahip_ranksum,
+                    exact integer rank sums), scores is the z score of the normal approximation without continuity
+                    correction (scanpy's), pvals its two-sided p-value; mean, var and logfoldchanges stay as they are.
+                    Stores ``auroc`` [K, n_vars] (U / (n_group n_other)), ``method`` and ``tie_correct`` as well
+        tie_correct with 'wilcoxon': the variance is multiplied by 1 - sum(t^3 - t) / (N^3 - N) over the runs of ties
 
         Stores ``adata.uns['dca_groups']``: groupby, names (the sorted labels), counts [K], value, log1p, reference and
         float64 arrays [K, n_vars] ALIGNED to ``var_names`` (not ranked; NaN for the genes a gene-subset network does not
@@ -400,7 +406,7 @@ class Autoencoder():
         if ``copy`` else None, like ``predict``."""
         from .groups import group_stats
         return group_stats(self, adata, groupby, groups=groups, value=value, log1p=log1p, reference=reference, copy=copy,
-                           output_subset=output_subset)
+                           output_subset=output_subset, method=method, tie_correct=tie_correct)
 
     # ------------------------------------------------------------------ gene-gene correlation of the denoised expression
     def gene_correlation(self, adata, genes=None, groupby=None, group=None, value='denoised', log1p=False,

@@ -95,6 +95,37 @@ class HipOps:
         hip.check(self.L.dcahip_gram(p(x), ldx, p(cols), p(keep), p(shift), B, G, p(cross), ldc, p(dsum), p(ws),
                                      hip.stream()), 'gram')
 
+    def ranksum_workspace_bytes(self, g, n):
+        """The workspace of ranksum for g genes of n cells, in bytes (per workgroup of its grid, not per gene)."""
+        from .groups import check_ranksum_args
+        check_ranksum_args(int(g), int(n))
+        nbytes = int(self.L.dcahip_ranksum_workspace_bytes(g, n))
+        hip.check(min(nbytes, 0), 'ranksum_workspace_bytes')
+        return nbytes
+
+    def ranksum(self, x, ldx, g, n, order, m, gstart, K, ref, rank2, tie, ldr, ws):
+        """K-RANKS (include/dcahip.h, dcahip_ranksum): per row of the gene-major fp32 plane x [g, ldx] the m cells order
+        lists (int32 columns, group after group; gstart int32 [K + 1] the group boundaries) are sorted and every group's
+        doubled rank sum (ref = -1) or doubled Mann-Whitney U against group ref, and the tie term sum t^3 - t, are WRITTEN
+        to columns [0, g) of rank2 / tie (int64 [K, ldr]); a row with a NaN among the m cells gets -1.  ws:
+        ranksum_workspace_bytes(g, n) bytes.  A limit of the kernel (K 1 .. 4096, n <= 2 097 151) raises ValueError."""
+        from .groups import check_ranksum_args
+        g, n, m, K, ref = int(g), int(n), int(m), int(K), int(ref)
+        check_ranksum_args(g, n, m, K, ref)
+        if ldx < n or ldr < g:
+            raise ValueError('dca_amd: ranksum: ldx = %d for %d cells, ldr = %d for %d genes' % (ldx, n, ldr, g))
+        if x.dtype != torch.float32 or rank2.dtype != torch.int64 or tie.dtype != torch.int64:
+            raise ValueError('dca_amd: ranksum: x is float32, rank2 and tie are int64')
+        if gstart.dtype != torch.int32 or gstart.numel() < K + 1 or (m and (order.dtype != torch.int32 or order.numel() < m)):
+            raise ValueError('dca_amd: ranksum: order is int32 [%d], gstart int32 [%d]' % (m, K + 1))
+        need = self.ranksum_workspace_bytes(g, n)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError('dca_amd: ranksum: the workspace holds %d bytes, %d are needed'
+                             % (ws.numel() * ws.element_size(), need))
+        p = hip.ptr
+        hip.check(self.L.dcahip_ranksum(p(x), ldx, g, n, p(order) if m else None, m, p(gstart), K, ref, p(rank2), p(tie), ldr,
+                                        p(ws), hip.stream()), 'ranksum')
+
     def loss_finalize(self, partials, n, scale, loss_out):
         hip.check(self.L.dcahip_loss_finalize(hip.ptr(partials), n, scale, hip.ptr(loss_out),
                                               hip.stream()), 'loss_finalize')

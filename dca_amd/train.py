@@ -440,6 +440,18 @@ def train_with_args(args):
         if not 0 <= getattr(args, 'kmeans_seed', 0) < 1 << 64:
             raise ValueError('dca: --kmeans-seed is a non-negative integer below 2^64 (got %d)' % args.kmeans_seed)
 
+    gs_method = getattr(args, 'groupstats_method', None) or 't-test'     # refused here, not after the fit
+    gs_tie = bool(getattr(args, 'groupstats_tie_correct', False))
+    if getattr(args, 'groupstats_method', None) is not None and labels is None and not getattr(args, 'kmeansstats', False):
+        raise ValueError('dca: --groupstats-method names the test of --groupstats FILE or --kmeansstats: give one of them')
+    if gs_tie and gs_method != 'wilcoxon':
+        raise ValueError('dca: --groupstats-tie-correct belongs to --groupstats-method wilcoxon')
+    if gs_method == 'wilcoxon':
+        from .groups import MAX_RANK_CELLS
+        if adata.n_obs > MAX_RANK_CELLS:
+            raise ValueError('dca: --groupstats-method wilcoxon ranks at most %d cells (the input has %d)'
+                             % (MAX_RANK_CELLS, adata.n_obs))
+
     sil = getattr(args, 'silhouette', None)         # --silhouette: refused here, not after the fit
     if sil is not None:
         from .silhouette import check_label_count, check_silhouette_args
@@ -500,11 +512,11 @@ def train_with_args(args):
     if getattr(args, 'neighbors', None):
         write_neighbors(net, adata, x_in, args.neighbors, args.outputdir)
     if labels is not None:
-        write_group_stats(net, adata, x_in, labels, subset, args.outputdir)
+        write_group_stats(net, adata, x_in, labels, subset, args.outputdir, gs_method, gs_tie)
     if kmeans_k is not None:
         klabels = write_kmeans(net, adata, x_in, kmeans_k, getattr(args, 'kmeans_seed', 0), args.outputdir)
         if getattr(args, 'kmeansstats', False):
-            write_group_stats(net, adata, x_in, klabels, subset, args.outputdir)
+            write_group_stats(net, adata, x_in, klabels, subset, args.outputdir, gs_method, gs_tie)
     if sil is not None:
         write_silhouette(net, adata, x_in, 'dca_kmeans' if sil == 'kmeans' else labels, args.outputdir)
     if corr_genes is not None:
@@ -659,21 +671,24 @@ def write_gene_corr(net, adata, x_in, genes, log1p, subset, output_dir):
     write_text_matrix(d['corr'], os.path.join(output_dir, 'gene_corr.tsv'), rownames=names, colnames=names)
 
 
-def write_group_stats(net, adata, x_in, labels, subset, output_dir):
+def write_group_stats(net, adata, x_in, labels, subset, output_dir, method='t-test', tie_correct=False):
     """--groupstats FILE: the groups of FILE compared on log1p of the denoised mean without size factors (train and test
     cells alike: Autoencoder.group_stats(value='normalized', log1p=True), every group against the rest) -> group_sizes.tsv
     (index = group; cells) and, genes x groups with a header, group_mean.tsv, group_var.tsv, group_scores.tsv,
     group_logfoldchanges.tsv (six decimals) and group_pvals_adj.tsv (%.6e); the genes a --denoisesubset network does not
-    fit: empty."""
+    fit: empty.  --groupstats-method wilcoxon: scores and p-values of the rank-sum test (--groupstats-tie-correct: with
+    the tie correction) and group_auroc.tsv (six decimals) beside them."""
     import pandas as pd
     if adata.X is not x_in:
         adata.X = x_in
-    net.group_stats(adata, labels, value='normalized', log1p=True, output_subset=subset)
+    extra = {} if method == 't-test' else {'method': method, 'tie_correct': bool(tie_correct)}
+    net.group_stats(adata, labels, value='normalized', log1p=True, output_subset=subset, **extra)
     d = adata.uns['dca_groups']
     names = [str(g) for g in d['names']]
     pd.DataFrame({'cells': d['counts']}, index=pd.Index(names, name='group')).to_csv(
         os.path.join(output_dir, 'group_sizes.tsv'), sep='\t')
     genes = pd.Index(adata.var_names)
-    for key, fmt in (('mean', '%.6f'), ('var', '%.6f'), ('scores', '%.6f'), ('pvals_adj', '%.6e'), ('logfoldchanges', '%.6f')):
+    files = (('mean', '%.6f'), ('var', '%.6f'), ('scores', '%.6f'), ('pvals_adj', '%.6e'), ('logfoldchanges', '%.6f'))
+    for key, fmt in files + ((('auroc', '%.6f'),) if method == 'wilcoxon' else ()):
         pd.DataFrame(d[key].T, index=genes, columns=names).to_csv(os.path.join(output_dir, 'group_%s.tsv' % key), sep='\t',
                                                                   float_format=fmt)

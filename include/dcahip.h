@@ -173,6 +173,46 @@ int dcahip_group_moments(const float* a_mean, long lda, const float* sf, const i
                          double* workspace, void* stream);
 
 /*
+ * K-RANKS (dca_amd/csrc/dcahip_ranksum.hip): the Wilcoxon rank-sum (Mann-Whitney) statistics of groups of cells, gene by
+ * gene, as exact integers -- what scanpy's rank_genes_groups(method='wilcoxon') sorts every gene on the host for, without the
+ * cells x genes matrix leaving the device.  The sort is this library's own (a stable LSD radix sort per gene).
+ *
+ *   x, ldx          : GENE-MAJOR fp32: g rows (genes) of n cell values, row stride ldx >= n (dcahip_transpose_rows writes it)
+ *   order           : [m] int32, the labelled cells as DISTINCT column numbers of x, group after group; a cell that is
+ *                     not listed takes no part (whatever it holds, NaN included)
+ *   gstart          : [K + 1] int32, starts at 0, does not decrease, ends at m: positions gstart[c] .. gstart[c + 1] of
+ *                     order are group c (the caller's responsibility; a group code is clamped before it is an index)
+ *   ref             : -1 = every group against the pooled labelled cells; 0 <= ref < K = every group against group ref
+ *   rank2, tie, ldr : [K][ldr] 64-bit integers, WRITTEN (not added to) in columns [0, g); columns >= g are not touched
+ *   workspace       : >= dcahip_ranksum_workspace_bytes(g, n) bytes, 16-byte aligned, any content: a status word, the
+ *                     group code of every position of order, and per WORKGROUP of the persistent grid (min(g, 512), 256
+ *                     for n > 262 144) two uint32 [n] and two uint16 [n] arrays -- it does not grow with g beyond the grid.
+ *                     The query returns DCAHIP_EINVAL for g <= 0, n <= 0 or n > 2 097 151
+ *
+ * Per row the m values are ordered as real numbers: -0.0f ties with +0.0f, denormals and +-inf take their natural place;
+ * inside a run [a, b) (0-based sorted positions) of equal values ties keep group order.  With P(p) the number of cells of
+ * group ref at sorted positions below p, every cell i of group c of row j adds to rank2[c * ldr + j]
+ *   ref < 0 :  a_i + b_i + 1    twice the cell's mid-rank: rank2 is twice the rank sum of group c
+ *   ref >= 0:  P(a_i) + P(b_i)  twice the Mann-Whitney U of c against ref (a ref cell below counts 2, a tied one 1)
+ * and tie[c * ldr + j] is the sum of t^3 - t over the runs of the pooled sample of that comparison: all m cells with ref < 0
+ * (the same number for every c), the cells of c and ref together with ref >= 0, t counting only those (row ref: ref alone).
+ * A group without cells gets rank2 = 0; m == 0 writes zeros.
+ * A row whose m values hold a NaN gets -1 in every rank2 and tie entry of that row, the other rows are not affected.  An
+ * order entry outside [0, n) is never used as an index: every row gets -1 instead.
+ *
+ * Integers throughout (64-bit accumulators; n <= 2 097 151 keeps t^3 below 2^63), no floating-point atomics: the results
+ * are exact and identical from run to run.  The time of a row does not depend on its ties (no thread walks along a run).
+ * 1 <= K <= 4096, 0 <= m <= n <= 2 097 151.
+ * DCAHIP_EINVAL (nothing launched): NULL x / gstart / rank2 / tie / workspace, NULL order with m > 0, ldx < n, ldr < g,
+ * g <= 0, n <= 0 or above the limit, m outside 0 .. n, K outside 1 .. 4096, ref outside -1 .. K - 1.
+ */
+long dcahip_ranksum_workspace_bytes(int g, int n);
+int dcahip_ranksum(const float* x, long ldx, int g, int n,
+                   const int* order, int m, const int* gstart, int K, int ref,
+                   long long* rank2, long long* tie, long ldr,
+                   void* workspace, void* stream);
+
+/*
  * K-GRAM: centred cross-products of selected columns of an fp32 plane, in double -- what a gene-gene correlation of the
  * denoised expression starts from (covariance = (cross - dsum dsum^T / n) / (n - 1)), without the cells x genes matrix
  * leaving the device.
