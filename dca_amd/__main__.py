@@ -83,7 +83,18 @@ _OPTIONS = [
                               help='with --kmeans: the group_*.tsv files of --groupstats for the k-means clusters (not together '
                                    'with --groupstats)')),
     (('--kmeans-seed',), dict(dest='kmeans_seed', type=int, default=0, metavar='N', help='seed of the k-means++ draws (default: 0)')),
-    (('--silhouette',), dict(dest='silhouette', choices=('kmeans', 'groups'), default=None,
+    (('--louvain',), dict(dest='louvain', action='store_true',
+                          help='after the result files: Louvain communities of the cells\' neighbour graph in the latent space '
+                               '(--neighbors K other cells each, 15 when absent), computed on the GPU; the number of clusters '
+                               'follows from the graph (louvain_labels.tsv: cell name and label per line, the format '
+                               '--groupstats reads) and the modularity is printed')),
+    (('--louvain-resolution',), dict(dest='louvain_resolution', type=float, default=None, metavar='R',
+                                     help='with --louvain: the resolution of the modularity, 1/1024 .. 64 (default: 1.0; '
+                                          'larger: more, smaller clusters)')),
+    (('--louvainstats',), dict(dest='louvainstats', action='store_true',
+                               help='with --louvain: the group_*.tsv files of --groupstats for the Louvain clusters (not '
+                                    'together with --groupstats or --kmeansstats)')),
+    (('--silhouette',), dict(dest='silhouette', choices=('kmeans', 'groups', 'louvain'), default=None,
                              help='after the result files: the silhouette coefficient of every cell in the latent space, '
                                   'computed on the GPU, under the clusters of --kmeans K (kmeans) or the labels of --groupstats '
                                   'FILE (groups); writes silhouette.tsv (cell, label, silhouette, nearest other cluster) and '
@@ -103,7 +114,7 @@ _OPTIONS = [
 
 _DEFAULTS = dict(transpose=False, testsplit=False, saveweights=False, sizefactors=True, batchnorm=True,
                  checkcounts=True, norminput=True, hyper=False, debug=False, tensorboard=False,
-                 loginput=True, score=False, kmeansstats=False, silhouette=None, genecorr_log1p=False,
+                 loginput=True, score=False, kmeansstats=False, louvain=False, louvainstats=False, silhouette=None, genecorr_log1p=False,
                  groupstats_tie_correct=False)
 
 

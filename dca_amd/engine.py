@@ -2212,6 +2212,22 @@ class Engine:
         latent = self._latent_all(chunk)
         return latent, ops.silhouette(latent, codes, k)
 
+    def latent_louvain(self, n_neighbors=15, resolution=1.0, max_levels=32, max_sweeps=1000, chunk=None):
+        """Louvain communities of the cells' neighbour graph in the latent space, on the device: the latent and its k nearest
+        neighbours exactly as latent_knn gives them, then dca_amd.community.louvain on the indices (dcahip_graph_symmetrize /
+        dcahip_louvain_sweep); no index leaves the device.  Returns (latent [n, h] float32, idx [n, k] int32, d2 [n, k]
+        float32, community.LouvainResult of device tensors).  Training state is not touched."""
+        ops = self.ops
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: latent_louvain() does not apply to data-parallel runs (%d processes)' % self.comm.world)
+        if not hasattr(ops, 'louvain_level'):
+            raise NotImplementedError('dca_amd: latent_louvain() needs ops with louvain_level (ops %s has none)' % ops.name)
+        from .community import check_louvain_args, louvain
+        check_louvain_args(self.n, int(n_neighbors), resolution, max_levels, max_sweeps)
+        latent, idx, d2 = self.latent_knn(n_neighbors, chunk=chunk)
+        return latent, idx, d2, louvain(idx, resolution=resolution, max_levels=max_levels, max_sweeps=max_sweeps, ops=ops,
+                                        on_device=True)
+
     def heads_gene_block(self, g0, gb, want, out):
         """The heads of genes [g0, g0 + gb) for ALL cells, written gene-major: out[k] [gb, >= n] device tensors for k in
         want (mean = mean * size factor, dispersion, dropout) -- a [n, hL] x [hL, gb] product per head, the inference

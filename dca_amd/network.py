@@ -351,6 +351,54 @@ class Autoencoder():
                                            'seed': int(seed)}}
         return adata if copy else None
 
+    def louvain(self, adata, n_neighbors=15, resolution=1.0, key_added='dca_louvain', copy=False, max_levels=32,
+                max_sweeps=1000):
+        """Louvain communities of these cells' neighbour graph in the latent space, computed on the device
+        (Engine.latent_louvain -> dcahip_knn, dcahip_graph_symmetrize, dcahip_louvain_sweep; dca_amd.community.louvain
+        documents the algorithm) -- beyond the reference, which leaves community detection to scanpy on the host.  The number
+        of clusters follows from the graph and ``resolution``.  The inputs are bound as ``predict`` binds them.  Stores
+
+            adata.obsm['X_dca'], adata.obsm['dca_knn_indices'], adata.obsm['dca_knn_distances'], adata.uns['dca_neighbors']
+                                       exactly what ``neighbors(adata, n_neighbors)`` stores
+            adata.obs[key_added]       pandas categorical of the strings '0' .. (categories in numeric order), clusters
+                                       numbered by size descending
+            adata.uns[key_added]       {'modularity', 'sizes' int64, 'level_sizes', 'n_levels', 'n_sweeps',
+                                        'params': {'n_neighbors', 'resolution' (the quantised value used), 'max_levels',
+                                                   'max_sweeps'}}
+
+        ``group_stats(adata, key_added)`` and ``silhouette(adata, key_added)`` follow with no glue.  Returns ``adata`` if
+        ``copy`` else None, like ``predict``."""
+        import pandas as pd
+        from .community import check_louvain_args
+        from .neighbors import check_knn_args
+        eng = self.engine
+        self._wanted('latent', False)                     # hidden_size=(): no centre layer
+        k, n = int(n_neighbors), adata.n_obs
+        if k > n - 1:
+            raise ValueError('dca_amd: louvain: n_neighbors = %d, but every one of the %d cells has only %d others'
+                             % (k, n, n - 1))
+        check_knn_args(n, n, eng.lay.hidden[eng.center], k)
+        check_louvain_args(n, k, resolution, max_levels, max_sweeps)
+        if eng.comm.world > 1:
+            raise ValueError('dca_amd: louvain() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        adata = adata.copy() if copy else adata
+        self._bind_inputs(adata)
+        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
+        latent, idx, d2, res = eng.latent_louvain(k, resolution=resolution, max_levels=max_levels, max_sweeps=max_sweeps,
+                                                  chunk=min(chunk, n))
+        adata.obsm['X_dca'] = latent.cpu().numpy()
+        adata.obsm['dca_knn_indices'] = idx.cpu().numpy()
+        adata.obsm['dca_knn_distances'] = np.sqrt(d2.cpu().numpy())
+        adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
+        sizes = res.sizes.cpu().numpy().astype(np.int64)
+        cats = [str(c) for c in range(len(sizes))]
+        adata.obs[key_added] = pd.Categorical.from_codes(res.labels.cpu().numpy().astype(np.int64), categories=cats)
+        adata.uns[key_added] = {'modularity': float(res.modularity), 'sizes': sizes, 'level_sizes': list(res.level_sizes),
+                                'n_levels': int(res.n_levels), 'n_sweeps': list(res.n_sweeps),
+                                'params': {'n_neighbors': k, 'resolution': float(res.resolution),
+                                           'max_levels': int(max_levels), 'max_sweeps': int(max_sweeps)}}
+        return adata if copy else None
+
     def silhouette(self, adata, groupby='dca_kmeans', key_added='dca_silhouette', copy=False):
         """The silhouette coefficient of every cell in the latent space under a clustering, computed on the device
         (Engine.latent_silhouette -> dcahip_silhouette; dca_amd.silhouette documents the number) -- beyond the reference,

@@ -806,6 +806,49 @@ class HipOps:
         self.silhouette_raise(status, r['counts'])
         return r
 
+    def graph_symmetrize_workspace_bytes(self, n, k):
+        """The workspace of graph_symmetrize for an [n, k] index array, in bytes."""
+        from .community import check_graph_args
+        check_graph_args(int(n), int(k))
+        nbytes = int(self.L.dcahip_graph_symmetrize_workspace_bytes(n, k))
+        hip.check(min(nbytes, 0), 'graph_symmetrize_workspace_bytes')
+        return nbytes
+
+    def graph_symmetrize(self, idx):
+        """K-LOUVAIN (include/dcahip.h, dcahip_graph_symmetrize): W = A + A^T of the index array idx [n, k] (int32 device
+        tensor, unit column stride; -1 is padding, an entry equal to its row is dropped) as a CSR of unit entries.  Returns
+        (rowptr int64 [n + 1], col int32 [2m], deg int32 [n]); the order inside a row is not fixed.  Reads 2m (a
+        synchronisation).  An entry outside 0 .. n-1 other than -1, or a limit of the kernel (2 n k < 2^31), raises
+        ValueError."""
+        from .community import check_graph_args
+        p = hip.ptr
+        if idx.dtype != torch.int32 or idx.dim() != 2 or (idx.shape[1] > 1 and idx.stride(1) != 1):
+            raise ValueError('dca_amd: louvain: the neighbour indices are a 2-d int32 tensor with unit column stride')
+        n, k = idx.shape
+        check_graph_args(n, k)
+        dev = idx.device
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        deg = torch.zeros(n, dtype=torch.int32, device=dev)
+        cap = 2 * n * k
+        col = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        if n == 0:
+            return rowptr, col[:0], deg
+        ws = torch.empty(max(self.graph_symmetrize_workspace_bytes(n, k), 16), dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.check(self.L.dcahip_graph_symmetrize(p(idx), idx.stride(0) if n > 1 else k, n, k, p(rowptr), p(col), cap, p(deg),
+                                                 p(ws), p(status), hip.stream()), 'graph_symmetrize')
+        bad = int(status.item())
+        if bad:
+            raise ValueError('dca_amd: louvain: %d neighbour indices lie outside 0 .. %d (and are not the padding -1)' % (bad, n - 1))
+        return rowptr, col[:int(rowptr[n].item())], deg
+
+    def louvain_level(self, rowptr, col, wt, twom, g, max_sweeps, labels=None, best_q=None):
+        """K-LOUVAIN (include/dcahip.h, dcahip_louvain_begin / dcahip_louvain_sweep): one level on the CSR graph (rowptr int64
+        [n + 1], col int32 [nnz], wt int32 [nnz] or None for unit weights), the arguments checked once.  It starts from
+        singletons, or from ``labels`` (int32 [n]) with ``best_q`` the integer Q the first sweep has to exceed.  Returns a
+        LouvainLevel: ``sweep(s)`` enqueues sweep s = 0, 1, .., ``read(s)`` the state after it (a synchronisation)."""
+        return LouvainLevel(self, rowptr, col, wt, twom, g, max_sweeps, labels, best_q)
+
     def csr_gather(self, csr, perm, cursor, row0, B, sf, fac, do_log, mean, std, Y, ldy, X, ldx, sf_out, status):
         """The minibatch tile of a resident CSR (prep.CsrCounts): storage rows perm[*cursor + r] (perm given) or row0 + r ->
         every element of Y[:B, :ldy], X[:B, :ldx] (X = the normalised input, None: not written), sf_out[:B] = sf[row];
@@ -863,3 +906,60 @@ class HipOps:
 
     def rmsprop_clip(self, w, g, ms, n, lr, rho, eps, clip):
         self.rmsprop_clip_end(w, g, ms, n, lr, rho, eps, clip, None, 0.0, None, 0, None, None, 0)
+
+
+class LouvainLevel:
+    """One level of K-LOUVAIN on the device (HipOps.louvain_level).  ``labels`` / ``tot``: the current (best) state;
+    ``labels_new``: what the last sweep decided, kept or not; ``ki``: the weighted degrees."""
+
+    def __init__(self, ops, rowptr, col, wt, twom, g, max_sweeps, labels=None, best_q=None):
+        from .community import check_level_args
+        n = rowptr.numel() - 1
+        nnz = col.numel()
+        twom, g, max_sweeps = int(twom), int(g), int(max_sweeps)
+        check_level_args(n, nnz, twom, g, max_sweeps)
+        if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or not rowptr.is_contiguous() or not col.is_contiguous() or \
+                (wt is not None and (wt.dtype != torch.int32 or wt.numel() != nnz or not wt.is_contiguous())):
+            raise ValueError('dca_amd: louvain: the graph is rowptr int64 [n + 1], col int32 [nnz], wt int32 [nnz] or None')
+        dev = rowptr.device
+        p = hip.ptr
+        self.n, self.g, self.twom = n, g, twom
+        self.ki = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.labels = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.tot = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.labels_new = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.tot_new = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.state = torch.zeros(24, dtype=torch.int64, device=dev)
+        self._keep = (rowptr, col, wt)
+        graph = (n, nnz, p(rowptr), p(col) if nnz else None, p(wt) if wt is not None and nnz else None)
+        L = ops.L
+        hip.check(L.dcahip_louvain_begin(*graph, p(self.ki) if n else None, p(self.labels) if n else None,
+                                         p(self.tot) if n else None, twom, g, p(self.state), hip.stream()), 'louvain_begin')
+        if labels is not None:
+            if labels.dtype != torch.int32 or tuple(labels.shape) != (n,):
+                raise ValueError('dca_amd: louvain: labels is an int32 tensor of shape (%d,)' % n)
+            if n and (int(labels.min()) < 0 or int(labels.max()) >= n):
+                raise ValueError('dca_amd: louvain: labels lie in 0 .. %d' % (n - 1))
+            self.labels.copy_(labels)
+            self.tot.zero_().index_add_(0, labels.long(), self.ki)
+            q = int(best_q)
+            if not -(1 << 127) <= q < 1 << 127:
+                raise ValueError('dca_amd: louvain: best_q is a 128-bit integer')
+            self.state[2] = self.state[10] = (q & ((1 << 64) - 1)) - ((1 << 64) if q & (1 << 63) else 0)
+            self.state[3] = self.state[11] = q >> 64
+        tail = (p(self.ki), p(self.labels), p(self.tot), p(self.labels_new), p(self.tot_new)) if n else (None,) * 5
+        fn, st = L.dcahip_louvain_sweep, p(self.state)
+
+        def sweep(s):
+            hip.check(fn(*graph, *tail, twom, g, int(s), max_sweeps, st, hip.stream()), 'louvain_sweep')
+        self.sweep = sweep
+
+    def read(self, s):
+        """The state after sweep s: dict of done (0 running, 1 Q did not rise, 2 two idle sweeps, 3 max_sweeps), sweeps, q
+        (the best integer Q), idle, kept (whether sweep s was), and the sums of sweep s: moved, inside, tot2."""
+        w = [int(v) for v in self.state.cpu().tolist()]
+        st = w[8 * ((s + 1) & 1):][:8]
+        sm = w[16 + 4 * (s & 1):][:4]
+        u = lambda v: v & ((1 << 64) - 1)
+        return dict(done=st[0], sweeps=st[1], q=(st[3] << 64) | u(st[2]), idle=st[4], kept=bool(st[5]), moved=u(sm[0]),
+                    inside=u(sm[1]), tot2=u(sm[2]))

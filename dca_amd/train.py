@@ -442,7 +442,8 @@ def train_with_args(args):
 
     gs_method = getattr(args, 'groupstats_method', None) or 't-test'     # refused here, not after the fit
     gs_tie = bool(getattr(args, 'groupstats_tie_correct', False))
-    if getattr(args, 'groupstats_method', None) is not None and labels is None and not getattr(args, 'kmeansstats', False):
+    if getattr(args, 'groupstats_method', None) is not None and labels is None and not getattr(args, 'kmeansstats', False) \
+            and not getattr(args, 'louvainstats', False):
         raise ValueError('dca: --groupstats-method names the test of --groupstats FILE or --kmeansstats: give one of them')
     if gs_tie and gs_method != 'wilcoxon':
         raise ValueError('dca: --groupstats-tie-correct belongs to --groupstats-method wilcoxon')
@@ -452,8 +453,37 @@ def train_with_args(args):
             raise ValueError('dca: --groupstats-method wilcoxon ranks at most %d cells (the input has %d)'
                              % (MAX_RANK_CELLS, adata.n_obs))
 
+    louv = bool(getattr(args, 'louvain', False))    # --louvain / --louvainstats / --louvain-resolution: refused here too
+    louv_k = getattr(args, 'neighbors', None) or 15
+    louv_res = getattr(args, 'louvain_resolution', None)
+    if getattr(args, 'louvainstats', False):
+        if not louv:
+            raise ValueError('dca: --louvainstats describes the clusters of --louvain: give --louvain')
+        if labels is not None or getattr(args, 'kmeansstats', False):
+            raise ValueError('dca: --louvainstats, --kmeansstats and --groupstats all write the group_*.tsv files: give one of them')
+        if args.type == 'normal':
+            raise ValueError("dca: --louvainstats compares log1p of the mean: not for --type normal, whose mean is linear")
+    if louv_res is not None and not louv:
+        raise ValueError('dca: --louvain-resolution belongs to --louvain: give --louvain')
+    if louv:
+        from .community import check_louvain_args
+        from .neighbors import check_knn_args
+        widths_l = [int(w) for w in args.hiddensize.split(',') if w.strip()]
+        if not widths_l:
+            raise ValueError('dca: --louvain clusters the latent space: not for a network without hidden layers')
+        check_knn_args(adata.n_obs, adata.n_obs, widths_l[len(widths_l) // 2], louv_k)
+        if louv_k > adata.n_obs - 1:
+            raise ValueError('dca: --louvain: %d neighbours, but every one of the %d cells has only %d others'
+                             % (louv_k, adata.n_obs, adata.n_obs - 1))
+        check_louvain_args(adata.n_obs, louv_k, 1.0 if louv_res is None else louv_res)
+
     sil = getattr(args, 'silhouette', None)         # --silhouette: refused here, not after the fit
-    if sil is not None:
+    if sil == 'louvain':
+        from .silhouette import check_silhouette_args
+        if not louv:
+            raise ValueError('dca: --silhouette louvain describes the clusters of --louvain: give --louvain')
+        check_silhouette_args(adata.n_obs, widths_l[len(widths_l) // 2], 2)
+    elif sil is not None:
         from .silhouette import check_label_count, check_silhouette_args
         from .groups import label_codes
         if sil == 'kmeans' and kmeans_k is None:
@@ -517,8 +547,12 @@ def train_with_args(args):
         klabels = write_kmeans(net, adata, x_in, kmeans_k, getattr(args, 'kmeans_seed', 0), args.outputdir)
         if getattr(args, 'kmeansstats', False):
             write_group_stats(net, adata, x_in, klabels, subset, args.outputdir, gs_method, gs_tie)
+    if louv:
+        llabels = write_louvain(net, adata, x_in, louv_k, 1.0 if louv_res is None else louv_res, args.outputdir)
+        if getattr(args, 'louvainstats', False):
+            write_group_stats(net, adata, x_in, llabels, subset, args.outputdir, gs_method, gs_tie)
     if sil is not None:
-        write_silhouette(net, adata, x_in, 'dca_kmeans' if sil == 'kmeans' else labels, args.outputdir)
+        write_silhouette(net, adata, x_in, {'kmeans': 'dca_kmeans', 'louvain': 'dca_louvain'}.get(sil, labels), args.outputdir)
     if corr_genes is not None:
         write_gene_corr(net, adata, x_in, corr_genes, args.genecorr_log1p, subset, args.outputdir)
 
@@ -596,6 +630,23 @@ def write_kmeans(net, adata, x_in, k, seed, output_dir):
     pd.DataFrame(centers, index=pd.Index([str(c) for c in range(k)], name='cluster'),
                  columns=['z%d' % (j + 1) for j in range(centers.shape[1])]).to_csv(
         os.path.join(output_dir, 'kmeans_centers.tsv'), sep='\t', float_format='%.6f')
+    return labels
+
+
+def write_louvain(net, adata, x_in, k, resolution, output_dir):
+    """--louvain: Louvain communities of all cells' neighbour graph in the latent space (train and test cells alike:
+    Autoencoder.louvain) -> louvain_labels.tsv (`cell name<TAB>label`, no header: the format --groupstats reads) and one
+    printed line with the clusters and the modularity.  Returns the labels, one string per cell."""
+    import pandas as pd
+    if adata.X is not x_in:
+        adata.X = x_in
+    net.louvain(adata, n_neighbors=k, resolution=resolution)
+    labels = np.asarray(adata.obs['dca_louvain']).astype(str).astype(object)
+    pd.DataFrame({'label': labels}, index=pd.Index(adata.obs_names)).to_csv(
+        os.path.join(output_dir, 'louvain_labels.tsv'), sep='\t', header=False)
+    u = adata.uns['dca_louvain']
+    print('dca: louvain: %d clusters, modularity %.6f (%d neighbours, resolution %g, %d levels)'
+          % (len(u['sizes']), u['modularity'], k, u['params']['resolution'], u['n_levels']))
     return labels
 
 

@@ -1096,6 +1096,58 @@ int dcahip_silhouette(const float* X, long ldx, int n, int d, const int* labels,
                       void* ws, int* status, void* stream);
 
 /*
+ * K-LOUVAIN (dca_amd/csrc/dcahip_louvain.hip): Louvain modularity optimisation (Blondel et al. 2008) of the neighbour graph
+ * dcahip_knn writes, on the device, in integers throughout: the labels equal those of the host restatement
+ * (tests/_louvain_ref.py) and are the same on every run.  Beyond the reference, which leaves community detection on
+ * obsm['X_dca'] to scanpy on the host; no reference call site.
+ *
+ * dcahip_graph_symmetrize: W = A + A^T of the directed 0/1 adjacency A of an index array, as a CSR of unit entries.
+ *   idx [n, ldi] int32      : k columns (ldi >= k >= 1).  -1 is padding; an entry equal to its row is dropped; any other entry
+ *                             outside 0 .. n-1 adds 1 to *status and is never used as an index
+ *   rowptr [n + 1] int64    : OUT the row starts; rowptr[n] = 2m, the number of entries
+ *   col [cap] int32         : OUT the neighbours, cap >= 2 n k entries of room.  A mutual pair stands twice in both rows.  The
+ *                             order inside a row may differ from run to run (an integer atomic hands out the places)
+ *   deg [n] int32           : OUT the rows' lengths = the weighted degrees k_i
+ *   ws                      : >= dcahip_graph_symmetrize_workspace_bytes(n, k) bytes, 16-byte aligned, any content
+ *   status                  : one int32, zeroed by the caller
+ *   Six launches (histogram, three of a scan, fill).  DCAHIP_EINVAL (nothing launched): n < 0, k < 1, ldi < k,
+ *   2 n k >= 2^31, cap < 2 n k, a missing pointer.  n = 0 writes rowptr[0] = 0.
+ *
+ * The level.  A CSR graph of n vertices: rowptr [n + 1] int64, col [nnz] int32, wt [nnz] int32 (NULL: every entry weighs 1);
+ * an undirected edge stands in both rows, a self-loop (col = row) once, carrying the weight inside a merged community in both
+ * directions.  k_i = the sum of row i, 2m = the sum of all k_i < 2^31.  R = 1024, g = round(resolution R) in 1 .. 64 R,
+ * M = 2m R.  Every vertex carries a community label in 0 .. n-1; tot_c = the sum of k_i over the members of c.
+ *   A sweep is synchronous: every vertex decides from `labels` and `tot` as they stand.  With a its own community and k_{i,c}
+ *   the weight from i to community c (self-loop excluded): staying scores k_{i,a} M - g k_i (tot_a - k_i), moving to a
+ *   neighbouring c != a scores k_{i,c} M - g k_i tot_c; an even sweep admits only c < a, an odd one only c > a; the vertex
+ *   takes the admissible c of the highest score if that is strictly above staying, ties to the lowest c.  The products (up to
+ *   2^78) are formed in 128 bits.  Then, from the NEW labels: in = the weight inside the communities (both directions plus
+ *   self-loops), tot2 = the sum of tot_c^2, Q = M in - g tot2 (modularity = Q / ((2m)^2 R)).
+ *   state [24] int64        : two slots of 8 words, read at slot sweep & 1 and written at the other -- done (0 running, 1 Q did
+ *                             not rise, 2 two idle sweeps in a row, 3 max_sweeps), sweeps run, best Q (low word, high word),
+ *                             idle sweeps in a row, 1 if this sweep was kept -- and from word 16 two slots of 4 words with the
+ *                             sweep's sums: vertices moved, in, tot2 (slot sweep & 1 holds them after the call)
+ *   A sweep that moves nothing is idle: two in a row end the level.  A sweep that moves something is kept if its Q exceeds the
+ *   best so far -- labels_new and tot_new are copied over labels and tot -- and is otherwise discarded, which ends the level.
+ *   After the level's end every sweep is an exact no-op (nothing but the state's other slot is written), so a host may read
+ *   the state every few sweeps only: the result does not depend on how often it looks.
+ * dcahip_louvain_begin: labels[i] = i, ki = tot = the row sums, state = the start of a level whose best Q is that of the
+ *   singletons.  dcahip_louvain_sweep: sweep number `sweep` (0, 1, ..; its parity picks the direction and the slot), four
+ *   launches; labels_new [n], tot_new [n] are scratch and outputs (the labels decided, kept or not).
+ * Integer atomics only, plain stores, every index formed in 64 bits; a column or label outside 0 .. n-1 is skipped, never an
+ * index.  DCAHIP_EINVAL (nothing launched): n < 0, nnz or twom outside 0 .. 2^31 - 1, g outside 1 .. 65536, sweep < 0,
+ * max_sweeps < 1, a missing pointer.
+ */
+long dcahip_graph_symmetrize_workspace_bytes(int n, int k);
+int dcahip_graph_symmetrize(const int* idx, long ldi, int n, int k, long* rowptr, int* col, long cap, int* deg,
+                            void* ws, int* status, void* stream);
+int dcahip_louvain_begin(int n, long nnz, const long* rowptr, const int* col, const int* wt, int* ki, int* labels, int* tot,
+                         long twom, int g, long* state, void* stream);
+int dcahip_louvain_sweep(int n, long nnz, const long* rowptr, const int* col, const int* wt, const int* ki, int* labels,
+                         int* tot, int* labels_new, int* tot_new, long twom, int g, int sweep, int max_sweeps, long* state,
+                         void* stream);
+
+/*
  * K-PEER (dca_amd/csrc/dcahip_peer.hip): the small exchanges of the data-parallel step without a library call.
  *   slots[q], flags[q]: device arrays of `world` pointers to every rank's exchange buffers (rank's own: its local
  *   allocation; the others: mapped with hipIpcOpenMemHandle), each dcahip_peer_slot_bytes(world, nmax) /
