@@ -11,6 +11,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._device import as_points, default_ops, device_of
+
 MAX_CLUSTERS = 256      # the limits of the kernels (include/dcahip.h)
 MAX_D = 128
 CHECK_EVERY = 8         # Lloyd iterations between two reads of the device's convergence state (the result does not depend on it)
@@ -86,21 +88,11 @@ def kmeans(X, n_clusters, n_init=10, max_iter=300, seed=0, init=None, ops=None, 
     iteration.  Host input gives numpy arrays, a device tensor gives device tensors.  Runs on the GPU (there is no host
     fallback); 1 <= n_clusters <= min(256, n), d <= 128; non-finite input raises ValueError."""
     import torch
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
+    ops = default_ops(ops)
     if on_device is None:                                 # tensors out for a device tensor in (the engine asks for them)
         on_device = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = X.device if isinstance(X, torch.Tensor) and X.is_cuda else \
-        torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu')
-
-    def tensor(a):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
-        if a.dim() != 2:
-            raise ValueError('dca_amd: kmeans: points are the rows of a 2-d array (got %d dimensions)' % a.dim())
-        return a.to(device=dev, dtype=torch.float32).contiguous()
-    Xt = tensor(X)
+    dev = device_of(X, ops)
+    Xt = as_points(X, dev, 'kmeans')
     n, d = Xt.shape
     k, n_init, max_iter, seed = int(n_clusters), int(n_init), int(max_iter), int(seed)
     check_kmeans_args(n, d, k)
@@ -112,7 +104,7 @@ def kmeans(X, n_clusters, n_init=10, max_iter=300, seed=0, init=None, ops=None, 
         raise ValueError('dca_amd: kmeans: seed is an unsigned 64-bit integer (got %d)' % seed)
     C0 = None
     if init is not None:
-        C0 = tensor(init)
+        C0 = as_points(init, dev, 'kmeans')
         if tuple(C0.shape) != (k, d):
             raise ValueError('dca_amd: kmeans: init must be [%d, %d] centres (got %s)' % (k, d, tuple(C0.shape)))
         n_init = 1

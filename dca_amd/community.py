@@ -13,6 +13,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._device import default_ops, device_of
+
 R = 1024                # the denominator of the quantised resolution
 MAX_G = 64 * R
 CHECK_EVERY = 8         # sweeps between two reads of the device's state (the result does not depend on it)
@@ -95,13 +97,6 @@ def aggregate(rowptr, col, wt, cu, nc):
     return out, (ukey - r * nc).to(torch.int32), wsum.to(torch.int32)
 
 
-def _device_of(x, ops):
-    import torch
-    if isinstance(x, torch.Tensor) and x.is_cuda:
-        return x.device
-    return torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu')
-
-
 def _indices(indices, dev):
     import torch
     if not isinstance(indices, torch.Tensor):
@@ -145,12 +140,10 @@ def louvain(indices, resolution=1.0, max_levels=32, max_sweeps=1000, ops=None, c
     ``details=True`` returns (result, dict of q_int, twom, g) for tests and tools."""
     import torch
     from .cluster import renumber
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
+    ops = default_ops(ops)
     if on_device is None:                                 # tensors out for a device tensor in (the engine asks for them)
         on_device = isinstance(indices, torch.Tensor) and indices.is_cuda
-    dev = _device_of(indices, ops)
+    dev = device_of(indices, ops)
     idx = _indices(indices, dev)
     n, k = idx.shape
     g = check_louvain_args(n, k, resolution, max_levels, max_sweeps)
@@ -200,10 +193,8 @@ def modularity(indices, labels, resolution=1.0, ops=None):
     one community per distinct value.  The integers are formed on the device; the float is Q_int / ((2m)^2 1024), the number
     ``louvain`` reports for its own labels."""
     import torch
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
-    dev = _device_of(indices, ops)
+    ops = default_ops(ops)
+    dev = device_of(indices, ops)
     g = quantise(resolution)
     idx = _indices(indices, dev)
     if not isinstance(labels, torch.Tensor):

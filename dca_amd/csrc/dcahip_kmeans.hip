@@ -42,18 +42,13 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr unsigned kInfBits = 0x7F800000u;
 constexpr int kMaxK = 256, kMaxD = 128, kNT = 256;
 constexpr int kStage = 4096;                // floats of one staged chunk of centres (16 KiB)
 constexpr int kAccLds = 5120;               // doubles of LDS accumulators (40 KiB)
 constexpr int kBlocksLds = 512, kBlocksWs = 128, kSeedBlocks = 1024;
 
-inline int pad_d(int d) { return d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 128; }
-inline long r16(long x) { return (x + 15) / 16 * 16; }
 
 bool shape_ok(int n, int d, int k) { return n >= 0 && d >= 1 && d <= kMaxD && k >= 1 && k <= kMaxK; }
-
-__device__ __forceinline__ int nonfinite(float v) { return (__float_as_uint(v) & kInfBits) == kInfBits ? 1 : 0; }
 
 struct Plan {
     int dp, lds, G, tpb, nb;

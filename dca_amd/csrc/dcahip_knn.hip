@@ -32,7 +32,6 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr unsigned kInfBits = 0x7F800000u;
 constexpr int kMaxK = 64, kMaxD = 128, kMaxSplits = 64;
 constexpr int kMinPerSplit = 1024;          // a split keeps about this many candidates: below, its list fill dominates
 constexpr int kTargetBlocks = 1536;         // six workgroups per CU of the 256-CU part: measured, 68 579 x 32 x 15
@@ -40,10 +39,8 @@ constexpr int kTargetBlocks = 1536;         // six workgroups per CU of the 256-
 
 __host__ __device__ inline u64 empty_key(int slot) { return ((u64)kInfBits << 32) | (0x80000000u + (unsigned)slot); }
 
-inline int pad_d(int d) { return d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 128; }
 inline int pad_k(int k) { return k <= 16 ? 16 : k <= 32 ? 32 : 64; }
 inline int scan_threads(int kp) { return kp == 64 ? 128 : 256; }          // [kp][threads] keys = at most 64 KiB of LDS
-inline long r16(long x) { return (x + 15) / 16 * 16; }
 
 bool shape_ok(int nq, int n, int d, int k) { return nq >= 0 && n >= 0 && d >= 1 && d <= kMaxD && k >= 1 && k <= kMaxK; }
 

@@ -38,15 +38,12 @@
 
 namespace {
 
-constexpr unsigned kInfBits = 0x7F800000u;
 constexpr int kMaxK = 256, kMaxD = 128, kMaxSplits = 64, kNT = 256;
 constexpr int kSortBlocks = 1024;           // workgroups of the counting sort: [kSortBlocks][k] counters at most (1 MiB)
 constexpr int kMinPerSplit = 1024;          // a split keeps about this many candidates
 constexpr int kTargetBlocks = 1536;         // six workgroups per CU of the 256-CU part, as K-NEIGHBOURS
 constexpr long kPartialBudget = 256l << 20; // bytes of segment partials the library's own choice of splits stays under
 
-inline int pad_d(int d) { return d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 128; }
-inline long r16(long x) { return (x + 15) / 16 * 16; }
 
 bool shape_ok(int n, int d, int k) { return n >= 0 && d >= 1 && d <= kMaxD && k >= 2 && k <= kMaxK; }
 
@@ -87,7 +84,6 @@ Plan make_plan(int n, int d, int k, int splits) {
     return p;
 }
 
-__device__ __forceinline__ int nonfinite(float v) { return (__float_as_uint(v) & kInfBits) == kInfBits ? 1 : 0; }
 __device__ __forceinline__ double d_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 __device__ __forceinline__ double d_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
 

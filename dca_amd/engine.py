@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import prep as _prep
+from ._device import default_ops, device_of
 
 BN_MOMENTUM = 0.99   # keras BatchNormalization defaults (network.py:127-128)
 BN_EPS = 1e-3
@@ -289,16 +290,11 @@ class Engine:
         if ae_type not in AE_HEADS:
             raise NotImplementedError('ae_type %r is not available on the MI355X path yet '
                                       '(supported: %s)' % (ae_type, ', '.join(AE_HEADS)))
-        if ops is None:
-            from .ops import HipOps
-            ops = HipOps()                              # raises without the HIP library / a GPU
-        self.ops = ops
+        self.ops = ops = default_ops(ops)               # raises without the HIP library / a GPU
         self.comm = comm or SingleProcess()
         from . import config as _config
         self.cfg = config if config is not None else _config.current()      # every path decision below reads this
-        self.dev = torch.device(device) if device is not None else (
-            torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda'
-            else torch.device('cpu'))
+        self.dev = torch.device(device) if device is not None else device_of(None, ops)
         output_size = input_size if output_size is None else output_size
         self.lay = ParamLayout(ae_type, input_size, output_size, hidden_size, batchnorm, prelu=(activation == 'PReLU'))
         self.ridge = float(ridge)
@@ -1818,16 +1814,80 @@ class Engine:
         return s
 
     # ------------------------------------------------------------------ evaluation / inference
-    def eval_loss_sum(self, r0, r1, scale, chunk=None):
-        """Adds scale * sum of element-wise NLL over storage rows [r0, r1) (inference mode) to
-        acc[1] (Keras validation pass, train.py:97)."""
-        lay, ops = self.lay, self.ops
-        chunk = chunk or self.Bmax
+    def _forward_chunks(self, r0, r1, chunk, heads=True):
+        """The inference forward over storage rows [r0, r1), `chunk` rows at a time, along the path predict_chunk takes:
+        yields (s, b, o) -- first row, rows, their offset in the device buffers (_range_rows) -- once the hidden stack and,
+        with `heads`, the heads' pre-activation planes of those rows are in place."""
         for s in range(r0, r1, chunk):
             b = min(chunk, r1 - s)
             o = self._range_rows(s, b)
             KL = self._hidden_forward(b, ('range', o), False)
-            self._heads_forward(b, KL)
+            if heads:
+                self._heads_forward(b, KL)
+            yield s, b, o
+
+    def _chunk_rows(self, chunk, rows):
+        """Rows per chunk of a pass over `rows` rows, reserved."""
+        chunk = min(chunk or self.Bmax or 1024, rows)
+        self.reserve(chunk)
+        return chunk
+
+    def _pass_ready(self, what, op, latent=False, data=True):
+        """The opening guards of an inference pass `what`, in the order every pass checks them: one process, (latent) a
+        centre layer, ops with the entry `op`, (data) data attached."""
+        if self.comm.world > 1:
+            raise ValueError('dca_amd: %s() does not apply to data-parallel runs (%d processes)' % (what, self.comm.world))
+        if latent and not self.lay.hidden:
+            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
+        if not hasattr(self.ops, op):
+            raise NotImplementedError('dca_amd: %s() needs ops with %s (ops %s has none)' % (what, op, self.ops.name))
+        if data and self.csr is None and self.X is None:
+            raise ValueError('dca_amd: %s() needs data: load_data / attach_counts first' % what)
+
+    def _row_range(self, what, r0, r1):
+        """r1 (None: all rows) of a pass over storage rows [r0, r1), checked."""
+        r1 = self.n if r1 is None else r1
+        if not 0 <= r0 <= r1 <= self.n:
+            raise ValueError('dca_amd: %s() rows [%d, %d) are not inside [0, %d)' % (what, r0, r1, self.n))
+        return r1
+
+    def _no_log1p_on_linear(self, what, log1p):
+        if log1p and self.flags & 8:
+            raise ValueError("dca_amd: %s(): log1p does not apply to the linear mean of ae_type 'normal': it may be <= -1"
+                             % what)
+
+    def _group_codes(self, what, codes, n_groups, log1p):
+        """(host, K): the group codes of every storage row as a checked host array and the number of groups.  The log1p
+        refusal sits between the checks of K and of the codes, where group_moments and rank_sums have it."""
+        K = int(n_groups)
+        if not 1 <= K <= 4096:
+            raise ValueError('dca_amd: %s(): %d groups (1 .. 4096)' % (what, K))
+        self._no_log1p_on_linear(what, log1p)
+        host = codes.cpu().numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
+        if host.shape != (self.n,) or host.dtype.kind not in 'iu':
+            raise ValueError('dca_amd: %s(): codes must be %d integers, one per cell (got %s %s)'
+                             % (what, self.n, host.dtype, host.shape))
+        if host.size and (host.min() < -1 or host.max() >= K):
+            raise ValueError('dca_amd: %s(): codes must lie in -1 .. %d (found %d .. %d)'
+                             % (what, K - 1, host.min(), host.max()))
+        return host, K
+
+    def _value_plane(self, b, o, no_sf, log1p, ones):
+        """The value predict_chunk writes as 'mean' for the b rows at offset o, in place on the mean head's plane (mean *
+        size factor; no_sf: times `ones`, exact; log1p: log1p of either).  Returns the plane."""
+        lay = self.lay
+        m = self._plane(self.A, 'mean')
+        self.ops.heads_infer(m, None, None, lay.ldA, ones if no_sf else self.sf[o:], b, lay.G_out, m, None, None, lay.ldA,
+                             self.flags & 8)
+        if log1p:
+            torch.log1p_(m[:b, :lay.G_out])
+        return m
+
+    def eval_loss_sum(self, r0, r1, scale, chunk=None):
+        """Adds scale * sum of element-wise NLL over storage rows [r0, r1) (inference mode) to
+        acc[1] (Keras validation pass, train.py:97)."""
+        lay, ops = self.lay, self.ops
+        for s, b, o in self._forward_chunks(r0, r1, chunk or self.Bmax):
             n = self._nll(b, None, None, self.Y[o:], self.sf[o:], 1.0, False)
             ops.loss_finalize(self.partials, n, scale, self.val_loss_tmp)
             ops.step_end(self.val_loss_tmp, 1.0, None, 0, self.acc[1:], None, 0)
@@ -1840,30 +1900,20 @@ class Engine:
         (dcahip_nll_marginals), so every network type and both residency modes take the same path.  Training state
         (parameters, optimizer slots, acc, cursor, moving statistics) is not touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: score() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not hasattr(ops, 'nll_marginals'):
-            raise NotImplementedError('dca_amd: score() needs ops with nll_marginals (ops %s has none)' % ops.name)
+        self._pass_ready('score', 'nll_marginals', data=False)
         if self.csr is None and (self.Y is None or not self.has_targets):
             raise ValueError('dca_amd: score() needs the targets Y: this engine has none (load_data(X, None, sf) attaches '
                              'inputs only)')
-        r1 = self.n if r1 is None else r1
-        if not 0 <= r0 <= r1 <= self.n:
-            raise ValueError('dca_amd: score() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        r1 = self._row_range('score', r0, r1)
         f64 = dict(dtype=torch.float64, device=self.dev)
         cell, gene = torch.zeros(r1 - r0, **f64), torch.zeros(lay.G_out, **f64)
         if r1 == r0:
             return {'cell': cell, 'gene': gene}
-        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
-        self.reserve(chunk)
+        chunk = self._chunk_rows(chunk, r1 - r0)
         ws = torch.zeros(ops.nll_marginals_workspace_doubles(chunk, lay.G_out), **f64)
         tw = lay.view(self.w, 'theta_w') if lay.const_disp else None
         A = self.A
-        for s in range(r0, r1, chunk):
-            b = min(chunk, r1 - s)
-            o = self._range_rows(s, b)
-            KL = self._hidden_forward(b, ('range', o), False)
-            self._heads_forward(b, KL)
+        for s, b, o in self._forward_chunks(r0, r1, chunk):
             ops.nll_marginals(self._plane(A, 'mean'), self._plane(A, 'disp'), self._plane(A, 'pi'), lay.ldA, tw,
                               self.Y[o:], self.ldy, self.sf[o:], b, lay.G_out, self.ridge, self.flags,
                               cell[s - r0:], gene, ws)
@@ -1878,28 +1928,9 @@ class Engine:
         (dcahip_group_moments), so every network type and both residency modes take the same path.  No targets are
         needed; training state is not touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: group_moments() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not hasattr(ops, 'group_moments'):
-            raise NotImplementedError('dca_amd: group_moments() needs ops with group_moments (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: group_moments() needs data: load_data / attach_counts first')
-        K = int(n_groups)
-        if not 1 <= K <= 4096:
-            raise ValueError('dca_amd: group_moments(): %d groups (1 .. 4096)' % K)
-        if log1p and self.flags & 8:
-            raise ValueError("dca_amd: group_moments(): log1p does not apply to the linear mean of ae_type 'normal': it may "
-                             'be <= -1')
-        host = codes.cpu().numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
-        if host.shape != (self.n,) or host.dtype.kind not in 'iu':
-            raise ValueError('dca_amd: group_moments(): codes must be %d integers, one per cell (got %s %s)'
-                             % (self.n, host.dtype, host.shape))
-        if host.size and (host.min() < -1 or host.max() >= K):
-            raise ValueError('dca_amd: group_moments(): codes must lie in -1 .. %d (found %d .. %d)'
-                             % (K - 1, host.min(), host.max()))
-        r1 = self.n if r1 is None else r1
-        if not 0 <= r0 <= r1 <= self.n:
-            raise ValueError('dca_amd: group_moments() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        self._pass_ready('group_moments', 'group_moments')
+        host, K = self._group_codes('group_moments', codes, n_groups, log1p)
+        r1 = self._row_range('group_moments', r0, r1)
         f64 = dict(dtype=torch.float64, device=self.dev)
         s1, s2 = torch.zeros(K, lay.G_out, **f64), torch.zeros(K, lay.G_out, **f64)
         inside = host[r0:r1]
@@ -1908,16 +1939,11 @@ class Engine:
         if r1 == r0:
             return res
         cdev = torch.as_tensor(np.ascontiguousarray(host, dtype=np.int32)).to(self.dev)
-        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
-        self.reserve(chunk)
+        chunk = self._chunk_rows(chunk, r1 - r0)
         ws = torch.zeros(ops.group_moments_workspace_doubles(chunk, lay.G_out, K), **f64)
         flags = (self.flags & 8) | (16 if no_sf else 0) | (32 if log1p else 0)
         A = self.A
-        for s in range(r0, r1, chunk):
-            b = min(chunk, r1 - s)
-            o = self._range_rows(s, b)
-            KL = self._hidden_forward(b, ('range', o), False)
-            self._heads_forward(b, KL)
+        for s, b, o in self._forward_chunks(r0, r1, chunk):
             ops.group_moments(self._plane(A, 'mean'), lay.ldA, self.sf[o:], cdev[s:], b, lay.G_out, K, flags,
                               s1, s2, lay.G_out, ws)
         return res
@@ -1935,15 +1961,8 @@ class Engine:
         its store of the mean, then one dcahip_gram call on that plane, so every network type and both residency modes
         take the same path.  No targets are needed; training state is not touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: gene_gram() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not hasattr(ops, 'gram'):
-            raise NotImplementedError('dca_amd: gene_gram() needs ops with gram (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: gene_gram() needs data: load_data / attach_counts first')
-        if log1p and self.flags & 8:
-            raise ValueError("dca_amd: gene_gram(): log1p does not apply to the linear mean of ae_type 'normal': it may be "
-                             '<= -1')
+        self._pass_ready('gene_gram', 'gram')
+        self._no_log1p_on_linear('gene_gram', log1p)
         chost = cols.cpu().numpy() if isinstance(cols, torch.Tensor) else np.asarray(cols)
         if chost.ndim != 1 or chost.dtype.kind not in 'iu' or chost.size < 1:
             raise ValueError('dca_amd: gene_gram(): cols must be a 1-d integer array of at least one gene (got %s %s)'
@@ -1963,9 +1982,7 @@ class Engine:
                 raise ValueError('dca_amd: gene_gram(): keep must be %d flags, one per cell (got %s %s)'
                                  % (self.n, khost.dtype, khost.shape))
             khost = khost != 0
-        r1 = self.n if r1 is None else r1
-        if not 0 <= r0 <= r1 <= self.n:
-            raise ValueError('dca_amd: gene_gram() rows [%d, %d) are not inside [0, %d)' % (r0, r1, self.n))
+        r1 = self._row_range('gene_gram', r0, r1)
         f64 = dict(dtype=torch.float64, device=self.dev)
         cross, dsum, shift = torch.zeros(g, g, **f64), torch.zeros(g, **f64), torch.zeros(g, **f64)
         res = {'cross': cross, 'dsum': dsum, 'shift': shift,
@@ -1974,22 +1991,12 @@ class Engine:
             return res
         cdev = torch.as_tensor(np.ascontiguousarray(chost, dtype=np.int32)).to(self.dev)
         kdev = torch.as_tensor(khost.astype(np.int32)).to(self.dev) if khost is not None else None
-        chunk = min(chunk or self.Bmax or 1024, r1 - r0)
-        self.reserve(chunk)
+        chunk = self._chunk_rows(chunk, r1 - r0)
         nws = ops.gram_workspace_doubles(chunk, g)
         ws = torch.zeros(nws, **f64) if nws else None
         ones = torch.ones(chunk, dtype=torch.float32, device=self.dev) if no_sf else None
-        A = self.A
-        for s in range(r0, r1, chunk):
-            b = min(chunk, r1 - s)
-            o = self._range_rows(s, b)
-            KL = self._hidden_forward(b, ('range', o), False)
-            self._heads_forward(b, KL)
-            m = self._plane(A, 'mean')
-            ops.heads_infer(m, None, None, lay.ldA, ones if no_sf else self.sf[o:], b, lay.G_out, m, None, None, lay.ldA,
-                            self.flags & 8)                      # no_sf: x * 1.0f is exact
-            if log1p:
-                torch.log1p_(m[:b, :lay.G_out])
+        for s, b, o in self._forward_chunks(r0, r1, chunk):
+            m = self._value_plane(b, o, no_sf, log1p, ones)
             if s == r0:
                 rows = m[:b] if kdev is None else m[:b][kdev[s:s + b] != 0]
                 if rows.shape[0]:
@@ -2017,25 +2024,8 @@ class Engine:
         20 000 genes: 5.5 GB, one pass), otherwise to what fits.  Every network type and both residency modes take
         this path; no targets are needed; training state is not touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: rank_sums() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not hasattr(ops, 'ranksum'):
-            raise NotImplementedError('dca_amd: rank_sums() needs ops with ranksum (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: rank_sums() needs data: load_data / attach_counts first')
-        K = int(n_groups)
-        if not 1 <= K <= 4096:
-            raise ValueError('dca_amd: rank_sums(): %d groups (1 .. 4096)' % K)
-        if log1p and self.flags & 8:
-            raise ValueError("dca_amd: rank_sums(): log1p does not apply to the linear mean of ae_type 'normal': it may "
-                             'be <= -1')
-        host = codes.cpu().numpy() if isinstance(codes, torch.Tensor) else np.asarray(codes)
-        if host.shape != (self.n,) or host.dtype.kind not in 'iu':
-            raise ValueError('dca_amd: rank_sums(): codes must be %d integers, one per cell (got %s %s)'
-                             % (self.n, host.dtype, host.shape))
-        if host.size and (host.min() < -1 or host.max() >= K):
-            raise ValueError('dca_amd: rank_sums(): codes must lie in -1 .. %d (found %d .. %d)'
-                             % (K - 1, host.min(), host.max()))
+        self._pass_ready('rank_sums', 'ranksum')
+        host, K = self._group_codes('rank_sums', codes, n_groups, log1p)
         ref = -1 if reference is None else int(reference)
         if not -1 <= ref < K:
             raise ValueError('dca_amd: rank_sums(): the reference group %d is not one of 0 .. %d' % (ref, K - 1))
@@ -2066,22 +2056,12 @@ class Engine:
         odev, gdev = torch.as_tensor(order).to(self.dev), torch.as_tensor(gstart).to(self.dev)
         buf = torch.empty(gb, ldn, dtype=torch.float32, device=self.dev)
         ws = torch.empty(ops.ranksum_workspace_bytes(gb, n), dtype=torch.uint8, device=self.dev)
-        chunk = min(chunk or self.Bmax or 1024, n)
-        self.reserve(chunk)
+        chunk = self._chunk_rows(chunk, n)
         ones = torch.ones(chunk, dtype=torch.float32, device=self.dev) if no_sf else None
-        A = self.A
         for g0 in range(0, G, gb):
             g1 = min(g0 + gb, G)
-            for s in range(0, n, chunk):
-                b = min(chunk, n - s)
-                o = self._range_rows(s, b)
-                KL = self._hidden_forward(b, ('range', o), False)
-                self._heads_forward(b, KL)
-                mp = self._plane(A, 'mean')
-                ops.heads_infer(mp, None, None, lay.ldA, ones if no_sf else self.sf[o:], b, G, mp, None, None, lay.ldA,
-                                self.flags & 8)                      # no_sf: x * 1.0f is exact
-                if log1p:
-                    torch.log1p_(mp[:b, :G])
+            for s, b, o in self._forward_chunks(0, n, chunk):
+                mp = self._value_plane(b, o, no_sf, log1p, ones)
                 ops.transpose(mp[:, g0:], lay.ldA, b, g1 - g0, buf[:, s:], ldn)
             ops.ranksum(buf, ldn, g1 - g0, n, odev, m, gdev, K, ref, rank2[:, g0:], tie[:, g0:], G, ws)
         return res
@@ -2134,21 +2114,12 @@ class Engine:
         alike), only the centre layer kept ([n, h]: 8.8 MB at 68 579 x 32, 192 MB at 1.5 M cells), then ops.knn on it
         (dcahip_knn, self_offset = 0).  Returns (latent [n, h] float32, idx [n, k] int32, d2 [n, k] float32 -- SQUARED
         Euclidean distances, every row ascending in (d2, index)) as device tensors.  Training state is not touched."""
-        lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: latent_knn() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not lay.hidden:
-            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
-        if not hasattr(ops, 'knn'):
-            raise NotImplementedError('dca_amd: latent_knn() needs ops with knn (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: latent_knn() needs data: load_data / attach_counts first')
-        n, h = self.n, lay.hidden[self.center]
-        k = int(k)
+        self._pass_ready('latent_knn', 'knn', latent=True)
+        n, k = self.n, int(k)
         if not 1 <= k <= n - 1:
             raise ValueError('dca_amd: latent_knn(): k = %d neighbours of %d cells (every cell has %d others)' % (k, n, n - 1))
         latent = self._latent_all(chunk)
-        idx, d2 = ops.knn(latent, latent, k, self_offset=0, splits=splits)
+        idx, d2 = self.ops.knn(latent, latent, k, self_offset=0, splits=splits)
         return latent, idx, d2
 
     def _latent_all(self, chunk=None):
@@ -2156,12 +2127,8 @@ class Engine:
         chunk by chunk along the path predict_chunk takes (dense and counts-resident data alike).  What latent_knn and
         latent_kmeans work on; training state is not touched."""
         n, h = self.n, self.lay.hidden[self.center]
-        chunk = min(chunk or self.Bmax or 1024, n)
-        self.reserve(chunk)
         latent = torch.empty(n, h, dtype=torch.float32, device=self.dev)
-        for s in range(0, n, chunk):
-            b = min(chunk, n - s)
-            self._hidden_forward(b, ('range', self._range_rows(s, b)), False)
+        for s, b, o in self._forward_chunks(0, n, self._chunk_rows(chunk, n), heads=False):
             latent[s:s + b].copy_(self.Z[self.center][:b, :h])
         return latent
 
@@ -2171,14 +2138,7 @@ class Engine:
         cluster.KMeansResult of device tensors: labels, centers, inertia, n_iter, converged, sizes).  Training state is not
         touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: latent_kmeans() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not lay.hidden:
-            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
-        if not hasattr(ops, 'kmeans_step'):
-            raise NotImplementedError('dca_amd: latent_kmeans() needs ops with kmeans_step (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: latent_kmeans() needs data: load_data / attach_counts first')
+        self._pass_ready('latent_kmeans', 'kmeans_step', latent=True)
         from .cluster import check_kmeans_args, kmeans
         k = int(k)
         check_kmeans_args(self.n, lay.hidden[self.center], k)
@@ -2193,14 +2153,7 @@ class Engine:
         ops.silhouette on it (dcahip_silhouette).  Returns (latent [n, h] float32, dict of device tensors: s, a, b, nearest,
         counts, cluster_mean, mean).  Training state is not touched."""
         lay, ops = self.lay, self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: latent_silhouette() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not lay.hidden:
-            raise ValueError('No such layer: center (hidden_size=() has no latent representation)')
-        if not hasattr(ops, 'silhouette'):
-            raise NotImplementedError('dca_amd: latent_silhouette() needs ops with silhouette (ops %s has none)' % ops.name)
-        if self.csr is None and self.X is None:
-            raise ValueError('dca_amd: latent_silhouette() needs data: load_data / attach_counts first')
+        self._pass_ready('latent_silhouette', 'silhouette', latent=True)
         from .silhouette import check_silhouette_args
         k = int(k)
         check_silhouette_args(self.n, lay.hidden[self.center], k)
@@ -2217,16 +2170,12 @@ class Engine:
         neighbours exactly as latent_knn gives them, then dca_amd.community.louvain on the indices (dcahip_graph_symmetrize /
         dcahip_louvain_sweep); no index leaves the device.  Returns (latent [n, h] float32, idx [n, k] int32, d2 [n, k]
         float32, community.LouvainResult of device tensors).  Training state is not touched."""
-        ops = self.ops
-        if self.comm.world > 1:
-            raise ValueError('dca_amd: latent_louvain() does not apply to data-parallel runs (%d processes)' % self.comm.world)
-        if not hasattr(ops, 'louvain_level'):
-            raise NotImplementedError('dca_amd: latent_louvain() needs ops with louvain_level (ops %s has none)' % ops.name)
+        self._pass_ready('latent_louvain', 'louvain_level', data=False)
         from .community import check_louvain_args, louvain
         check_louvain_args(self.n, int(n_neighbors), resolution, max_levels, max_sweeps)
         latent, idx, d2 = self.latent_knn(n_neighbors, chunk=chunk)
-        return latent, idx, d2, louvain(idx, resolution=resolution, max_levels=max_levels, max_sweeps=max_sweeps, ops=ops,
-                                        on_device=True)
+        return latent, idx, d2, louvain(idx, resolution=resolution, max_levels=max_levels, max_sweeps=max_sweeps,
+                                        ops=self.ops, on_device=True)
 
     def heads_gene_block(self, g0, gb, want, out):
         """The heads of genes [g0, g0 + gb) for ALL cells, written gene-major: out[k] [gb, >= n] device tensors for k in

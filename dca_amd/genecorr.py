@@ -8,7 +8,7 @@ float64 arrays.  ``Autoencoder.gene_correlation`` is the public entry; ``top_par
 """
 import numpy as np
 
-from .groups import VALUES, label_codes
+from .groups import VALUES, label_codes, obs_labels
 
 MAX_GENES = 8192             # include/dcahip.h, dcahip_gram
 
@@ -83,14 +83,7 @@ def gene_correlation(net, adata, genes=None, groupby=None, group=None, value='de
     else:
         if group is None:
             raise ValueError('dca_amd: gene_correlation: groupby needs group, the one label whose cells take part')
-        if isinstance(groupby, str):
-            if groupby not in adata.obs.columns:
-                raise ValueError('dca_amd: gene_correlation: adata.obs has no column %r' % groupby)
-            labels, key = adata.obs[groupby], groupby
-        else:
-            labels = groupby
-            if np.ndim(labels) != 1 or len(labels) != n:
-                raise ValueError('dca_amd: gene_correlation: %d labels for %d cells' % (np.size(labels), n))
+        labels, key = obs_labels(adata, groupby, 'gene_correlation')
         try:
             _, codes = label_codes(labels, [group])
         except ValueError as e:
@@ -98,8 +91,7 @@ def gene_correlation(net, adata, genes=None, groupby=None, group=None, value='de
         keep = codes == 0
     adata = adata.copy() if copy else adata
     net._bind_inputs(adata)
-    chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
-    res = eng.gene_gram(cols, keep=keep, no_sf=(value == 'normalized'), log1p=log1p, chunk=min(chunk, n))
+    res = eng.gene_gram(cols, keep=keep, no_sf=(value == 'normalized'), log1p=log1p, chunk=net._chunk(n))
     count = int(res['count'])
     dsum, shift = res['dsum'].cpu().numpy(), res['shift'].cpu().numpy()
     cross = res['cross'].cpu().numpy()

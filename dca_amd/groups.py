@@ -57,6 +57,18 @@ def label_codes(labels, groups=None, reference='rest'):
     return names, codes
 
 
+def obs_labels(adata, groupby, what):
+    """(labels, key): the labels `groupby` names -- a column of adata.obs (key: its name) or an array of one label per cell
+    (key: None)."""
+    if isinstance(groupby, str):
+        if groupby not in adata.obs.columns:
+            raise ValueError('dca_amd: %s: adata.obs has no column %r' % (what, groupby))
+        return adata.obs[groupby], groupby
+    if np.ndim(groupby) != 1 or len(groupby) != adata.n_obs:
+        raise ValueError('dca_amd: %s: %d labels for %d cells' % (what, np.size(groupby), adata.n_obs))
+    return groupby, None
+
+
 def moments_to_mean_var(s1, s2, n):
     """Mean and UNBIASED variance [K, G] from the sums of x and x^2 and the counts n [K]: (S2 - S1^2 / n) / (n - 1), clamped
     at 0; NaN for n < 2 (the mean: for n < 1)."""
@@ -185,14 +197,7 @@ def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False,
         raise ValueError("dca_amd: group_stats: log1p does not apply to ae_type='normal': its mean is linear and may be "
                          '<= -1')
     n = adata.n_obs
-    if isinstance(groupby, str):
-        if groupby not in adata.obs.columns:
-            raise ValueError('dca_amd: group_stats: adata.obs has no column %r' % groupby)
-        labels, key = adata.obs[groupby], groupby
-    else:
-        labels, key = groupby, None
-        if np.ndim(labels) != 1 or len(labels) != n:
-            raise ValueError('dca_amd: group_stats: %d labels for %d cells' % (np.size(labels), n))
+    labels, key = obs_labels(adata, groupby, 'group_stats')
     names, codes = label_codes(labels, groups, reference)
     if not names:
         raise ValueError('dca_amd: group_stats: no cell carries a label: there is no group')
@@ -208,13 +213,13 @@ def group_stats(net, adata, groupby, groups=None, value='denoised', log1p=False,
                          % (G_out, len(cols) if cols is not None else adata.n_vars))
     adata = adata.copy() if copy else adata
     net._bind_inputs(adata)
-    chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
-    res = eng.group_moments(codes, len(names), no_sf=(value == 'normalized'), log1p=log1p, chunk=min(chunk, n))
+    chunk = net._chunk(n)
+    res = eng.group_moments(codes, len(names), no_sf=(value == 'normalized'), log1p=log1p, chunk=chunk)
     counts = res['count'].cpu().numpy()
     ref = None if reference == 'rest' else names.index(reference)
     st = stats_from_moments(res['sum'].cpu().numpy(), res['sumsq'].cpu().numpy(), counts, log1p, ref)
     if method == 'wilcoxon':                            # mean, var and the fold change stay; the test is the rank-sum one
-        rk = eng.rank_sums(codes, len(names), reference=ref, no_sf=(value == 'normalized'), log1p=log1p, chunk=min(chunk, n))
+        rk = eng.rank_sums(codes, len(names), reference=ref, no_sf=(value == 'normalized'), log1p=log1p, chunk=chunk)
         wt = wilcoxon_from_ranks(rk['rank2'].cpu().numpy(), rk['tie'].cpu().numpy(), counts, ref, tie_correct)
         for k in ('scores', 'pvals', 'pvals_adj', 'auroc'):
             st[k] = wt[k]

@@ -9,6 +9,8 @@ module the one for a stored ``X_dca`` and for mapping new cells onto a fitted at
 """
 import numpy as np
 
+from ._device import as_points, default_ops, device_of
+
 MAX_K = 64          # the limits of the kernel (include/dcahip.h)
 MAX_D = 128
 MAX_SPLITS = 64
@@ -36,21 +38,11 @@ def knn(X, n_neighbors, queries=None, ops=None):
     (other) rows the tail is -1 at inf.  Host inputs give numpy arrays, a device tensor ``X`` gives device tensors.
     Runs on the GPU (there is no host fallback); 1 <= n_neighbors <= 64, d <= 128."""
     import torch
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
+    ops = default_ops(ops)
     on_device = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = X.device if on_device else torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' \
-        else torch.device('cpu')
-
-    def tensor(a):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
-        if a.dim() != 2:
-            raise ValueError('dca_amd: knn: points are the rows of a 2-d array (got %d dimensions)' % a.dim())
-        return a.to(device=dev, dtype=torch.float32).contiguous()
-    Xt = tensor(X)
-    Qt = Xt if queries is None else tensor(queries)
+    dev = device_of(X, ops)
+    Xt = as_points(X, dev, 'knn')
+    Qt = Xt if queries is None else as_points(queries, dev, 'knn')
     idx, d2 = ops.knn(Qt, Xt, int(n_neighbors), self_offset=0 if queries is None else -1)
     dist = torch.sqrt(d2)
     if on_device:

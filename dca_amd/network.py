@@ -206,14 +206,25 @@ class Autoencoder():
         else:
             eng.load_data(X, None, sf)
 
+    def _chunk(self, n):
+        """Rows per chunk of an inference pass over n cells.  Every pass takes predict's chunks: the same latent, the same
+        mean, bit for bit."""
+        eng = self.engine
+        return min(eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024, n)
+
+    def _one_process(self, what):
+        """The doors of the single-process passes refuse a data-parallel run before they bind any input."""
+        world = self.engine.comm.world
+        if world > 1:
+            raise ValueError('dca_amd: %s() does not apply to data-parallel runs (%d processes)' % (what, world))
+
     def _run_predict(self, adata, want, chunk=None):
         """One inference pass over all cells; returns host arrays for the requested outputs."""
         eng = self.engine
-        if chunk is None:       # rows per device -> host chunk: 2 page-locked staging buffers of this many rows per output
-            chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024
         n = adata.n_obs
         self._bind_inputs(adata)
-        chunk = min(chunk, n)
+        # rows per device -> host chunk: 2 page-locked staging buffers of this many rows per output
+        chunk = self._chunk(n) if chunk is None else min(chunk, n)
         eng.reserve(chunk)
         lay = eng.lay
         cols = {}
@@ -301,17 +312,25 @@ class Autoencoder():
                              % (k, n, n - 1))
         from .neighbors import check_knn_args
         check_knn_args(n, n, eng.lay.hidden[eng.center], k)
-        if eng.comm.world > 1:
-            raise ValueError('dca_amd: neighbors() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        self._one_process('neighbors')
         adata = adata.copy() if copy else adata
         self._bind_inputs(adata)
-        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
-        latent, idx, d2 = eng.latent_knn(k, chunk=min(chunk, n))
+        self._store_knn(adata, *eng.latent_knn(k, chunk=self._chunk(n)), k)
+        return adata if copy else None
+
+    @staticmethod
+    def _store_knn(adata, latent, idx, d2, k):
+        """What ``neighbors`` stores, from the device tensors of Engine.latent_knn."""
         adata.obsm['X_dca'] = latent.cpu().numpy()
         adata.obsm['dca_knn_indices'] = idx.cpu().numpy()
         adata.obsm['dca_knn_distances'] = np.sqrt(d2.cpu().numpy())
         adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
-        return adata if copy else None
+
+    @staticmethod
+    def _numbered(labels, k):
+        """Device labels 0 .. k-1 as the pandas categorical of the strings '0' .. 'k-1', categories in numeric order."""
+        import pandas as pd
+        return pd.Categorical.from_codes(labels.cpu().numpy().astype(np.int64), categories=[str(c) for c in range(k)])
 
     # ------------------------------------------------------------------ clusters
     def cluster(self, adata, n_clusters, n_init=10, max_iter=300, seed=0, key_added='dca_kmeans', copy=False):
@@ -328,7 +347,6 @@ class Autoencoder():
         ``group_stats(adata, key_added)`` then compares the clusters on the denoised expression.  1 <= n_clusters <=
         min(256, n); the latent space has at most 128 dimensions.  Returns ``adata`` if ``copy`` else None, like
         ``predict``."""
-        import pandas as pd
         from .cluster import check_kmeans_args
         eng = self.engine
         self._wanted('latent', False)                     # hidden_size=(): no centre layer
@@ -336,15 +354,12 @@ class Autoencoder():
         check_kmeans_args(n, eng.lay.hidden[eng.center], k)
         if k > n:
             raise ValueError('dca_amd: cluster: %d clusters of %d cells' % (k, n))
-        if eng.comm.world > 1:
-            raise ValueError('dca_amd: cluster() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        self._one_process('cluster')
         adata = adata.copy() if copy else adata
         self._bind_inputs(adata)
-        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
-        latent, res = eng.latent_kmeans(k, n_init=n_init, max_iter=max_iter, seed=seed, chunk=min(chunk, n))
+        latent, res = eng.latent_kmeans(k, n_init=n_init, max_iter=max_iter, seed=seed, chunk=self._chunk(n))
         adata.obsm['X_dca'] = latent.cpu().numpy()
-        cats = [str(c) for c in range(k)]
-        adata.obs[key_added] = pd.Categorical.from_codes(res.labels.cpu().numpy().astype(np.int64), categories=cats)
+        adata.obs[key_added] = self._numbered(res.labels, k)
         adata.uns[key_added] = {'centers': res.centers.cpu().numpy(), 'inertia': float(res.inertia), 'n_iter': int(res.n_iter),
                                 'converged': bool(res.converged), 'sizes': res.sizes.cpu().numpy().astype(np.int64),
                                 'params': {'n_clusters': k, 'n_init': int(n_init), 'max_iter': int(max_iter),
@@ -368,7 +383,6 @@ class Autoencoder():
 
         ``group_stats(adata, key_added)`` and ``silhouette(adata, key_added)`` follow with no glue.  Returns ``adata`` if
         ``copy`` else None, like ``predict``."""
-        import pandas as pd
         from .community import check_louvain_args
         from .neighbors import check_knn_args
         eng = self.engine
@@ -379,20 +393,14 @@ class Autoencoder():
                              % (k, n, n - 1))
         check_knn_args(n, n, eng.lay.hidden[eng.center], k)
         check_louvain_args(n, k, resolution, max_levels, max_sweeps)
-        if eng.comm.world > 1:
-            raise ValueError('dca_amd: louvain() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+        self._one_process('louvain')
         adata = adata.copy() if copy else adata
         self._bind_inputs(adata)
-        chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
         latent, idx, d2, res = eng.latent_louvain(k, resolution=resolution, max_levels=max_levels, max_sweeps=max_sweeps,
-                                                  chunk=min(chunk, n))
-        adata.obsm['X_dca'] = latent.cpu().numpy()
-        adata.obsm['dca_knn_indices'] = idx.cpu().numpy()
-        adata.obsm['dca_knn_distances'] = np.sqrt(d2.cpu().numpy())
-        adata.uns['dca_neighbors'] = {'n_neighbors': k, 'metric': 'euclidean', 'include_self': False}
+                                                  chunk=self._chunk(n))
+        self._store_knn(adata, latent, idx, d2, k)
         sizes = res.sizes.cpu().numpy().astype(np.int64)
-        cats = [str(c) for c in range(len(sizes))]
-        adata.obs[key_added] = pd.Categorical.from_codes(res.labels.cpu().numpy().astype(np.int64), categories=cats)
+        adata.obs[key_added] = self._numbered(res.labels, len(sizes))
         adata.uns[key_added] = {'modularity': float(res.modularity), 'sizes': sizes, 'level_sizes': list(res.level_sizes),
                                 'n_levels': int(res.n_levels), 'n_sweeps': list(res.n_sweeps),
                                 'params': {'n_neighbors': k, 'resolution': float(res.resolution),

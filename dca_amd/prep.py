@@ -17,6 +17,8 @@ import numpy as np
 import scipy.sparse as sp_sparse
 import torch
 
+from ._device import default_ops, device_of
+
 
 def host_chunk_tensor(a):
     """A host chunk as a CPU tensor for the upload (read only here).  A read-only array (a select-everything subset of the
@@ -665,11 +667,8 @@ def transform(ops, Y, n, G, fac, logtrans_input, normalize_input, comm=None, ret
 def resident_counts(X, ops=None, device=None):
     """(Y, gene_totals): the host count matrix on the device and the exact integer total of every gene.  Y is a CsrCounts
     when the counts go counts-resident (residency()), else the dense [n, r4(G)] tensor."""
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
-    dev = torch.device(device) if device is not None else (
-        torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
+    ops = default_ops(ops)
+    dev = torch.device(device) if device is not None else device_of(None, ops)
     n, G = X.shape
     if residency(X, dev, ops) == 'counts':
         csr = upload_csr(X, dev, ops)
@@ -682,11 +681,8 @@ def normalize_device(adata, filter_min_counts=True, size_factors=True, normalize
                      logtrans_input=True, ops=None, device=None, to_host=True, Y=None):
     """``io.normalize`` with the arithmetic on the device.  Returns (adata, DeviceData)."""
     from . import io as _io
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
-    dev = torch.device(device) if device is not None else (
-        torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu'))
+    ops = default_ops(ops)
+    dev = torch.device(device) if device is not None else device_of(None, ops)
     n, G = adata.X.shape
     if isinstance(Y, CsrCounts) and (Y.n, Y.G) == (n, G):
         return _normalize_counts(adata, filter_min_counts, size_factors, normalize_input, logtrans_input, ops, dev,

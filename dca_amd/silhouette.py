@@ -13,6 +13,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._device import as_points, default_ops, device_of
+
 MAX_CLUSTERS = 256      # the limits of the kernel (include/dcahip.h)
 MAX_D = 128
 MAX_SPLITS = 64
@@ -42,22 +44,6 @@ def check_label_count(k, what='silhouette'):
         raise ValueError('dca_amd: %s: %d distinct labels (at most %d)' % (what, k, MAX_CLUSTERS))
 
 
-def _device(X, ops):
-    import torch
-    if isinstance(X, torch.Tensor) and X.is_cuda:
-        return X.device
-    return torch.device('cuda', torch.cuda.current_device()) if ops.device_type == 'cuda' else torch.device('cpu')
-
-
-def _points(X, dev, what):
-    import torch
-    if not isinstance(X, torch.Tensor):
-        X = torch.from_numpy(np.ascontiguousarray(np.asarray(X), dtype=np.float32))
-    if X.dim() != 2:
-        raise ValueError('dca_amd: %s: points are the rows of a 2-d array (got %d dimensions)' % (what, X.dim()))
-    return X.to(device=dev, dtype=torch.float32).contiguous()
-
-
 def silhouette(X, labels, ops=None):
     """The silhouette of every row of ``X`` [n, d] (host array or device tensor, taken as float32) under ``labels``.
 
@@ -73,12 +59,10 @@ def silhouette(X, labels, ops=None):
     tensor gives device tensors.  Runs on the GPU (there is no host fallback); 2 .. 256 clusters, at least two of them with
     points, d <= 128; non-finite input raises ValueError."""
     import torch
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
+    ops = default_ops(ops)
     on_device = isinstance(X, torch.Tensor) and X.is_cuda
-    dev = _device(X, ops)
-    Xt = _points(X, dev, 'silhouette')
+    dev = device_of(X, ops)
+    Xt = as_points(X, dev, 'silhouette')
     n, d = Xt.shape
     if isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.device == dev and labels.dim() == 1:
         codes = labels.contiguous()
@@ -114,10 +98,8 @@ def choose_k(X, ks, n_init=10, max_iter=300, seed=0, ops=None):
     highest mean silhouette, ties to the lowest k."""
     import pandas as pd
     from .cluster import kmeans
-    if ops is None:
-        from .ops import HipOps
-        ops = HipOps()
-    Xt = _points(X, _device(X, ops), 'choose_k')
+    ops = default_ops(ops)
+    Xt = as_points(X, device_of(X, ops), 'choose_k')
     n, d = Xt.shape
     ks = [int(k) for k in ks]
     if not ks:
@@ -139,28 +121,19 @@ def choose_k(X, ks, n_init=10, max_iter=300, seed=0, ops=None):
 
 def model_silhouette(net, adata, groupby='dca_kmeans', key_added='dca_silhouette', copy=False):
     """Autoencoder.silhouette (documented there)."""
-    from .groups import label_codes
+    from .groups import label_codes, obs_labels
     eng = net.engine
     net._wanted('latent', False)                          # hidden_size=(): no centre layer
     n = adata.n_obs
-    if isinstance(groupby, str):
-        if groupby not in adata.obs.columns:
-            raise ValueError('dca_amd: silhouette: adata.obs has no column %r' % groupby)
-        labels, key = adata.obs[groupby], groupby
-    else:
-        labels, key = groupby, None
-        if np.ndim(labels) != 1 or len(labels) != n:
-            raise ValueError('dca_amd: silhouette: %d labels for %d cells' % (np.size(labels), n))
+    labels, key = obs_labels(adata, groupby, 'silhouette')
     names, codes = label_codes(labels)
     k = len(names)
     check_label_count(k)
     check_silhouette_args(n, eng.lay.hidden[eng.center], k)
-    if eng.comm.world > 1:
-        raise ValueError('dca_amd: silhouette() does not apply to data-parallel runs (%d processes)' % eng.comm.world)
+    net._one_process('silhouette')
     adata = adata.copy() if copy else adata
     net._bind_inputs(adata)
-    chunk = eng.cfg.predict_chunk if hasattr(eng, 'cfg') else 1024      # predict's chunks: the same latent, bit for bit
-    latent, r = eng.latent_silhouette(codes, k, chunk=min(chunk, n))
+    latent, r = eng.latent_silhouette(codes, k, chunk=net._chunk(n))
     nearest = r['nearest'].cpu().numpy()
     near = np.full(n, None, dtype=object)
     near[nearest >= 0] = np.array(names, dtype=object)[nearest[nearest >= 0]]

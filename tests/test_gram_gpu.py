@@ -296,7 +296,7 @@ def test_gene_correlation_against_corrcoef_of_predict(trained):
     d = ad.uns['dca_gene_corr']
     assert list(d['genes']) == list(ad.var_names) and d['n_cells'] == n and d['corr'].dtype == np.float64
     v = x.astype(np.float64)
-    chunk = min(net.engine.cfg.predict_chunk if hasattr(net.engine, 'cfg') else 1024, n)
+    chunk = net._chunk(n)
     shift = v[:chunk].mean(axis=0)                                   # what Engine.gene_gram fixes from its first chunk
     _check_corr(d, v, shift, 'all cells')
     np.testing.assert_allclose(d['mean'], v.mean(axis=0), rtol=1e-12)
