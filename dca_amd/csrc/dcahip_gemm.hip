@@ -1492,8 +1492,8 @@ static Plan make_plan3(int M, int N, int K, int split_k, bool wide) {
     return p;
 }
 
-static bool p3_wide(int M, int N, int K, const int* perm, const long long* cursor) {
-    return M >= 256 && N >= 256 && K % 16 == 0 && (long)M * N >= 512L * 512 && !perm && !cursor;
+static bool p3_wide(int M, int N, int K, bool gather) {
+    return M >= 256 && N >= 256 && K % 16 == 0 && (long)M * N >= 512L * 512 && !gather;
 }
 
 // tail splitting of the 256 x 256 kernel (split == 1 only): T tiles on 256 CUs run as ceil(T / 256) rounds; a last round of
@@ -1520,33 +1520,83 @@ static TailPlan tail_plan(const Plan& p, int M, int K, int colsum_row) {
     return t;
 }
 
-extern "C" long dcahip_gemm_p3_workspace_bytes(int M, int N, int K, int colsum_row, int split_k) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    // (the larger of the two plans a call of this shape can take: with and without a row gather)
-    const Plan pw = make_plan3(M, N, K, split_k, p3_wide(M, N, K, nullptr, nullptr));
-    const Plan pn = make_plan3(M, N, K, split_k, false);
-    const Plan p = pw.split > pn.split ? pw : pn;
-    const long tail = tail_plan(pw, M, K, colsum_row).ws_bytes;
-    if (tail > 0 && p.split <= 1) return tail;
-    if (p.split <= 1) return 0;
-    return (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float);
-}
-
-// ---- what dcahip_gemm_p3 and dcahip_gemm_h2 share on the host
-static bool plane_operands_ok(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a, const void* B, long ldb,
-                              long plane_b, const float* C, long ldc, int colsum_row) {
-    if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || ldc < N) return false;
-    if (colsum_row && tb) return false;
-    if (!al16(A) || !al16(B) || lda % 8 != 0 || ldb % 8 != 0 || plane_a % 8 != 0 || plane_b % 8 != 0) return false;
-    // k-contiguous operands are read in units of 8 k: K must be a multiple of 8 (pad both operands with zeros)
-    if ((!ta || tb) && K % 8 != 0) return false;
-    // rows must cover the 16-byte units the tile reads: ld >= the extent rounded up to 8
-    return !((ta ? lda < (M + 7) / 8 * 8 : lda < K) || (tb ? ldb < K : ldb < (N + 7) / 8 * 8));
-}
-
 // workspace of a plan: the split-K slabs, or the partial tiles of the tail
 static long plane_workspace(const Plan& p, const TailPlan& tp, int M, int N, int colsum_row) {
     return p.split > 1 ? (long)p.split * (M + (colsum_row ? 1 : 0)) * N * (long)sizeof(float) : tp.ws_bytes;
+}
+
+// Everything dcahip_gemm_p3 (pieces == 3) and dcahip_gemm_h2 (pieces == 2) decide on the host from the shape: the kernel, its
+// tiles, the K split, the tail and the workspace.  The one definition behind both launches and the query
+// dcahip_gemm_planes_plan.
+struct PlanesPlan {
+    Plan p;
+    TailPlan tp;
+    int kernel;         // 0: gemm_p3_kernel, 1: the 256 x 256 eight-wave kernel (gemm_p3w_kernel / gemm_h2w_kernel), 2: gemm_h2m_kernel
+    bool cs;            // the column-sum instantiation of the eight-wave kernel
+    long ws_bytes;
+};
+
+// the shape reasons for DCAHIP_EINVAL of the two products
+static bool planes_shape_ok(int pieces, int ta, int tb, int M, int N, int K, bool gather, int colsum_row) {
+    if (pieces != 2 && pieces != 3) return false;
+    if (M <= 0 || N <= 0 || K <= 0) return false;
+    if (colsum_row && tb) return false;
+    // k-contiguous operands are read in units of 8 k: K must be a multiple of 8 (pad both operands with zeros)
+    if ((!ta || tb) && K % 8 != 0) return false;
+    // two pieces: the shapes of the 256 x 256 kernel only, no row gather
+    if (pieces == 2 && (gather || !p3_wide(M, N, K, false))) return false;
+    return true;
+}
+
+static PlanesPlan planes_plan(int pieces, int ta, int tb, int M, int N, int K, bool gather, int colsum_row, int split_k) {
+    PlanesPlan pp;
+    const bool wide = p3_wide(M, N, K, gather);
+    pp.p = make_plan3(M, N, K, split_k, wide);
+    pp.tp = tail_plan(pp.p, M, K, colsum_row);
+    pp.ws_bytes = plane_workspace(pp.p, pp.tp, M, N, colsum_row);
+    pp.kernel = wide ? 1 : 0;
+    pp.cs = wide && !tb && colsum_row;
+    // two pieces, forward products (A k-contiguous, B n-contiguous, no column sums): 128 x 256 tiles by four waves, two
+    // workgroups per CU (gemm_h2m_kernel), no tail (the split and the workspace demand stay those of the 256 x 256 plan).
+    // Measured at configs[4] (tools/ab_heads_lib.py, one box): heads forward 0.87 - 0.90 -> 0.73 - 0.74 ms, first layer forward
+    // (split-K) 0.368 -> 0.362; the input gradient (B k-contiguous, split-K) 0.50 -> 0.64: stays on the 8-wave kernel
+    if (pieces == 2 && wide && !ta && !tb && !colsum_row) {
+        pp.kernel = 2;
+        pp.p.BM = 128;
+        pp.p.mtiles = (M + 127) / 128;
+        pp.tp = TailPlan{0, 1, 0, 0};
+    }
+    return pp;
+}
+
+extern "C" long dcahip_gemm_p3_workspace_bytes(int M, int N, int K, int colsum_row, int split_k) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    // (the larger of the two plans a call of this shape can take: with and without a row gather)
+    const long w = planes_plan(3, 1, 0, M, N, K, false, colsum_row, split_k).ws_bytes;
+    const long g = planes_plan(3, 1, 0, M, N, K, true, colsum_row, split_k).ws_bytes;
+    return w > g ? w : g;
+}
+
+extern "C" int dcahip_gemm_planes_plan(int pieces, int ta, int tb, int M, int N, int K, int gather, int colsum_row, int split_k,
+                                       int out[12]) {
+    if (!planes_shape_ok(pieces, ta, tb, M, N, K, gather != 0, colsum_row) || !out) return DCAHIP_EINVAL;
+    const PlanesPlan pp = planes_plan(pieces, ta, tb, M, N, K, gather != 0, colsum_row, split_k);
+    out[0] = pp.kernel; out[1] = pp.p.BM; out[2] = pp.p.BN; out[3] = pp.p.mtiles; out[4] = pp.p.ntiles;
+    out[5] = pp.p.split; out[6] = pp.p.kslab;
+    out[7] = pp.tp.first; out[8] = pp.tp.split; out[9] = pp.tp.kslab;
+    out[10] = pp.cs ? 1 : 0;
+    out[11] = pp.ws_bytes > 0x7fffffffL ? 0x7fffffff : (int)pp.ws_bytes;
+    return 0;
+}
+
+// ---- what dcahip_gemm_p3 and dcahip_gemm_h2 share on the host
+static bool plane_operands_ok(int pieces, int ta, int tb, int M, int N, int K, bool gather, const void* A, long lda, long plane_a,
+                              const void* B, long ldb, long plane_b, const float* C, long ldc, int colsum_row) {
+    if (!planes_shape_ok(pieces, ta, tb, M, N, K, gather, colsum_row)) return false;
+    if (!A || !B || !C || ldc < N) return false;
+    if (!al16(A) || !al16(B) || lda % 8 != 0 || ldb % 8 != 0 || plane_a % 8 != 0 || plane_b % 8 != 0) return false;
+    // rows must cover the 16-byte units the tile reads: ld >= the extent rounded up to 8
+    return !((ta ? lda < (M + 7) / 8 * 8 : lda < K) || (tb ? ldb < K : ldb < (N + 7) / 8 * 8));
 }
 
 // after the product's launch: its status, then the ordered split-K reduce or the sum of the tail's K slices
@@ -1612,16 +1662,18 @@ extern "C" int dcahip_gemm_p3(int ta, int tb, int M, int N, int K, const void* A
                               const void* B, long ldb, long plane_b, float* C, long ldc, const float* bias,
                               const int* perm, const long long* cursor, int colsum_row, int split_k,
                               void* workspace, long workspace_bytes, void* stream) {
-    if (!plane_operands_ok(ta, tb, M, N, K, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
-    const Plan p = make_plan3(M, N, K, split_k, p3_wide(M, N, K, perm, cursor));
-    const TailPlan tp = tail_plan(p, M, K, colsum_row);
-    const long need = plane_workspace(p, tp, M, N, colsum_row);
+    const bool gather = perm || cursor;
+    if (!plane_operands_ok(3, ta, tb, M, N, K, gather, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
+    const PlanesPlan pp = planes_plan(3, ta, tb, M, N, K, gather, colsum_row, split_k);
+    const Plan& p = pp.p;
+    const TailPlan& tp = pp.tp;
+    const long need = pp.ws_bytes;
     if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
     Gemm3Args a{static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(B), lda, ldb, plane_a, plane_b,
                 C, bias, perm, cursor, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
                 p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace)};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.cfg == 4) return gemm_wide<3>(a, ta, tb, p, tp, s);
+    if (pp.kernel == 1) return gemm_wide<3>(a, ta, tb, p, tp, s);
     const int grid = p.mtiles * p.ntiles * p.split;
     if (!ta && !tb) hipLaunchKernelGGL((gemm_p3_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
     else if (!ta && tb) hipLaunchKernelGGL((gemm_p3_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
@@ -1659,37 +1711,34 @@ extern "C" int dcahip_split_planes_h2(const float* src, long ld, const int* perm
 }
 
 // the shapes the 256 x 256 kernel takes (the same as the wide form of dcahip_gemm_p3)
-extern "C" int dcahip_gemm_h2_supported(int M, int N, int K) { return p3_wide(M, N, K, nullptr, nullptr) ? 1 : 0; }
+extern "C" int dcahip_gemm_h2_supported(int M, int N, int K) { return p3_wide(M, N, K, false) ? 1 : 0; }
 
 extern "C" long dcahip_gemm_h2_workspace_bytes(int M, int N, int K, int colsum_row, int split_k) {
-    if (!p3_wide(M, N, K, nullptr, nullptr)) return 0;
-    const Plan p = make_plan3(M, N, K, split_k, true);
-    return plane_workspace(p, tail_plan(p, M, K, colsum_row), M, N, colsum_row);
+    if (!p3_wide(M, N, K, false)) return 0;
+    // (the layout does not change the demand: the four-wave forward form asks for what the 256 x 256 plan of its shape asks)
+    return planes_plan(2, 1, 0, M, N, K, false, colsum_row, split_k).ws_bytes;
 }
 
 extern "C" int dcahip_gemm_h2(int ta, int tb, int M, int N, int K, const void* A, long lda, long plane_a, const int* exp_a, int exp_a_add,
                               const void* B, long ldb, long plane_b, const int* exp_b, int exp_b_add, float alpha,
                               float* C, long ldc, const float* bias, int colsum_row, int split_k,
                               void* workspace, long workspace_bytes, void* stream) {
-    if (!plane_operands_ok(ta, tb, M, N, K, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
-    if (!p3_wide(M, N, K, nullptr, nullptr)) return DCAHIP_EINVAL;
-    const Plan p = make_plan3(M, N, K, split_k, true);
-    const TailPlan tp = tail_plan(p, M, K, colsum_row);
-    const long need = plane_workspace(p, tp, M, N, colsum_row);
+    if (!plane_operands_ok(2, ta, tb, M, N, K, false, A, lda, plane_a, B, ldb, plane_b, C, ldc, colsum_row)) return DCAHIP_EINVAL;
+    // the kernels take the scales out with h2_pow2i(-(ea + eb)), a power of two for |ea + eb| <= 126 only: device words in
+    // [-60, 60] (dcahip_absmax_exp clamps there) plus these stay inside
+    if (labs((long)exp_a_add) + labs((long)exp_b_add) > 6) return DCAHIP_EINVAL;
+    const PlanesPlan pp = planes_plan(2, ta, tb, M, N, K, false, colsum_row, split_k);
+    const Plan& p = pp.p;
+    const TailPlan& tp = pp.tp;
+    const long need = pp.ws_bytes;
     if (need > 0 && (!workspace || workspace_bytes < need)) return DCAHIP_EINVAL;
     GemmH2Args a{static_cast<const unsigned short*>(A), static_cast<const unsigned short*>(B), lda, ldb, plane_a, plane_b,
                  C, bias, static_cast<float*>(workspace), ldc, M, N, K, p.split, p.kslab, colsum_row,
                  p.mtiles, p.ntiles, tp.first, tp.split, tp.kslab, static_cast<float*>(workspace), exp_a, exp_b, exp_a_add, exp_b_add, alpha};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (ta || tb || colsum_row) return gemm_wide<2>(a, ta, tb, p, tp, s);
-    // forward products (A k-contiguous, B n-contiguous): 128 x 256 tiles by four waves, two workgroups per CU
-    // (gemm_h2m_kernel).  Measured at configs[4] (tools/ab_heads_lib.py, one box): heads forward 0.87 - 0.90 -> 0.73 - 0.74 ms,
-    // first layer forward (split-K) 0.368 -> 0.362; the input gradient (B k-contiguous, split-K) 0.50 -> 0.64: stays on
-    // the 8-wave kernel
-    a.mtiles = (M + 127) / 128;
-    a.tail_first = 0; a.tail_split = 1;
+    if (pp.kernel == 1) return gemm_wide<2>(a, ta, tb, p, tp, s);
+    // gemm_h2m_kernel (planes_plan: 128 x 256 tiles, no tail)
     constexpr int bytes = 3 * (WideImage<2, true, 4>::BYTES + WideImage<2, false, 8>::BYTES);
     launch_ring<GemmH2Args, gemm_h2m_kernel<false>>(a.mtiles * a.ntiles * a.split, 256, bytes, s, a);
-    return plane_finish(p, TailPlan{0, 1, 0, 0}, a.ws, M, N, 0, bias, C, ldc, s);
+    return plane_finish(p, tp, a.ws, M, N, 0, bias, C, ldc, s);
 }
-

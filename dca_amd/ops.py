@@ -269,6 +269,15 @@ class HipOps:
                                         B.stride(0), p(C), ldc, p(bias), p(perm), p(cursor), int(colsum_row), split_k,
                                         p(ws), wsb, hip.stream()), 'gemm_p3')
 
+    def gemm_planes_plan(self, pieces, ta, tb, M, N, K, gather=False, colsum_row=False, split_k=0):
+        """What gemm_p3 (pieces 3) / gemm_h2 (pieces 2) would launch for this shape (nothing is launched): the tuple (kernel 0
+        gemm_p3_kernel / 1 the 256 x 256 eight-wave kernel / 2 gemm_h2m_kernel, tile rows, tile columns, m tiles, n tiles,
+        split, k slab, first tail tile, tail slices, k per tail slice, column-sum instantiation, workspace bytes)."""
+        out = (ctypes.c_int * 12)()
+        hip.check(self.L.dcahip_gemm_planes_plan(int(pieces), int(ta), int(tb), M, N, K, int(bool(gather)), int(colsum_row),
+                                                 split_k, ctypes.addressof(out)), 'gemm_planes_plan')
+        return tuple(out)
+
     # ---- fp16 x 2 planes (include/dcahip.h: dcahip_gemm_h2).  exp: an int32 device tensor [2] = (block exponent, scratch)
     def absmax_exp(self, src, ld, R, C, exp):
         """exp[0] <- the exponent that brings max |src [R, C]| into [2^13, 2^14) (stays on the device: capturable)."""

@@ -402,17 +402,45 @@ int dcahip_gemm_p3(int ta, int tb, int M, int N, int K, const void* A, long lda,
                    const int* perm, const long long* cursor, int colsum_row, int split_k,
                    void* workspace, long workspace_bytes, void* stream);
 long dcahip_gemm_p3_workspace_bytes(int M, int N, int K, int colsum_row, int split_k);
+/* What dcahip_gemm_p3 (pieces == 3) or dcahip_gemm_h2 (pieces == 2, below) would launch for these arguments, exposed for
+ * testing (as dcahip_sgemm_plan is): nothing is launched.  gather: non-zero when perm or cursor would be passed.  Both
+ * products take their kernel, tiles, K split, tail and workspace from the function that fills `out`, so the answer cannot
+ * differ from the launch.
+ *   out[0]         : the kernel, 0 = gemm_p3_kernel (128 x 128 tiles, four waves), 1 = the 256 x 256 eight-wave kernel
+ *                    (gemm_p3w_kernel, gemm_h2w_kernel), 2 = gemm_h2m_kernel (128 x 256 tiles, four waves; two pieces, NN
+ *                    without column sums)
+ *   out[1], out[2] : tile rows, tile columns
+ *   out[3], out[4] : tiles along M, along N
+ *   out[5], out[6] : K splits (1 = none; empty trailing splits are dropped), K elements per split
+ *   out[7..9]      : the tail (K splits == 1 only): first tail tile, K slices per tail tile (1 = no tail), K elements per slice
+ *   out[10]        : 1 when the column-sum instantiation of the eight-wave kernel is the one launched
+ *   out[11]        : the workspace bytes the call will demand (INT_MAX when they are more than that)
+ * The ending follows: out[5] > 1 the ordered split-K reduce, else out[8] > 1 the sum of the tail's K slices, else none.
+ * DCAHIP_EINVAL wherever the product returns it for reasons of shape (non-positive sizes, colsum_row && tb, K % 8 != 0 with
+ * an operand contiguous along k; two pieces: a shape dcahip_gemm_h2_supported refuses, any gather), for pieces other than
+ * 2 and 3 and for a NULL out. */
+int dcahip_gemm_planes_plan(int pieces, int ta, int tb, int M, int N, int K, int gather, int colsum_row, int split_k, int out[12]);
 /*
  * The plane products on TWO fp16 pieces per operand and THREE products per fp32 product (round 6: the arithmetic of K-HEADS,
  * dcahip_x3_product_32x32; half the matrix instructions of dcahip_gemm_p3).  An operand matrix is scaled by the power of two
  * that brings its largest magnitude into [2^13, 2^14) before it is split: the exponent lives in a DEVICE word, so nothing
  * leaves the stream (capturable).
- *   dcahip_absmax_exp       *exp_out = that exponent for src [R, C] (scratch_word: 4 bytes of device memory the call may use)
+ *   dcahip_absmax_exp       *exp_out = that exponent for src [R, C] (scratch_word: 4 bytes of device memory the call may use),
+ *                           clamped to [-60, 60]; NaN entries are ignored; 0 for an all-zero block and for one that holds
+ *                           +-Inf.  Supported range: a largest magnitude in [2^-46, 2^74).  Below it the clamp at +60
+ *                           leaves the scaled block under 2^13 and the pieces keep their ABSOLUTE floor only (2^-25 of the
+ *                           scaled value, i.e. 2^-85 of the data; the split stays correct down to the fp32 denormals);
+ *                           from 2^74 on the clamp at -60 leaves a scaled maximum of 2^14 or more, which from 2^76 on
+ *                           overflows the fp16 pieces to Inf: the product is then non-finite, never a wrong finite number.
  *   dcahip_split_planes_h2  fp32 [R, C] (rows gathered through perm / cursor) x 2^*exp -> planes [2][R][ldp] fp16 (exp NULL: 0)
  *   dcahip_gemm_h2          C = alpha 2^-(ea + eb) op(A) op(B) (+ bias), ea = (exp_a ? *exp_a : 0) + exp_a_add, eb likewise;
  *                           colsum_row: row M of C = alpha 2^-eb x the column sums of B.  Shapes: those of the 256 x 256 kernel
  *                           (dcahip_gemm_h2_supported; M, N >= 256, M N >= 2^18, K % 16 == 0, no row gather); layouts, ta / tb,
- *                           split_k and the workspace as dcahip_gemm_p3.
+ *                           split_k and the workspace as dcahip_gemm_p3.  The kernels take the scale out as ONE power of
+ *                           two, 2^-(ea + eb), which exists for |ea + eb| <= 126: the exponent words must come from
+ *                           dcahip_absmax_exp or lie in [-60, 60], and |exp_a_add| + |exp_b_add| <= 6 (DCAHIP_EINVAL
+ *                           otherwise, before any launch).  The factor applied is alpha 2^-(ea + eb), formed in fp32: the
+ *                           contract holds where that number is a normal one (alpha >= 1 at ea + eb = 126).
  * Contract (tests/test_gemm_h2_gpu.py): |C - alpha op(A) op(B)| <= 1e-6 alpha sum|a b| per element (a priori 3 x 2^-22 = 7.2e-7
  * plus the fp32 accumulation over K; the worst of 3 M elements at K = 512 measured 5.7e-7), deterministic.
  * A producer that writes planes directly (dcahip_zinb_nll_planes_h2: the gradient planes as g 2^d_exp) passes its static
