@@ -16,10 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libdcahip.so')
-SOURCES = ['dcahip_zinb.hip', 'dcahip_gemm.hip', 'dcahip_layers.hip', 'dcahip_heads.hip', 'dcahip_prep.hip', 'dcahip_opt.hip',
+SOURCES = ['dcahip_zinb.hip', 'dcahip_score.hip', 'dcahip_gemm.hip', 'dcahip_layers.hip', 'dcahip_heads.hip', 'dcahip_prep.hip', 'dcahip_opt.hip',
            'dcahip_dropout.hip', 'dcahip_sparse.hip', 'dcahip_peer.hip', 'dcahip_knn.hip', 'dcahip_kmeans.hip', 'dcahip_gram.hip',
            'dcahip_silhouette.hip', 'dcahip_ranksum.hip', 'dcahip_louvain.hip']
-HEADERS = ['zinb_math.hpp', 'h2_math.hpp', 'philox.hpp', 'knn_dist.hpp']
+HEADERS = ['zinb_math.hpp', 'nll_shared.hpp', 'h2_math.hpp', 'philox.hpp', 'knn_dist.hpp']
 ARCH = 'gfx950'
 HOST_LIB = os.path.join(CSRC, 'libdcahost.so')
 HOST_SOURCES = ['dcahost_tsv.cpp', 'dcahost_read.cpp']

@@ -1,11 +1,12 @@
-// K-ZINB: fused NB / ZINB negative log-likelihood + gradient over the cells x genes tile,
-// inference heads, deterministic loss reduction.  gfx950 (MI355X), wave64.
+// K-ZINB: the training and validation likelihood of the separate-head path -- fused NB / ZINB (Poisson, squared error)
+// negative log-likelihood + gradient over the cells x genes tile (dcahip_zinb_nll, dcahip_zinb_nll_planes[_h2]) -- and the
+// deterministic end of a step's loss (dcahip_loss_finalize, dcahip_step_end).  gfx950 (MI355X), wave64.
 //
-// Memory-bound by design: per element the training kernel reads 3 pre-activations + y
-// (16 B) and writes 3 gradients (12 B) = 28 B; everything else (exp, softplus, sigmoid,
-// log1p, pow, lgamma/digamma differences) stays in registers.  Each lane owns one 16-byte
-// quad of consecutive genes so every global access is a coalesced dwordx4; the minibatch
-// gather (row -> perm[cursor + row]) is a wave-uniform scalar load.
+// Memory-bound by design: everything between the loads and the stores (exp, softplus, sigmoid, log1p, pow, lgamma / digamma
+// differences) stays in registers.  Each lane owns one 16-byte quad of consecutive genes so every global access is a
+// coalesced dwordx4; the minibatch gather (row -> perm[cursor + row]) is a wave-uniform scalar load.  Per element the
+// kernels read 3 pre-activations + y (16 B); with gradients they write 12 B (fp32 planes), 18 B (three bf16 pieces) or 12 B
+// (two fp16 pieces).  The passes over a fitted model (inference heads, K-SCORE, K-GROUPS) are in dcahip_score.hip.
 //
 // Reference arithmetic restated here: dca/network.py:38-39 (MeanAct, DispAct),
 // dca/layers.py:21,85, dca/loss.py:72-114 (NB.loss), dca/loss.py:122-156 (ZINB.loss).
@@ -15,6 +16,7 @@
 #include "dcahip.h"
 #include "zinb_math.hpp"
 #include "h2_math.hpp"
+#include "nll_shared.hpp"
 
 namespace {
 
@@ -81,38 +83,73 @@ __device__ __forceinline__ double block_reduce_sum(double v) {
     return r;
 }
 
-template <int V> struct Vec;
-template <> struct Vec<4> { using T = float4; };
-template <> struct Vec<1> { using T = float; };
-
+// ---- what the three kernels share.  grid.x walks the gene segments (256 lanes x V genes), grid.y strides over the batch
+// rows: no integer division on the path, the per-row gather index and size factor are scalar loads.
 template <int V>
-__device__ __forceinline__ void ldv(const float* p, float (&o)[V]) {
-    if (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); o[0] = t.x; o[1 % V] = t.y; o[2 % V] = t.z; o[3 % V] = t.w; }
-    else o[0] = *p;
-}
-template <int V>
-__device__ __forceinline__ void stv(float* p, const float (&o)[V]) {
-    if (V == 4) *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1 % V], o[2 % V], o[3 % V]);
-    else *p = o[0];
+struct Segments {
+    const int nvec, nseg;             // a row's V-gene units (quads at V = 4: one per lane) and segments of 256 of them
+    __device__ __forceinline__ explicit Segments(int G) : nvec((G + V - 1) / V), nseg((nvec + 255) >> 8) {}
+    // first gene of this lane's unit of segment seg; live: the row has that unit (a lane without one is given gene 0)
+    __device__ __forceinline__ int gene(int seg, bool& live) const {
+        const int q = seg * 256 + threadIdx.x;
+        live = q < nvec;
+        return (live ? q : 0) * V;
+    }
+};
+
+// storage row of batch row `row`: through the minibatch permutation where there is one.  (Takes the pointer, not the kernel's
+// NllArgs: with a reference to the argument struct the compiler packs and contracts the NB arithmetic of the calling kernel
+// differently -- other bits in loss and gradients.)
+__device__ __forceinline__ long storage_row(const int* perm, long long cur, int row) {
+    return perm ? (long)perm[cur + row] : (long)(cur + row);
 }
 
-// LOSS: 0 = NB / ZINB, 1 = Poisson, 2 = squared error (mean head only)
+// One element by the branch its count selects, as K-HEADS evaluates it: nll and d nll / d (a_mean, a_disp, a_pi), unscaled
+// (gp = 0 without a dropout head).  K-HEADS keeps its own copies of these three: it sits at its register limit, and moving
+// its element code into shared helpers changes its register allocation.
+struct Elem { float nll, gm, gd, gp; };
+
+template <bool HAS_PI>
+__device__ __forceinline__ bool count_is_nonzero(float y) { return HAS_PI ? !(y < kZeroThresh) : (y != 0.f); }
+
+template <bool HAS_PI, bool CONST_DISP>
+__device__ __forceinline__ Elem zero_elem(float am, float ad, float ap, float sf, float ridge) {
+    Elem e;
+    e.gp = 0.f;
+    if (HAS_PI) e.nll = zinb_zero_elem<CONST_DISP>(am, ad, ap, sf, ridge, e.gm, e.gd, e.gp);
+    else e.nll = nb_zero_elem<CONST_DISP>(am, ad, sf, e.gm, e.gd);
+    return e;
+}
+
+template <bool HAS_PI, bool CONST_DISP>
+__device__ __forceinline__ Elem nonzero_elem(float am, float ad, float ap, float sf, float y, float ridge) {
+    Elem e;
+    e.gp = 0.f;
+    if (HAS_PI) {
+        e.nll = zinb_nz_elem<CONST_DISP>(am, ad, ap, sf, y, ridge, e.gm, e.gd, e.gp);
+    } else {
+        float dmu = 0.f, dth = 0.f, dpi = 0.f;
+        const Heads hd = head_acts<false, CONST_DISP>(am, ad, 0.f, sf);
+        e.nll = nll_elem<false, true, true>(hd, y, ridge, dmu, dth, dpi);
+        e.gm = dmu * hd.gm; e.gd = dth * hd.gd;
+    }
+    return e;
+}
+
+// ---- every loss, any alignment.  LOSS: 0 = NB / ZINB, 1 = Poisson, 2 = squared error (mean head only)
 template <bool HAS_PI, bool CONST_DISP, bool GRAD, int V, int LOSS = 0>
 __global__ __launch_bounds__(256) void zinb_nll_kernel(NllArgs a) {
-    // grid.x walks the gene segments (256 lanes x V genes), grid.y strides over the batch rows:
-    // no integer division on the path, the per-row gather index and size factor are scalar loads
-    const int nvec = (a.G + V - 1) / V;              // lanes' work units per row
-    const int nseg = (nvec + 255) >> 8;
+    const Segments<V> segs(a.G);
     const long long cur = a.cursor ? *a.cursor : 0;
     double dacc = 0.0;
-    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const int q = seg * 256 + threadIdx.x;
-        if (q >= nvec) continue;
-        const int g = q * V;
+    for (int seg = blockIdx.x; seg < segs.nseg; seg += gridDim.x) {
+        bool qv;
+        const int g = segs.gene(seg, qv);
+        if (!qv) continue;
         float vd[V];
         if (CONST_DISP) ldv<V>(a.theta_w + g, vd);
         for (int row = blockIdx.y; row < a.B; row += gridDim.y) {
-            const long srow = a.perm ? (long)a.perm[cur + row] : (long)(cur + row);
+            const long srow = storage_row(a.perm, cur, row);
             const float sf = a.sf[srow];
             const long ao = (long)row * a.lda + g;
             float vm[V], vp[V], vy[V];
@@ -156,26 +193,27 @@ __global__ __launch_bounds__(256) void zinb_nll_kernel(NllArgs a) {
     if (threadIdx.x == 0) a.partials[blockIdx.y * gridDim.x + blockIdx.x] = r;
 }
 
-// ---- NB / ZINB, 16-byte aligned operands: the training / validation kernel of the separate-head path (decoders
-// wider than 64 hidden units, validation).  Same decomposition as above -- one quad of genes per lane, rows strided
-// over grid.y -- but the two branches of the likelihood are no longer evaluated under divergence:
-//   * dense pass: the y = 0 formulas for every element (zinb_zero_elem / nb_zero_elem: ~100 VALU, the form K-HEADS
-//     uses); the ~7 % non-zero elements are queued per wave in LDS (pre-activations, count, size factor, destination);
-//   * sparse pass: whenever a wave holds 64 entries it evaluates the NB branch (lgamma / digamma differences) with
-//     all lanes busy and overwrites the three gradient values of those elements (4-byte stores behind the dense
-//     16-byte stores of the same wave: `s_waitcnt vmcnt(0)` in between orders them).
+// ---- NB / ZINB, 16-byte aligned operands, loss only: the validation kernel of the separate-head path (decoders wider than
+// 64 hidden units).  Same decomposition as above -- one quad of genes per lane, rows strided over grid.y -- but the two
+// branches of the likelihood are no longer evaluated under divergence:
+//   * dense pass: the y = 0 formulas for every element (zero_elem: ~100 VALU, the form K-HEADS uses); the ~7 % non-zero
+//     elements are queued per wave in LDS (pre-activations, count, size factor);
+//   * sparse pass: whenever a wave holds 64 entries it evaluates the NB branch (lgamma / digamma differences) with all
+//     lanes busy.
 // Before: both branches for every wave-row (~370 VALU per element) at 3.0-3.2 TB/s = 0.38-0.40 of the HBM peak.
 constexpr int kNzCap = 64 + 256;      // entries per wave: < 64 left over + up to 4 x 64 pushed per row
-struct NzEntry { float am, ad, ap, y, sf; unsigned dof, pad; };      // pad (a copy of dof): 32-byte entries
+// seven words, two of them padding (35 872 B of LDS per workgroup): with five-word entries the kernel measured 4-7 % slower on
+// the forms with a dropout head (2048 x 25 000, 7 % non-zero: 0.161 against 0.150 ms conditional, 0.125 against 0.120 ms constant
+// dispersion) and 5 % faster without one; the padding is written with the entry
+struct NzEntry { float am, ad, ap, y, sf; unsigned pad[2]; };
 
-template <bool HAS_PI, bool CONST_DISP, bool GRAD>
+template <bool HAS_PI, bool CONST_DISP>
 __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {     // 4 waves per SIMD: 128 registers
     constexpr int V = 4;
     __shared__ NzEntry queue[4][kNzCap];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     NzEntry* Q = queue[wave];
-    const int nvec = (a.G + V - 1) / V;
-    const int nseg = (nvec + 255) >> 8;
+    const Segments<V> segs(a.G);
     const long long cur = a.cursor ? *a.cursor : 0;
     double dacc = 0.0;
     int qn = 0;
@@ -185,41 +223,24 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
             const int c = qn < 64 ? qn : 64;
             const bool act = lane < c;
             const NzEntry e = Q[qn - c + (act ? lane : 0)];
-            float o1, o2, o3 = 0.f, nll;
-            if (HAS_PI) {
-                nll = zinb_nz_elem<CONST_DISP>(e.am, e.ad, e.ap, e.sf, e.y, a.ridge, o1, o2, o3);
-            } else {
-                float dmu = 0.f, dth = 0.f, dpi = 0.f;
-                const Heads hd = head_acts<false, CONST_DISP>(e.am, e.ad, 0.f, e.sf);
-                nll = nll_elem<false, true, true>(hd, e.y, a.ridge, dmu, dth, dpi);
-                o1 = dmu * hd.gm; o2 = dth * hd.gd;
-            }
+            const float nll = nonzero_elem<HAS_PI, CONST_DISP>(e.am, e.ad, e.ap, e.sf, e.y, a.ridge).nll;
             lsp += act ? nll : 0.f;
-            if (GRAD && act) {
-                __builtin_amdgcn_s_waitcnt(0x0f70);                       // vmcnt(0): the dense stores of these addresses are done
-                a.d_mean[e.dof] = o1 * a.inv_n;
-                a.d_disp[e.dof] = o2 * a.inv_n;
-                if (HAS_PI) a.d_pi[e.dof] = o3 * a.inv_n;
-            }
             qn -= c;
         }
     };
-    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const int q = seg * 256 + threadIdx.x;
-        const bool qv = q < nvec;
-        const int g = (qv ? q : 0) * V;
+    for (int seg = blockIdx.x; seg < segs.nseg; seg += gridDim.x) {
+        bool qv;
+        const int g = segs.gene(seg, qv);
         float vd[V] = {0.f, 0.f, 0.f, 0.f};
         if (CONST_DISP && qv) ldv<V>(a.theta_w + g, vd);
         // storage row of the NEXT iteration requested one iteration ahead: perm -> (size factor, counts) is a chain of
         // two memory round trips per row otherwise
-        long srow_n = a.perm ? (long)a.perm[cur + (blockIdx.y < a.B ? blockIdx.y : 0)] : (long)(cur + blockIdx.y);
+        long srow_n = storage_row(a.perm, cur, blockIdx.y < a.B ? blockIdx.y : 0);
         for (int row = blockIdx.y; row < a.B; row += gridDim.y) {
             const long srow = srow_n;
-            const int rown = row + gridDim.y < a.B ? row + gridDim.y : row;
-            srow_n = a.perm ? (long)a.perm[cur + rown] : (long)(cur + rown);
+            srow_n = storage_row(a.perm, cur, row + gridDim.y < a.B ? row + gridDim.y : row);
             const float sf = a.sf[srow];
             const long ao = (long)row * a.lda + g;
-            const long dof = (long)row * a.ldd + g;
             float vm[V] = {0.f, 0.f, 0.f, 0.f}, vp[V] = {0.f, 0.f, 0.f, 0.f}, vy[V] = {0.f, 0.f, 0.f, 0.f};
             if (qv) {
                 ldv<V>(a.a_mean + ao, vm);
@@ -227,31 +248,21 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
                 if (HAS_PI) ldv<V>(a.a_pi + ao, vp);
                 ldv<V>(a.y + srow * a.ldy + g, vy);
             }
-            float om[V], od[V], op[V];
             float lacc = 0.f;
             bool nz[V];
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const bool valid = qv && (g + j) < a.G;
-                nz[j] = valid && (HAS_PI ? !(vy[j] < kZeroThresh) : (vy[j] != 0.f));
-                float gmv, gdv, gpv = 0.f, nll;
-                if (HAS_PI) nll = zinb_zero_elem<CONST_DISP>(vm[j], vd[j], vp[j], sf, a.ridge, gmv, gdv, gpv);
-                else nll = nb_zero_elem<CONST_DISP>(vm[j], vd[j], sf, gmv, gdv);
+                nz[j] = valid && count_is_nonzero<HAS_PI>(vy[j]);
+                const float nll = zero_elem<HAS_PI, CONST_DISP>(vm[j], vd[j], vp[j], sf, a.ridge).nll;
                 lacc += (valid && !nz[j]) ? nll : 0.f;
-                const float sc = valid ? a.inv_n : 0.f;
-                om[j] = gmv * sc; od[j] = gdv * sc; op[j] = gpv * sc;
-            }
-            if (GRAD && qv) {
-                stv<V>(a.d_mean + dof, om);
-                stv<V>(a.d_disp + dof, od);
-                if (HAS_PI) stv<V>(a.d_pi + dof, op);
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const unsigned long long m = __ballot(nz[j]);
                 if (m) {
                     const int slot = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (nz[j]) Q[slot] = NzEntry{vm[j], vd[j], vp[j], vy[j], sf, (unsigned)(dof + j), (unsigned)(dof + j)};
+                    if (nz[j]) Q[slot] = NzEntry{vm[j], vd[j], vp[j], vy[j], sf, {0u, 0u}};
                     qn += __popcll(m);
                 }
             }
@@ -269,9 +280,9 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_compact_kernel(NllArgs a) {  
 // its 256 genes per iteration, evaluates the y = 0 formulas of both into registers, queues the non-zero elements of both
 // rows in LDS (row 0 first), evaluates the queue 64 entries at a time with the NB branch -- each result written back over
 // its queue entry -- and every lane then fetches the results of its own non-zero elements (its slot follows from the
-// wave-uniform ballot masks) before the one dense store of the two rows.  Against the patching form: no 2- / 4-byte
-// scattered stores behind the dense ones (measured at configs[4]'s decoder, 2048 x 25 000, bf16 pieces out: 0.445 ms, of
-// which 0.145 ms were the patches -- partial-line writes -- profiles/r03_zinb_rows_notes.txt).
+// wave-uniform ballot masks) before the one dense store of the two rows.  Against patching the non-zero elements' gradients
+// behind a dense store of the y = 0 values: no 2- / 4-byte scattered stores (measured at configs[4]'s decoder, 2048 x 25 000,
+// bf16 pieces out: 0.445 ms, of which 0.145 ms were the patches -- partial-line writes -- profiles/r03_zinb_rows_notes.txt).
 constexpr int kRowsPerIter = 2;
 template <bool HAS_PI, bool CONST_DISP, int PL>          // PL: 0 fp32 gradient planes, 1 three bf16 pieces, 2 two fp16 pieces of g 2^kD
 __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
@@ -280,15 +291,13 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
     __shared__ float4 queue[4][R * 256];                   // 8 KB per wave: every element of both rows may be non-zero
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4* Q = queue[wave];
-    const int nvec = (a.G + V - 1) / V;
-    const int nseg = (nvec + 255) >> 8;
+    const Segments<V> segs(a.G);
     const long long cur = a.cursor ? *a.cursor : 0;
     double dacc = 0.0;
     float lsp = 0.f;
-    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const int q = seg * 256 + threadIdx.x;
-        const bool qv = q < nvec;
-        const int g = (qv ? q : 0) * V;
+    for (int seg = blockIdx.x; seg < segs.nseg; seg += gridDim.x) {
+        bool qv;
+        const int g = segs.gene(seg, qv);
         float vd[R][V];
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -306,8 +315,7 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int rw = blockIdx.y + r * gridDim.y;
-            const int rc = rw < a.B ? rw : 0;
-            srow_n[r] = a.perm ? (long)a.perm[cur + rc] : (long)(cur + rc);
+            srow_n[r] = storage_row(a.perm, cur, rw < a.B ? rw : 0);
         }
         for (int row0 = blockIdx.y; row0 < a.B; row0 += R * gridDim.y) {
             long srow[R];
@@ -320,8 +328,7 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
                 rv[r] = row < a.B;
                 srow[r] = srow_n[r];
                 const int rn = row + R * gridDim.y;
-                const int rc = rn < a.B ? rn : (rv[r] ? row : 0);
-                srow_n[r] = a.perm ? (long)a.perm[cur + rc] : (long)(cur + rc);
+                srow_n[r] = storage_row(a.perm, cur, rn < a.B ? rn : (rv[r] ? row : 0));
                 sf[r] = a.sf[srow[r]];
 #pragma unroll
                 for (int j = 0; j < V; ++j) { vm[r][j] = 0.f; vp[r][j] = 0.f; vy[r][j] = 0.f; }
@@ -344,13 +351,11 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     const bool valid = qv && rv[r] && (g + j) < a.G;
-                    nz[r][j] = valid && (HAS_PI ? !(vy[r][j] < kZeroThresh) : (vy[r][j] != 0.f));
-                    float gmv, gdv, gpv = 0.f, nll;
-                    if (HAS_PI) nll = zinb_zero_elem<CONST_DISP>(vm[r][j], vd[r][j], vp[r][j], sf[r], a.ridge, gmv, gdv, gpv);
-                    else nll = nb_zero_elem<CONST_DISP>(vm[r][j], vd[r][j], sf[r], gmv, gdv);
-                    lacc += (valid && !nz[r][j]) ? nll : 0.f;
+                    nz[r][j] = valid && count_is_nonzero<HAS_PI>(vy[r][j]);
+                    const Elem z = zero_elem<HAS_PI, CONST_DISP>(vm[r][j], vd[r][j], vp[r][j], sf[r], a.ridge);
+                    lacc += (valid && !nz[r][j]) ? z.nll : 0.f;
                     const float sc = valid ? psc : 0.f, scd = valid ? (CONST_DISP ? a.inv_n : psc) : 0.f;
-                    om[r][j] = gmv * sc; od[r][j] = gdv * scd; op[r][j] = gpv * sc;
+                    om[r][j] = z.gm * sc; od[r][j] = z.gd * scd; op[r][j] = z.gp * sc;
                     const unsigned long long m = __ballot(nz[r][j]);
                     mask[r][j] = m; base[r][j] = qn;
                     if (nz[r][j]) {
@@ -370,17 +375,19 @@ __global__ __launch_bounds__(256, 4) void zinb_nll_rows_kernel(NllArgs a) {
                 float esf = sf[R - 1];
 #pragma unroll
                 for (int r = R - 2; r >= 0; --r) esf = idx < nend[r] ? sf[r] : esf;
-                float o1, o2, o3 = 0.f, nll;
+                Elem o;
                 if (HAS_PI) {
-                    nll = zinb_nz_elem<CONST_DISP>(e.x, e.y, e.z, esf, e.w, a.ridge, o1, o2, o3);
+                    o = nonzero_elem<true, CONST_DISP>(e.x, e.y, e.z, esf, e.w, a.ridge);
                 } else {
+                    // nonzero_elem<false, ..> written out: through the helper the compiler moves the product mu = exp(a_mean) sf
+                    // next to the addition mu + eps and contracts the two (one rounding, not two: other bits in the NB planes)
                     float dmu = 0.f, dth = 0.f, dpi = 0.f;
                     const Heads hd = head_acts<false, CONST_DISP>(e.x, e.y, 0.f, esf);
-                    nll = nll_elem<false, true, true>(hd, e.w, a.ridge, dmu, dth, dpi);
-                    o1 = dmu * hd.gm; o2 = dth * hd.gd;
+                    o.nll = nll_elem<false, true, true>(hd, e.w, a.ridge, dmu, dth, dpi);
+                    o.gm = dmu * hd.gm; o.gd = dth * hd.gd; o.gp = 0.f;
                 }
-                lsp += act ? nll : 0.f;
-                if (act) Q[idx] = make_float4(o1 * psc, o2 * (CONST_DISP ? a.inv_n : psc), o3 * psc, 0.f);
+                lsp += act ? o.nll : 0.f;
+                if (act) Q[idx] = make_float4(o.gm * psc, o.gd * (CONST_DISP ? a.inv_n : psc), o.gp * psc, 0.f);
             }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -447,356 +454,37 @@ __global__ void step_end_kernel(const float* loss, double weight, float* hist, i
     }
 }
 
-struct InferArgs {
-    const float *a_mean, *a_disp, *a_pi, *sf;
-    float *mean_sf, *theta, *pi;
-    long lda, ldo;
-    int B, G;
-    int linear_mean;
-};
-
-// clip_by_value as comparisons: a NaN stays a NaN, as in the reference (fminf / fmaxf return their other argument)
-__device__ __forceinline__ float clip_keep_nan(float x, float lo, float hi) {
-    return x < lo ? lo : (x > hi ? hi : x);
+// the launch of every kernel above over a [B, G] batch with V genes per lane, and the partials it writes
+struct NllGrid { dim3 grid; int n_partials; };
+NllGrid nll_grid(int B, int G, int V) {
+    const int nvec = (G + V - 1) / V;
+    const int nseg = (nvec + 255) / 256;
+    const int gx = nseg < kMaxPartials ? nseg : kMaxPartials;
+    int gy = kMaxPartials / gx;
+    if (gy > B) gy = B;
+    if (gy < 1) gy = 1;
+    return {dim3(gx, gy), gx * gy};
 }
 
-// the mean head's activation (dca/network.py:38 MeanAct; the linear mean of ae_type 'normal'): the one expression
-// heads_infer_kernel stores and group_moments_kernel sums
-__device__ __forceinline__ float mean_act(float a, bool linear) {
-    return linear ? a : clip_keep_nan(expf(a), 1e-5f, 1e6f);
-}
+template <class K>
+void run(K kernel, dim3 grid, hipStream_t s, const NllArgs& a) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a); }
 
-template <int V>
-__global__ __launch_bounds__(256) void heads_infer_kernel(InferArgs a) {
-    const int nvec = (a.G + V - 1) / V;
-    const int nseg = (nvec + 255) >> 8;
-    const long total = (long)a.B * nseg;
-    for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int row = (int)(item / nseg);
-        const int q = (int)(item - (long)row * nseg) * 256 + threadIdx.x;
-        if (q >= nvec) continue;
-        const int g = q * V;
-        const float sf = a.sf[row];
-        const long ao = (long)row * a.lda + g, oo = (long)row * a.ldo + g;
-        float v[V], o[V];
-        if (a.mean_sf) {
-            ldv<V>(a.a_mean + ao, v);
-#pragma unroll
-            for (int j = 0; j < V; ++j) o[j] = mean_act(v[j], a.linear_mean) * sf;
-            stv<V>(a.mean_sf + oo, o);
-        }
-        if (a.theta) {
-            ldv<V>(a.a_disp + ao, v);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float sp = fmaxf(v[j], 0.f) + log1pf(expf(-fabsf(v[j])));
-                o[j] = clip_keep_nan(sp, 1e-4f, 1e4f);
-            }
-            stv<V>(a.theta + oo, o);
-        }
-        if (a.pi) {
-            ldv<V>(a.a_pi + ao, v);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float ex = expf(-fabsf(v[j]));
-                const float s = 1.f / (1.f + ex);
-                o[j] = v[j] >= 0.f ? s : ex * s;
-            }
-            stv<V>(a.pi + oo, o);
-        }
-    }
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// ---- K-SCORE: the two marginals of the element-wise NLL of a fitted model (dcahip_nll_marginals): per-row sums and
-// per-gene sums over consecutive rows, every element value accumulated in double.  The grid of zinb_nll_kernel:
-// blockIdx.x walks the gene segments (256 lanes x V genes), blockIdx.y = slice strides over the rows.
-//   * per gene: every lane keeps the V column sums of its quad over the rows of its slice and stores them to
-//     gene_part[slice][g] -- no reduction in the kernel;
-//   * per row: every wave adds up its 64 x V genes with shuffles and stores to row_part[segment * 4 + wave][row] -- no
-//     barrier in the row loop.
-// nll_finish_kernel adds the slices / the segment partials in index order.  Every workspace word it reads is written by
-// exactly one lane on every call and no sum depends on scheduling (no atomics): two calls give the same bits.
-// One readable kernel, both branches of the likelihood under divergence: scoring is a pass per dataset, not per step.
-constexpr int kScoreSlices = 64;
-
-struct MargArgs {
-    const float *a_mean, *a_disp, *a_pi, *theta_w, *y, *sf;
-    long lda, ldy;
-    double *gene_part, *row_part;
-    int B, G;
-    float ridge;
-};
-
-template <bool HAS_PI, bool CONST_DISP, int V, int LOSS>
-__global__ __launch_bounds__(256) void nll_marginals_kernel(MargArgs a) {
-    const int nvec = (a.G + V - 1) / V;
-    const int seg = blockIdx.x, wave = threadIdx.x >> 6;
-    const int q = seg * 256 + threadIdx.x;
-    const bool qv = q < nvec;
-    const int g = (qv ? q : 0) * V;
-    bool valid[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) valid[j] = qv && (g + j) < a.G;
-    float vd[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) vd[j] = 0.f;
-    if (CONST_DISP && qv) ldv<V>(a.theta_w + g, vd);
-    double col[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) col[j] = 0.0;
-    double* rp = a.row_part + (long)(seg * 4 + wave) * a.B;
-    const bool wave_live = seg * 256 + wave * 64 < nvec;         // a wave past the last quad only zeroes its partials
-    for (int row = blockIdx.y; row < a.B; row += gridDim.y) {
-        if (!wave_live) {
-            if ((threadIdx.x & 63) == 0) rp[row] = 0.0;
-            continue;
-        }
-        const float sf = a.sf[row];
-        float vm[V], vp[V], vy[V];
-#pragma unroll
-        for (int j = 0; j < V; ++j) { vm[j] = 0.f; vp[j] = 0.f; vy[j] = 0.f; }
-        if (qv) {
-            const long ao = (long)row * a.lda + g;
-            ldv<V>(a.a_mean + ao, vm);
-            if (!CONST_DISP && LOSS == 0) ldv<V>(a.a_disp + ao, vd);
-            if (HAS_PI) ldv<V>(a.a_pi + ao, vp);
-            ldv<V>(a.y + (long)row * a.ldy + g, vy);
-        }
-        double racc = 0.0;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            // the padding of a ragged last quad (columns G .. roundup4(G) - 1) holds anything: evaluated on zeros, not added
-            const float am = valid[j] ? vm[j] : 0.f, ad = valid[j] ? vd[j] : 0.f, ap = valid[j] ? vp[j] : 0.f;
-            const float y = valid[j] ? vy[j] : 0.f;
-            float nll, d0 = 0.f, d1 = 0.f, d2 = 0.f;
-            if (LOSS == 1) nll = poisson_elem(am, sf, y, d0);
-            else if (LOSS == 2) nll = mse_elem(am, sf, y, d0);
-            else nll = nll_elem<HAS_PI, false>(head_acts<HAS_PI, CONST_DISP>(am, ad, ap, sf), y, a.ridge, d0, d1, d2);
-            const double v = valid[j] ? (double)nll : 0.0;
-            col[j] += v;
-            racc += v;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) racc += __shfl_down(racc, off, 64);
-        if ((threadIdx.x & 63) == 0) rp[row] = racc;
-    }
-    double* gp = a.gene_part + (long)blockIdx.y * a.G + g;
-#pragma unroll
-    for (int j = 0; j < V; ++j)
-        if (valid[j]) gp[j] = col[j];
-}
-
-__global__ __launch_bounds__(256) void nll_finish_kernel(const double* __restrict__ gene_part, int S,
-                                                         const double* __restrict__ row_part, int P, int B, int G,
-                                                         double* __restrict__ cell_out, double* __restrict__ gene_acc) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < G) {
-        double s = 0.0;
-        for (int k = 0; k < S; ++k) s += gene_part[(long)k * G + i];
-        gene_acc[i] += s;
-    } else if (i < (long)G + B) {
-        const long r = i - G;
-        double s = 0.0;
-        for (int k = 0; k < P; ++k) s += row_part[(long)k * B + r];
-        cell_out[r] = s;
-    }
-}
-
-// doubles of the two partial arrays: [slices][G] and, for the scalar path's 256-gene segments (the larger count),
-// [segments * 4][B]
-long marginals_doubles(int B, int G) {
-    const long S = B < kScoreSlices ? B : kScoreSlices;
-    return S * G + (long)((G + 255) / 256) * 4 * B;
-}
-
-// ---- K-GROUPS: per-group first and second moments of the denoised expression (dcahip_group_moments): for every group
-// code k and gene g the sums of x and x^2 over the rows that carry k, x = the value heads_infer_kernel stores (mean_act,
-// times the row's size factor) or its log1p, every value converted to double before it is added.
-//   * blockIdx.x walks the gene segments (256 lanes x V genes), blockIdx.y = group code x row slice (S slices of
-//     consecutive rows: enough workgroups when segments x groups alone do not fill the chip);
-//   * a workgroup takes its slice 1 024 rows at a time: all four waves compact the indices of the rows that carry its code
-//     into LDS in ascending order (ballot + prefix over the wave counts), then every lane walks that list with
-//     kGroupLoads independent row loads in flight and adds them up in list order;
-//   * S == 1: the lane that owns (code, gene) adds its sums to the accumulators itself; S > 1: they go to
-//     part[moment][slice][code][g] and group_finish_kernel adds the slices in index order.
-// A row whose code is not in [0, K) matches no workgroup: it is never an index.  Every word of `part` that the finish reads is
-// written by exactly one lane on every call (a slice without a row of the code writes zeros); no atomics, no sum that
-// depends on scheduling: two calls give the same bits.
-constexpr int kGroupTile = 1024;            // rows compacted at a time (4 passes of the 256 lanes)
-constexpr int kGroupLoads = 4;              // independent row loads in flight per lane
-constexpr int kGroupMaxK = 4096, kGroupMaxSlices = 64, kGroupBlocks = 1024;
-
-struct GroupArgs {
-    const float *a_mean, *sf;               // sf == nullptr: DCAHIP_GROUP_NO_SF
-    const int* codes;
-    long lda, ldg;
-    double *sum_acc, *sumsq_acc, *part;
-    int B, G, K, S, rows_per;
-    int linear_mean, log1p;
-};
-
-__device__ __forceinline__ float group_value(float a, float sf, bool has_sf, bool linear, bool log1p) {
-    float x = mean_act(a, linear);
-    if (has_sf) x = x * sf;
-    return log1p ? log1pf(x) : x;
-}
-
-template <int V>
-__global__ __launch_bounds__(256) void group_moments_kernel(GroupArgs a) {
-    __shared__ int list[kGroupTile];
-    __shared__ int cnt[kGroupTile / 64];
-    constexpr int P = kGroupTile / 256;
-    const int nvec = (a.G + V - 1) / V;
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const bool qv = q < nvec;
-    const int g = (qv ? q : 0) * V;
-    const int code = blockIdx.y / a.S, slice = blockIdx.y - code * a.S;
-    const int r_begin = slice * a.rows_per;
-    const int r_end = r_begin + a.rows_per < a.B ? r_begin + a.rows_per : a.B;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool has_sf = a.sf != nullptr, linear = a.linear_mean != 0, lg = a.log1p != 0;
-    double s1[V], s2[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) { s1[j] = 0.0; s2[j] = 0.0; }
-    bool any = false;
-    for (int t0 = r_begin; t0 < r_end; t0 += kGroupTile) {
-        // the rows of this tile that carry `code`, ascending: pass p looks at rows t0 + p * 256 + lane id
-        bool m[P];
-        unsigned long long bal[P];
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int r = t0 + p * 256 + (int)threadIdx.x;
-            m[p] = r < r_end && a.codes[r] == code;
-            bal[p] = __ballot(m[p]);
-            if (lane == 0) cnt[p * 4 + wave] = __popcll(bal[p]);
-        }
-        __syncthreads();
-        int n = 0, base[P];
-#pragma unroll
-        for (int i = 0; i < P * 4; ++i) {
-            if ((i & 3) == wave) base[i >> 2] = n;
-            n += cnt[i];
-        }
-#pragma unroll
-        for (int p = 0; p < P; ++p)
-            if (m[p]) list[base[p] + __popcll(bal[p] & ((1ull << lane) - 1ull))] = t0 + p * 256 + (int)threadIdx.x;
-        __syncthreads();
-        any = any || n > 0;
-        if (qv) {
-            int i = 0;
-            for (; i + kGroupLoads <= n; i += kGroupLoads) {
-                float v[kGroupLoads][V], f[kGroupLoads];
-#pragma unroll
-                for (int u = 0; u < kGroupLoads; ++u) {
-                    const int row = __builtin_amdgcn_readfirstlane(list[i + u]);
-                    ldv<V>(a.a_mean + (long)row * a.lda + g, v[u]);
-                    f[u] = has_sf ? a.sf[row] : 1.f;
-                }
-#pragma unroll
-                for (int u = 0; u < kGroupLoads; ++u)
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        const double x = (double)group_value(v[u][j], f[u], has_sf, linear, lg);
-                        s1[j] += x;
-                        s2[j] += x * x;
-                    }
-            }
-            for (; i < n; ++i) {
-                const int row = __builtin_amdgcn_readfirstlane(list[i]);
-                float v[V];
-                ldv<V>(a.a_mean + (long)row * a.lda + g, v);
-                const float f = has_sf ? a.sf[row] : 1.f;
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const double x = (double)group_value(v[j], f, has_sf, linear, lg);
-                    s1[j] += x;
-                    s2[j] += x * x;
-                }
-            }
-        }
-        // no barrier here: the next tile's cnt writes come after this tile's cnt reads (the barrier above), its list writes
-        // after its own first barrier, which no wave passes before every wave has finished this walk
-    }
-    if (!qv) return;
-    // columns G .. roundup4(G) - 1 of a ragged last quad were summed in registers only
-    if (a.S == 1) {
-        if (!any) return;
-        double* o1 = a.sum_acc + (long)code * a.ldg + g;
-        double* o2 = a.sumsq_acc + (long)code * a.ldg + g;
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-            if (g + j < a.G) { o1[j] += s1[j]; o2[j] += s2[j]; }
-    } else {
-        const long skg = (long)a.S * a.K * a.G;
-        double* o = a.part + ((long)slice * a.K + code) * a.G + g;
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-            if (g + j < a.G) { o[j] = s1[j]; o[skg + j] = s2[j]; }
-    }
-}
-
-__global__ __launch_bounds__(256) void group_finish_kernel(const double* __restrict__ part, int S, int K, int G, long ldg,
-                                                           double* __restrict__ sum_acc, double* __restrict__ sumsq_acc) {
-    const long kg = (long)K * G;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= kg) return;
-    const long code = i / G, g = i - code * G;
-    double t1 = 0.0, t2 = 0.0;
-    for (int s = 0; s < S; ++s) {
-        t1 += part[(long)s * kg + i];
-        t2 += part[(long)(S + s) * kg + i];
-    }
-    sum_acc[code * ldg + g] += t1;
-    sumsq_acc[code * ldg + g] += t2;
-}
-
-// most row slices of K-GROUPS for V genes per lane: about kGroupBlocks workgroups, at most one slice per row.  Non-decreasing
-// in B and non-increasing in V
-long group_slice_cap(int B, int G, int K, int V) {
-    const long nseg = ((G + V - 1) / V + 255) / 256;
-    long s = (kGroupBlocks + nseg * K - 1) / (nseg * K);
-    if (s > kGroupMaxSlices) s = kGroupMaxSlices;
-    if (s > B) s = B;
-    return s < 1 ? 1 : s;
-}
-
-// the slices a call uses: rows_per = ceil(B / cap) consecutive rows each, S = ceil(B / rows_per) <= cap of them (no empty one)
-int group_slices(int B, int G, int K, int V, int* rows_per) {
-    const long s = group_slice_cap(B, G, K, V);
-    *rows_per = (int)((B + s - 1) / s);
-    return (B + *rows_per - 1) / *rows_per;
-}
-
-// doubles of part, an upper bound that is non-decreasing in B (a workspace sized for a chunk serves every shorter chunk): the
-// cap of the 16-byte path, which has the fewest segments and so the most slices
-long group_doubles(int B, int G, int K) {
-    const long S = group_slice_cap(B, G, K, 4);
-    return S > 1 ? 2 * S * K * G : 1;
-}
-
-template <bool HAS_PI, bool CONST_DISP, int LOSS>
-void launch_marginals(const MargArgs& a, bool vec, dim3 grid, hipStream_t s) {
-    if (vec) hipLaunchKernelGGL((nll_marginals_kernel<HAS_PI, CONST_DISP, 4, LOSS>), grid, dim3(256), 0, s, a);
-    else     hipLaunchKernelGGL((nll_marginals_kernel<HAS_PI, CONST_DISP, 1, LOSS>), grid, dim3(256), 0, s, a);
-}
-
-template <bool HAS_PI, bool CONST_DISP, bool GRAD>
+// the kernel of a dcahip_zinb_nll call; only what a call can reach is instantiated
+template <bool P, bool C, bool GRAD, int LOSS>
 int launch_nll(const NllArgs& a, bool vec, dim3 grid, hipStream_t s) {
-    // the compacted kernel addresses gradient elements with 32 bits
-    const bool fits = !GRAD || (long)a.B * a.ldd < (1L << 32);
-    if (vec && fits && GRAD) hipLaunchKernelGGL((zinb_nll_rows_kernel<HAS_PI, CONST_DISP, 0>), grid, dim3(256), 0, s, a);
-    else if (vec && fits) hipLaunchKernelGGL((zinb_nll_compact_kernel<HAS_PI, CONST_DISP, GRAD>), grid, dim3(256), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((zinb_nll_kernel<HAS_PI, CONST_DISP, GRAD, 4>), grid, dim3(256), 0, s, a);
-    else     hipLaunchKernelGGL((zinb_nll_kernel<HAS_PI, CONST_DISP, GRAD, 1>), grid, dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-template <int LOSS, bool GRAD>
-int launch_nll_simple(const NllArgs& a, bool vec, dim3 grid, hipStream_t s) {
-    if (vec) hipLaunchKernelGGL((zinb_nll_kernel<false, false, GRAD, 4, LOSS>), grid, dim3(256), 0, s, a);
-    else     hipLaunchKernelGGL((zinb_nll_kernel<false, false, GRAD, 1, LOSS>), grid, dim3(256), 0, s, a);
+    if constexpr (LOSS != 0) {
+        if (vec) run(zinb_nll_kernel<false, false, GRAD, 4, LOSS>, grid, s, a);
+        else     run(zinb_nll_kernel<false, false, GRAD, 1, LOSS>, grid, s, a);
+    } else if constexpr (GRAD) {
+        // kept from the form that patched gradients through 32-bit element offsets; the row-pair kernel has none
+        const bool fits = (long)a.B * a.ldd < (1L << 32);
+        if (vec && fits) run(zinb_nll_rows_kernel<P, C, 0>, grid, s, a);
+        else if (vec)    run(zinb_nll_kernel<P, C, true, 4>, grid, s, a);
+        else             run(zinb_nll_kernel<P, C, true, 1>, grid, s, a);
+    } else {
+        if (vec) run(zinb_nll_compact_kernel<P, C>, grid, s, a);
+        else     run(zinb_nll_kernel<P, C, false, 1>, grid, s, a);
+    }
     return (int)hipGetLastError();
 }
 
@@ -820,31 +508,23 @@ extern "C" int dcahip_zinb_nll(const float* a_mean, const float* a_disp, const f
     if (has_pi && !a_pi) return DCAHIP_EINVAL;
     if (loss == 0 && (cdisp ? (theta_w == nullptr) : (a_disp == nullptr))) return DCAHIP_EINVAL;
     if (grad && loss == 0 && (!d_disp || (has_pi && !d_pi))) return DCAHIP_EINVAL;
-    bool vec = (lda % 4 == 0) && (ldy % 4 == 0) && al16(a_mean) && al16(y) &&
-               (loss != 0 || (cdisp ? al16(theta_w) : al16(a_disp))) && (!has_pi || al16(a_pi)) &&
-               lda >= ((G + 3) & ~3) && ldy >= ((G + 3) & ~3);
+    bool vec = nll_reads_vec(a_mean, a_disp, a_pi, lda, theta_w, y, ldy, G, has_pi, cdisp, loss);
     if (grad) vec = vec && (ldd % 4 == 0) && ldd >= ((G + 3) & ~3) && al16(d_mean) && (loss != 0 || al16(d_disp)) && (!has_pi || al16(d_pi));
     NllArgs a{a_mean, a_disp, a_pi, theta_w, y, sf, perm, cursor, lda, ldy, ldd,
               d_mean, d_disp, d_pi, loss_partials, B, G, ridge, inv_n, {nullptr, nullptr, nullptr}, 0, 0};
-    const int V = vec ? 4 : 1;
-    const int nvec = (G + V - 1) / V;
-    const int nseg = (nvec + 255) / 256;
-    const int gx = nseg < kMaxPartials ? nseg : kMaxPartials;
-    int gy = kMaxPartials / gx;
-    if (gy > B) gy = B;
-    if (gy < 1) gy = 1;
-    const dim3 grid(gx, gy);
-    if (n_partials_out) *n_partials_out = gx * gy;
+    const NllGrid ng = nll_grid(B, G, vec ? 4 : 1);
+    if (n_partials_out) *n_partials_out = ng.n_partials;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (loss == 1) return grad ? launch_nll_simple<1, true>(a, vec, grid, s) : launch_nll_simple<1, false>(a, vec, grid, s);
-    if (loss == 2) return grad ? launch_nll_simple<2, true>(a, vec, grid, s) : launch_nll_simple<2, false>(a, vec, grid, s);
-#define DCA_DISPATCH(P, C)                                                  \
-    return grad ? launch_nll<P, C, true>(a, vec, grid, s) : launch_nll<P, C, false>(a, vec, grid, s)
-    if (has_pi && cdisp) { DCA_DISPATCH(true, true); }
-    if (has_pi) { DCA_DISPATCH(true, false); }
-    if (cdisp) { DCA_DISPATCH(false, true); }
-    DCA_DISPATCH(false, false);
-#undef DCA_DISPATCH
+    auto launch = [&](auto P, auto C, auto L) {
+        return grad ? launch_nll<P.value, C.value, true, L.value>(a, vec, ng.grid, s)
+                    : launch_nll<P.value, C.value, false, L.value>(a, vec, ng.grid, s);
+    };
+    using std::integral_constant;
+    if (loss != 0) {
+        return loss == 1 ? launch(std::false_type{}, std::false_type{}, integral_constant<int, 1>{})
+                         : launch(std::false_type{}, std::false_type{}, integral_constant<int, 2>{});
+    }
+    return dispatch_pc(has_pi, cdisp, [&](auto P, auto C) { return launch(P, C, integral_constant<int, 0>{}); });
 }
 
 static int zinb_nll_planes_impl(int h2, float pscale, const float* a_mean, const float* a_disp, const float* a_pi, long lda,
@@ -859,38 +539,24 @@ static int zinb_nll_planes_impl(int h2, float pscale, const float* a_mean, const
     if ((has_pi && !a_pi) || (cdisp ? (!theta_w || !d_theta) : !a_disp)) return DCAHIP_EINVAL;
     const int G4 = (G + 3) & ~3;
     // 16-byte vectors in, 8-byte piece vectors out; 32-bit element offsets inside a plane
-    if (lda % 4 || ldy % 4 || lda < G4 || ldy < G4 || !al16(a_mean) || !al16(y) || (has_pi && !al16(a_pi)) ||
-        (cdisp ? !al16(theta_w) : !al16(a_disp)))
-        return DCAHIP_EINVAL;
+    if (!nll_reads_vec(a_mean, a_disp, a_pi, lda, theta_w, y, ldy, G, has_pi, cdisp, 0)) return DCAHIP_EINVAL;
     if (ldp % 4 || plane_stride % 4 || !al16(d_planes) || col_mean % 4 || (!cdisp && col_disp % 4) || (has_pi && col_pi % 4) ||
         (long)B * ldp >= (1L << 32) || plane_stride < (long)B * ldp)
         return DCAHIP_EINVAL;
     if (col_mean + G4 > ldp || (!cdisp && col_disp + G4 > ldp) || (has_pi && col_pi + G4 > ldp)) return DCAHIP_EINVAL;
     if (cdisp && (ldd_theta % 4 || ldd_theta < G4 || !al16(d_theta) || (long)B * ldd_theta >= (1L << 32))) return DCAHIP_EINVAL;
-    unsigned short* P = static_cast<unsigned short*>(d_planes);
+    unsigned short* pl = static_cast<unsigned short*>(d_planes);
     NllArgs a{a_mean, a_disp, a_pi, theta_w, y, sf, perm, cursor, lda, ldy, cdisp ? ldd_theta : 0,
               nullptr, cdisp ? d_theta : nullptr, nullptr, loss_partials, B, G, ridge, inv_n,
-              {P + col_mean, cdisp ? nullptr : P + col_disp, has_pi ? P + col_pi : nullptr}, ldp, plane_stride, pscale};
-    const int nvec = (G + 3) / 4;
-    const int nseg = (nvec + 255) / 256;
-    const int gx = nseg < kMaxPartials ? nseg : kMaxPartials;
-    int gy = kMaxPartials / gx;
-    if (gy > B) gy = B;
-    if (gy < 1) gy = 1;
-    const dim3 grid(gx, gy);
-    if (n_partials_out) *n_partials_out = gx * gy;
+              {pl + col_mean, cdisp ? nullptr : pl + col_disp, has_pi ? pl + col_pi : nullptr}, ldp, plane_stride, pscale};
+    const NllGrid ng = nll_grid(B, G, 4);
+    const dim3 grid = ng.grid;
+    if (n_partials_out) *n_partials_out = ng.n_partials;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (h2) {
-        if (has_pi && cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, true, 2>), grid, dim3(256), 0, s, a);
-        else if (has_pi) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, false, 2>), grid, dim3(256), 0, s, a);
-        else if (cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<false, true, 2>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((zinb_nll_rows_kernel<false, false, 2>), grid, dim3(256), 0, s, a);
-        return (int)hipGetLastError();
-    }
-    if (has_pi && cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, true, 1>), grid, dim3(256), 0, s, a);
-    else if (has_pi) hipLaunchKernelGGL((zinb_nll_rows_kernel<true, false, 1>), grid, dim3(256), 0, s, a);
-    else if (cdisp) hipLaunchKernelGGL((zinb_nll_rows_kernel<false, true, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((zinb_nll_rows_kernel<false, false, 1>), grid, dim3(256), 0, s, a);
+    dispatch_pc(has_pi, cdisp, [&](auto P, auto C) {
+        if (h2) run(zinb_nll_rows_kernel<P.value, C.value, 2>, grid, s, a);
+        else    run(zinb_nll_rows_kernel<P.value, C.value, 1>, grid, s, a);
+    });
     return (int)hipGetLastError();
 }
 
@@ -917,78 +583,6 @@ extern "C" int dcahip_zinb_nll_planes_h2(const float* a_mean, const float* a_dis
                                 n_partials_out, stream);
 }
 
-extern "C" int dcahip_nll_marginals_workspace_doubles(int B, int G) {
-    if (B <= 0 || G <= 0) return 0;
-    const long n = marginals_doubles(B, G);
-    return n > 0x7fffffffL ? DCAHIP_EINVAL : (int)n;
-}
-
-extern "C" int dcahip_nll_marginals(const float* a_mean, const float* a_disp, const float* a_pi, long lda,
-                                    const float* theta_w, const float* y, long ldy, const float* sf,
-                                    int B, int G, float ridge, int flags,
-                                    double* cell_out, double* gene_acc, double* workspace, void* stream) {
-    const bool has_pi = flags & DCAHIP_NLL_HAS_PI, cdisp = flags & DCAHIP_NLL_CONST_DISP;
-    const int loss = (flags & DCAHIP_NLL_POISSON) ? 1 : ((flags & DCAHIP_NLL_MSE) ? 2 : 0);
-    if (B <= 0 || G <= 0 || !a_mean || !y || !sf || !cell_out || !gene_acc || !workspace) return DCAHIP_EINVAL;
-    if (loss != 0 && (has_pi || cdisp)) return DCAHIP_EINVAL;
-    if (has_pi && !a_pi) return DCAHIP_EINVAL;
-    if (loss == 0 && (cdisp ? (theta_w == nullptr) : (a_disp == nullptr))) return DCAHIP_EINVAL;
-    if (lda < G || ldy < G || marginals_doubles(B, G) > 0x7fffffffL) return DCAHIP_EINVAL;
-    const bool vec = (lda % 4 == 0) && (ldy % 4 == 0) && al16(a_mean) && al16(y) &&
-                     (loss != 0 || (cdisp ? al16(theta_w) : al16(a_disp))) && (!has_pi || al16(a_pi)) &&
-                     lda >= ((G + 3) & ~3) && ldy >= ((G + 3) & ~3);
-    const int V = vec ? 4 : 1;
-    const int nseg = ((G + V - 1) / V + 255) / 256;
-    const int S = B < kScoreSlices ? B : kScoreSlices;
-    MargArgs a{a_mean, a_disp, a_pi, theta_w, y, sf, lda, ldy, workspace, workspace + (long)S * G, B, G, ridge};
-    const dim3 grid(nseg, S);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (loss == 1) launch_marginals<false, false, 1>(a, vec, grid, s);
-    else if (loss == 2) launch_marginals<false, false, 2>(a, vec, grid, s);
-    else if (has_pi && cdisp) launch_marginals<true, true, 0>(a, vec, grid, s);
-    else if (has_pi) launch_marginals<true, false, 0>(a, vec, grid, s);
-    else if (cdisp) launch_marginals<false, true, 0>(a, vec, grid, s);
-    else launch_marginals<false, false, 0>(a, vec, grid, s);
-    const long items = (long)G + B;
-    hipLaunchKernelGGL(nll_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
-                       a.gene_part, S, a.row_part, nseg * 4, B, G, cell_out, gene_acc);
-    return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_group_moments_workspace_doubles(int B, int G, int K) {
-    if (B <= 0 || G <= 0 || K <= 0) return 0;
-    if (K > kGroupMaxK) return DCAHIP_EINVAL;
-    const long n = group_doubles(B, G, K);
-    return n > 0x7fffffffL ? DCAHIP_EINVAL : (int)n;
-}
-
-extern "C" int dcahip_group_moments(const float* a_mean, long lda, const float* sf, const int* codes,
-                                    int B, int G, int K, int flags,
-                                    double* sum_acc, double* sumsq_acc, long ldg,
-                                    double* workspace, void* stream) {
-    const bool no_sf = flags & DCAHIP_GROUP_NO_SF, lg = flags & DCAHIP_GROUP_LOG1P, linear = flags & DCAHIP_NLL_MSE;
-    if (B <= 0 || G <= 0 || K <= 0 || K > kGroupMaxK) return DCAHIP_EINVAL;
-    if (!a_mean || !codes || !sum_acc || !sumsq_acc || !workspace || (!no_sf && !sf)) return DCAHIP_EINVAL;
-    if (lda < G || ldg < G || (linear && lg) || group_doubles(B, G, K) > 0x7fffffffL) return DCAHIP_EINVAL;
-    const bool vec = (lda % 4 == 0) && al16(a_mean);          // lda % 4 == 0 and lda >= G: lda >= roundup4(G)
-    const int V = vec ? 4 : 1;
-    const int nseg = ((G + V - 1) / V + 255) / 256;
-    int rows_per = 0;
-    const int S = group_slices(B, G, K, V, &rows_per);
-    GroupArgs a{a_mean, no_sf ? nullptr : sf, codes, lda, ldg, sum_acc, sumsq_acc, workspace,
-                B, G, K, S, rows_per, linear ? 1 : 0, lg ? 1 : 0};
-    const dim3 grid(nseg, K * S);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(group_moments_kernel<4>, grid, dim3(256), 0, s, a);
-    else     hipLaunchKernelGGL(group_moments_kernel<1>, grid, dim3(256), 0, s, a);
-    if (S > 1) {
-        const long items = (long)K * G;
-        hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
-                           workspace, S, K, G, ldg, sum_acc, sumsq_acc);
-    }
-    return (int)hipGetLastError();
-}
-
 extern "C" int dcahip_loss_finalize(const double* partials, int n_partials, double scale,
                                     float* loss_out, void* stream) {
     if (!partials || n_partials <= 0 || !loss_out) return DCAHIP_EINVAL;
@@ -1001,24 +595,5 @@ extern "C" int dcahip_step_end(const float* loss, double weight, float* hist, in
                                double* acc, long long* cursor, int advance, void* stream) {
     hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
                        loss, weight, hist, rows_per_slot, acc, cursor, advance);
-    return (int)hipGetLastError();
-}
-
-extern "C" int dcahip_zinb_heads_infer(const float* a_mean, const float* a_disp, const float* a_pi,
-                                       long lda, const float* sf, int B, int G, float* mean_sf,
-                                       float* theta, float* pi, long ldo, int flags, void* stream) {
-    if (B <= 0 || G <= 0 || !sf) return DCAHIP_EINVAL;
-    if ((mean_sf && !a_mean) || (theta && !a_disp) || (pi && !a_pi)) return DCAHIP_EINVAL;
-    const int Gp = (G + 3) & ~3;
-    bool vec = (lda % 4 == 0) && (ldo % 4 == 0) && lda >= Gp && ldo >= Gp;
-    const void* ps[6] = {a_mean, a_disp, a_pi, mean_sf, theta, pi};
-    for (const void* p : ps) vec = vec && (p == nullptr || al16(p));
-    InferArgs a{a_mean, a_disp, a_pi, sf, mean_sf, theta, pi, lda, ldo, B, G, (flags & DCAHIP_NLL_MSE) ? 1 : 0};
-    const int V = vec ? 4 : 1;
-    const long total = (long)B * (((G + V - 1) / V + 255) / 256);
-    const int grid = (int)(total < 4096 ? total : 4096);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec) hipLaunchKernelGGL(heads_infer_kernel<4>, dim3(grid), dim3(256), 0, s, a);
-    else     hipLaunchKernelGGL(heads_infer_kernel<1>, dim3(grid), dim3(256), 0, s, a);
     return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // Shared device arithmetic of the NB / ZINB likelihood kernels (dcahip_zinb.hip: standalone
 // loss + gradient pass; dcahip_heads.hip: the fused heads kernel).  gfx950, wave64.
+// Also included by dcahip_score.hip (the per-cell / per-gene NLL of a fitted model, through head_acts + nll_elem).
 //
 // Reference arithmetic restated here: dca/network.py:38-39 (MeanAct, DispAct),
 // dca/layers.py:21,85, dca/loss.py:72-114 (NB.loss), dca/loss.py:122-156 (ZINB.loss).

@@ -1,5 +1,5 @@
 """Case table and fp64 reference of the inference heads kernel's edge tests (dcahip_zinb_heads_infer, heads_infer_kernel<V>
-in dca_amd/csrc/dcahip_zinb.hip): tests/test_heads_infer_gpu.py runs the cases on the device, tests/test_heads_infer_cases_cpu.py
+in dca_amd/csrc/dcahip_score.hip): tests/test_heads_infer_gpu.py runs the cases on the device, tests/test_heads_infer_cases_cpu.py
 checks on the host that the table reaches every path of the kernel and that the reference is what the tests take it for.
 No torch here, so that the CPU half loads it.
 

@@ -10,7 +10,7 @@ Host arithmetic restated from dcahip_zinb_nll (grid(), vec_predicate(), instanti
     V    = 4 if vec else 1;  nvec = ceil(G / V);  nseg = ceil(nvec / 256);  gx = min(nseg, 2048);  gy = min(2048 // gx, B)
     a workgroup (x, y) walks the rows y, y + gy, y + 2 gy, ... of gene segment x and writes partial y * gx + x
     NB / ZINB, vec:      gradients -> zinb_nll_rows_kernel<HAS_PI, CONST_DISP, 0>   (B * ldd < 2^32)
-                         loss only -> zinb_nll_compact_kernel<HAS_PI, CONST_DISP, false>
+                         loss only -> zinb_nll_compact_kernel<HAS_PI, CONST_DISP>
     NB / ZINB, not vec:  zinb_nll_kernel<HAS_PI, CONST_DISP, GRAD, 1>
     Poisson / MSE:       zinb_nll_kernel<false, false, GRAD, V, LOSS>
 (zinb_nll_kernel<HAS_PI, CONST_DISP, true, 4> needs B * ldd >= 2^32, more than 16 GB of gradients: no case reaches it.)
@@ -120,7 +120,7 @@ def instantiation(flags, grad, vec, B=1, ldd=0):
     if vec and fits and grad:
         return 'zinb_nll_rows_kernel<%d,%d,0>' % (has_pi, cdisp)
     if vec and fits:
-        return 'zinb_nll_compact_kernel<%d,%d,false>' % (has_pi, cdisp)
+        return 'zinb_nll_compact_kernel<%d,%d>' % (has_pi, cdisp)
     return 'zinb_nll_kernel<%d,%d,%s,%d>' % (has_pi, cdisp, g, 4 if vec else 1)
 
 

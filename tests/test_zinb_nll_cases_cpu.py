@@ -43,7 +43,7 @@ def test_every_case_and_trigger_reaches_the_form_it_claims():
                     elif scalar:
                         want = 'zinb_nll_kernel<%d,%d,%s,1>' % (flags & 1, flags >> 1 & 1, str(grad).lower())
                     else:
-                        want = ('zinb_nll_rows_kernel<%d,%d,0>' if grad else 'zinb_nll_compact_kernel<%d,%d,false>') % (flags & 1, flags >> 1 & 1)
+                        want = ('zinb_nll_rows_kernel<%d,%d,0>' if grad else 'zinb_nll_compact_kernel<%d,%d>') % (flags & 1, flags >> 1 & 1)
                     assert kernel == want, (c.name, flags, grad, trig, kernel)
                     reached.add(kernel)
                     assert g.n_partials == g.gx * g.gy <= C.GRID_CAP and g.gy <= c.B
@@ -76,7 +76,7 @@ def test_the_device_runs_reach_every_instantiation():
     assert set(by) == C.every_instantiation()
     for f in (0, 1, 2, 3):
         p, c = f & 1, f >> 1
-        assert ('deep_vec', None) in by['zinb_nll_compact_kernel<%d,%d,false>' % (p, c)]
+        assert ('deep_vec', None) in by['zinb_nll_compact_kernel<%d,%d>' % (p, c)]
         assert ('deep_vec', None) in by['zinb_nll_rows_kernel<%d,%d,0>' % (p, c)]
         for g in ('true', 'false'):
             k = by['zinb_nll_kernel<%d,%d,%s,1>' % (p, c, g)]
@@ -160,3 +160,52 @@ def test_oracle_is_finite_and_r_class_positive(name):
                 assert not bad.any() and all(v[1] == 0 for v in rep.values())
                 rep, bad = C.grad_report(name, flags, ridge, h, ref + 1.01 * b)
                 assert bad.all()
+
+
+def _kernel_label(text):
+    """'name<a, b, ..>' (demangled or a label of _zinb_nll_cases) -> (name, args) with true / false as 1 / 0 and
+    zinb_nll_kernel's defaulted LOSS = 0 written out."""
+    import re
+    name, args = re.search(r'(\w+)<([^>]*)>', text).groups()
+    args = tuple({'true': '1', 'false': '0'}.get(x.strip(), x.strip()) for x in args.split(','))
+    return name, args + ('0',) * (name == 'zinb_nll_kernel' and len(args) == 4)
+
+
+def test_no_kernel_form_is_compiled_that_no_call_reaches():
+    """dcahip_zinb.hip compiled for the device alone: the zinb_nll* kernels in the code object are exactly the forms an
+    argument list can reach -- every_instantiation(), the four V = 4 general kernels behind B * ldd >= 2^32 and the eight
+    plane forms of the row-pair kernel, 36 in all -- and each stays inside what its launch bounds and today's figures allow:
+    128 registers for the two __launch_bounds__(256, 4) kernels, 16 bytes of scratch per lane, and for the loss-only kernel
+    the 35 872 bytes of LDS of its queue of seven-word entries (4 waves x 320 entries x 28 bytes + 32)."""
+    import os
+    import re
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I' + os.path.join(root, 'include'),
+                          '--cuda-device-only', '-c', os.path.join(root, 'dca_amd', 'csrc', 'dcahip_zinb.hip'), '-o', os.devnull,
+                          '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True, check=True).stderr
+    kernels, cur = {}, None
+    for line in out.splitlines():
+        m = re.search(r'remark: +Function Name: (\S+)', line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r'remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)', line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    names = list(kernels)
+    demangled = subprocess.run(['c++filt'] + names, capture_output=True, text=True, check=True).stdout.split('\n')
+    got = {_kernel_label(d): kernels[n] for n, d in zip(names, demangled) if 'zinb_nll' in d}
+    want = {_kernel_label(k) for k in C.every_instantiation()}
+    want |= {_kernel_label(C.instantiation(f, True, True, 2 ** 20, 2 ** 12)) for f in (0, 1, 2, 3)}
+    want |= {('zinb_nll_rows_kernel', (str(f & 1), str(f >> 1), pl)) for f in (0, 1, 2, 3) for pl in ('1', '2')}
+    assert len(want) == 36
+    assert set(got) == want, (sorted(set(got) - want), sorted(want - set(got)))
+    for (name, args), r in got.items():
+        assert r['ScratchSize'] <= 16, (name, args, r)
+        if name in ('zinb_nll_compact_kernel', 'zinb_nll_rows_kernel'):              # __launch_bounds__(256, 4)
+            assert r['VGPRs'] + r['AGPRs'] <= 128, (name, args, r)
+        if name == 'zinb_nll_compact_kernel':
+            assert r['LDS Size'] <= 35872, (name, args, r)

@@ -5,7 +5,7 @@ named here and walks the rows / fills the queue it was written for).
 Which test reaches which instantiation (P = HAS_PI, C = CONST_DISP; flags 1, 0, 3, 2 give every (P, C)):
     zinb_nll_rows_kernel<P, C, 0>            test_vector_form: the gradient call of every case (deep_vec: 2 or 3 rows per
                                              workgroup; its gradients serve as the comparison value of the loss only)
-    zinb_nll_compact_kernel<P, C, false>     test_vector_form: the loss-only call -- deep_vec walks 2 or 3 rows per workgroup
+    zinb_nll_compact_kernel<P, C>            test_vector_form: the loss-only call -- deep_vec walks 2 or 3 rows per workgroup
                                              through the look-ahead, clamped at the batch end for some workgroups only, with a
                                              queue remainder of 0, 1 and 63 carried into rows that push 256 more (319 of the 320
                                              entries) and a last flush over entries of several rows; also the loss-only calls of
@@ -145,7 +145,7 @@ def run_forms(ops, name, flags, ridge, trigger, planes=True):
 
 @pytest.mark.parametrize('name,flags,ridge', C.VECTOR_RUNS)
 def test_vector_form(ops, name, flags, ridge):
-    """zinb_nll_compact_kernel<.., false> (loss only) and zinb_nll_rows_kernel<.., 0> (gradients) on 16-byte aligned
+    """zinb_nll_compact_kernel<..> (loss only) and zinb_nll_rows_kernel<.., 0> (gradients) on 16-byte aligned
     operands.  deep_vec's gradients are covered element-wise at the same shape by test_zinb_nll_row_pairs_and_planes and
     test_zinb_planes_h2_gpu.py: here its gradient call gives the loss the loss-only call is compared with."""
     k, g = C.reaches(C.BY_NAME[name].B, C.BY_NAME[name].G, flags, False)
